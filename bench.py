@@ -16,7 +16,18 @@ Workload (BASELINE.json metric: "Gpoints/s projected + CMA-ES iters/s, 100M-vert
 float32 planes, row-sharded over the ranks (strong scaling: the total is fixed).
 
   leg 1 (the timed "steps" -> `value`): one step = one single-pose forward projection of the
-        whole DSM (every rank projects its shard, no collective).  Gpoints/s = vertices / t.
+        whole DSM (every rank projects its shard, no collective).  Gpoints/s = vertices / t;
+        `ms_per_step` = the wall time of the K timed steps / K.
+
+A plain run does leg 1 only: set-up, W warm-up steps, K timed steps, the line.  `--full` adds
+everything below (and the single-launch median, the PCIe-inclusive figures and the parity spot
+check against the float64 oracle of leg 1), each leg still switchable off by its --no-* flag.
+
+`--dump-outputs DIR` (rank 0): after the timed steps, the pixel coordinates the last step computed,
+as `Points.fetch` returns them in the run's precision (float32 / float64), for a fixed seeded
+sample of at most DUMP_SAMPLE points: DIR/u.npy, DIR/v.npy.  The inputs are generated from fixed
+seeds, so two runs with the same arguments can be compared output for output.
+
   `cma`: CMA-ES generations = ask -> population evaluation on the GPU(s) with ONE RCCL all-reduce of
         the P+1 partial sums -> tell; pop = 2048, D = 21 (BASELINE config 5); kernel / all-reduce
         split from HIP events inside the library.
@@ -69,6 +80,8 @@ ROOFLINE_KEYS = ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel
                  "c3_iters_per_s", "c3_kernel_ms", "c3_valu_frac",
                  "raster_ms_per_frame", "raster_hbm_frac", "raster_binding_roof_frac", "raster_int32_indices_ms_per_frame")
 ROOFLINE_CAP = 24
+DUMP_SAMPLE = 2_000_000    # points written by --dump-outputs: u and v, 16 MB in float32, 32 MB in float64
+DUMP_SEED = 7
 
 
 def driver_roofline(flat):
@@ -88,6 +101,11 @@ def parse():
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
     ap.add_argument("--pop", type=int, default=2048)
     ap.add_argument("--dims", type=int, default=21, choices=[9, 21])
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg (CMA-ES, float64, 10 M configs, render, drop-in calls, next rows, CPU baseline, live PMC "
+                         "traffic, parity spot check); without it only the timed projection steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the projected u, v of the last step (a fixed seeded sample) to DIR/*.npy")
     ap.add_argument("--cma-steps", type=int, default=50, help="generations timed at pop 2048 / D 21 (SURVEY 8(d) c5: 50, whatever --steps is)")
     ap.add_argument("--c3-steps", type=int, default=100, help="generations timed at 10 M x pop 256 (SURVEY 8(d) c3: 100)")
     ap.add_argument("--no-cma", action="store_true")
@@ -147,6 +165,18 @@ def launch_times(L, fn, launches=24):
         L.event_record(3 + i)
     L.synchronize()
     return np.array([L.event_elapsed_ms(2 + i, 3 + i) for i in range(launches)])
+
+
+def dump_outputs(out_dir, pts, precision):
+    """--dump-outputs: the projected pixels the last timed step left on the device, in the run's own precision, at the
+    sorted indices of a fixed seeded sample (all points when there are at most DUMP_SAMPLE)"""
+    u, v = pts.fetch(np.float32 if precision == "f32" else np.float64)
+    if len(u) > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, len(u), DUMP_SAMPLE))
+        u, v = u[idx], v[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "u.npy"), u)
+    np.save(os.path.join(out_dir, "v.npy"), v)
 
 
 def selftest(ctl, args, emit=print):
@@ -651,9 +681,10 @@ def main():
     from alproj_amd import _lib as L
     from alproj_amd import dist as adist
     from alproj_amd import synthetic as syn
-    from alproj_amd.cma import CMA
-    from alproj_amd.optimize import bounds_to_array      # the product's own host logic
-    from oracle import ref_numpy as orc       # checker (parity spot check) and cpu_baseline only
+    if args.full:
+        from alproj_amd.cma import CMA
+        from alproj_amd.optimize import bounds_to_array      # the product's own host logic
+        from oracle import ref_numpy as orc       # checker (parity spot check) and cpu_baseline only
 
     if args.debug_share_device == "nocomm":
         L.init(0)
@@ -708,9 +739,10 @@ def main():
     t_up = time.perf_counter()
     pts = L.Points(xyz_l, origin, args.precision)
     t_up = time.perf_counter() - t_up              # host -> device upload of the vertex array (not in `value`)
-    t_up2 = time.perf_counter()                    # ... and once more: the first large copy of a process pays the
-    L.Points(xyz_l, origin, args.precision).close()   # runtime's one-off set-up of its pageable-memory path
-    t_up2 = time.perf_counter() - t_up2
+    if args.full:
+        t_up2 = time.perf_counter()                    # ... and once more: the first large copy of a process pays the
+        L.Points(xyz_l, origin, args.precision).close()   # runtime's one-off set-up of its pageable-memory path
+        t_up2 = time.perf_counter() - t_up2
     t_gen = time.perf_counter() - t_gen
     pv_truth = L.params_vector(truth)
 
@@ -721,19 +753,22 @@ def main():
     kern_s = dev_ms / args.steps / 1e3
     bpv = BYTES_PER_VERTEX[args.precision]
     achieved = n_local * bpv / kern_s
-    per_launch = launch_times(L, lambda: pts.project(pv_truth))      # one event pair per launch: the median next to the mean
+    if args.dump_outputs and ctl.rank == 0:
+        dump_outputs(args.dump_outputs, pts, args.precision)
 
-    t_fetch = time.perf_counter()
-    uu_all, vv_all = pts.fetch(np.float32)          # device -> host of all projected pixels
-    t_fetch = time.perf_counter() - t_fetch
-    del uu_all, vv_all
-    # parity spot check on the bench workload itself (outside the timed region)
-    step = max(1, n_local // 40000)
-    cnt = (n_local - 1) // step
-    u, v = pts.fetch_strided(0, step, cnt)
-    sample = xyz_l[0:cnt * step:step].astype(np.float64)
-    ref = orc.project_points(sample, truth)
-    parity = parity_report(np.stack([u, v], 1), ref, truth["w"])
+    if args.full:
+        per_launch = launch_times(L, lambda: pts.project(pv_truth))      # one event pair per launch: the median next to the mean
+        t_fetch = time.perf_counter()
+        uu_all, vv_all = pts.fetch(np.float32)          # device -> host of all projected pixels
+        t_fetch = time.perf_counter() - t_fetch
+        del uu_all, vv_all
+        # parity spot check on the bench workload itself (outside the timed region)
+        step = max(1, n_local // 40000)
+        cnt = (n_local - 1) // step
+        u, v = pts.fetch_strided(0, step, cnt)
+        sample = xyz_l[0:cnt * step:step].astype(np.float64)
+        ref = orc.project_points(sample, truth)
+        parity = parity_report(np.stack([u, v], 1), ref, truth["w"])
 
     traffic, traffic_src = (None, None)
     if args.precision == "f32":
@@ -765,26 +800,27 @@ def main():
                      "frac": achieved / HBM_PEAK, "traffic": traffic,
                      "traffic_source": f"{traffic_src} (rocprofv3 --pmc, bytes/vertex x vertices per launch)" if traffic else None,
                      "kernel": "project_kernel", "kernel_ms": kern_s * 1e3,
-                     "kernel_ms_median_of_single_launches": float(np.median(per_launch)), "single_launches": len(per_launch),
-                     "bytes_per_vertex": bpv, "vertices_per_launch": n_local,
-                     "scaled_1e-5_pass": parity["scaled_1e-5_pass_fraction"],
-                     "strict_1e-5_relative_pass": parity["strict_1e-5_relative_pass_fraction"]},
-        "parity": parity,
+                     "bytes_per_vertex": bpv, "vertices_per_launch": n_local},
         "device": info, "setup_s": t_gen,
         # the communicator the library itself reports (ncclCommInitRank succeeded on every rank), and where every rank ran
         "rccl": {"rank": comm_rank, "nranks": comm_world, "ranks": rank_devices} if not args.debug_share_device else
                 "NONE: --debug-share-device (all ranks on device 0, no communicator: this line is a control-flow check, not a measurement)",
-        # SURVEY 8(d) c2 asks for the end-to-end figure beside the kernel figure; it is never `value`
-        "pcie_inclusive": {"upload_s": t_up, "upload_s_second_time": t_up2,
-                           "upload_gb_per_s_second_time": xyz_l.nbytes / t_up2 / 1e9, "fetch_uv_s": t_fetch,
-                           "gpoints_per_s_one_pass_incl_upload_and_fetch":
-                               n_local / (t_up + ms_per_step / 1e3 + t_fetch) / 1e9},
     }
+    if args.full:
+        out["roofline"].update({"kernel_ms_median_of_single_launches": float(np.median(per_launch)), "single_launches": len(per_launch),
+                                "scaled_1e-5_pass": parity["scaled_1e-5_pass_fraction"],
+                                "strict_1e-5_relative_pass": parity["strict_1e-5_relative_pass_fraction"]})
+        out["parity"] = parity
+        # SURVEY 8(d) c2 asks for the end-to-end figure beside the kernel figure; it is never `value`
+        out["pcie_inclusive"] = {"upload_s": t_up, "upload_s_second_time": t_up2,
+                                 "upload_gb_per_s_second_time": xyz_l.nbytes / t_up2 / 1e9, "fetch_uv_s": t_fetch,
+                                 "gpoints_per_s_one_pass_incl_upload_and_fetch":
+                                     n_local / (t_up + ms_per_step / 1e3 + t_fetch) / 1e9}
 
     # ---------------------------------------------------------------- CMA-ES generations (config 5)
     obs = None
     targets = syn.TARGETS_D9 if args.dims == 9 else syn.TARGETS_D21
-    if not args.no_cma:
+    if args.full and not args.no_cma:
         uu, vv = pts.fetch(np.float32)
         rng = np.random.default_rng(1 + ctl.rank)
         obs = np.stack([uu, vv], 1)
@@ -842,7 +878,7 @@ def main():
                                     "cma_d9_first_phase_kernel_variant": variant9})
 
     # ---------------------------------------------------------------- float64 parity mode (1 GPU)
-    if ctl.world == 1 and not args.no_f64 and args.precision == "f32":
+    if args.full and ctl.world == 1 and not args.no_f64 and args.precision == "f32":
         p64 = L.Points(xyz_l, origin, "f64")
         k64 = max(20, min(args.steps, 40))
         wall64, dev64 = timed(ctl, L, lambda: p64.project(pv_truth), k64, 3)
@@ -875,7 +911,7 @@ def main():
         p64.close()
 
     # ---------------------------------------------------------------- BASELINE configs 2 and 3: 10 M vertices (1 GPU)
-    if ctl.world == 1 and not args.no_10m and n_total > 20_000_000:
+    if args.full and ctl.world == 1 and not args.no_10m and n_total > 20_000_000:
         n10 = syn.grid_side(10_000_000)
         s10 = syn.surface(n10)
         x10 = syn.vert_to_xyz_local(s10["vert"])
@@ -950,7 +986,7 @@ def main():
         del s10, x10, o10
 
     # ---------------------------------------------------------------- depth raster (1 GPU)
-    if ctl.world == 1 and not args.no_raster:
+    if args.full and ctl.world == 1 and not args.no_raster:
         cam = syn.base_params(n_side)              # camera on the surface's west edge
         pv_cam = L.params_vector(cam)
         k_r = min(args.steps, 10)
@@ -1042,7 +1078,7 @@ def main():
 
     # ---------------------------------------------------------------- the reference-typed call pair (1 GPU)
     df_full = ras_dev = None
-    if ctl.world == 1 and not args.no_dropin and not args.no_raster:
+    if args.full and ctl.world == 1 and not args.no_dropin and not args.no_raster:
         out["dropin_call"], df_full, _sim = dropin_leg(L, syn, surf, n_side, syn.base_params(n_side))
         # f4: set_gcp's gather of 1 127 GCPs from the resident coordinate image (gcp.py:644-648)
         from alproj_amd import project as aproj
@@ -1080,7 +1116,7 @@ def main():
                                                                                    "worst": max(walls) * 1e3, "calls": len(walls)},
                                     "kernel_ms": k_ms, "kernel_sections": k_n}
         aproj.clear_mesh_cache()
-    if ctl.world == 1 and not args.no_next_rows:
+    if args.full and ctl.world == 1 and not args.no_next_rows:
         out["next_rows"] = next_rows_leg(L, syn, orc, df_full, ras_dev)
         if "f2_device_fed" in out and "f2_rasterize_points" in out["next_rows"]:
             out["f2_device_fed"]["byte_identical_to_the_table_path"] = out["next_rows"]["f2_rasterize_points"].pop("equals_device_fed_raster")
@@ -1100,7 +1136,7 @@ def main():
     # the reference's own problem size: 1127 GCPs, pop 50, D = 9, 300 generations, Huber f = 10
     # (docs/usage.md:335, example.py:51-54); BASELINE.md measured 61.7 ms/generation for the
     # reference's inner loop (without the sampler) in the survey container
-    if ctl.world == 1 and not args.no_cma:
+    if args.full and ctl.world == 1 and not args.no_cma:
         import pandas as pd
         from alproj_amd import optimize as aopt
         tp = syn.truth_params(316)
@@ -1123,11 +1159,11 @@ def main():
                                 "reference_ms_per_generation_survey_container": 61.7}
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N=1)
-    if ctl.world == 1 and not args.no_cpu_baseline:
+    if args.full and ctl.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(orc, truth, base, targets, bounds_to_array, xyz_l, obs, n_total, args.pop)
         out["speedup_vs_cpu_baseline"] = gpts / out["cpu_baseline"]["value"]
 
-    if ctl.world > 1 and ctl.rank == 0:
+    if args.full and ctl.world > 1 and ctl.rank == 0:
         exp = expectation_from_one_gpu(ctl.world, out.get("cma", {}).get("all_reduce_ms"), n_total, args.pop if "cma" in out else None)
         if exp:
             exp["projection_measured_over_expected"] = (out["roofline"]["kernel_ms"] / exp["projection_kernel_ms"]) if exp.get("projection_kernel_ms") else None
@@ -1137,7 +1173,7 @@ def main():
             out["expected_from_1gpu"] = exp
     pts.close()
     # roofline.traffic, live: after everything else (the GPU is idle, the big host arrays are still this process's own)
-    if ctl.world == 1 and args.precision == "f32" and not args.no_live_traffic and not args.debug_share_device:
+    if args.full and ctl.world == 1 and args.precision == "f32" and not args.no_live_traffic and not args.debug_share_device:
         t_pmc = time.perf_counter()
         measured, why = live_traffic(n_total)
         out["roofline"]["traffic_committed_summary"] = out["roofline"].get("traffic")

@@ -2,6 +2,7 @@
 driver keeps (task 1).  No GPU: the split is exercised on the committed N = 1 line and on a canned one."""
 import json
 import os
+import sys
 
 import pytest
 
@@ -197,3 +198,33 @@ db.commit()
         assert got is None and "did not finish within" in why
     assert _tree_listing(ROOT) == before                         # nothing created in (or removed from) the checkout
     assert os.listdir(scratch) == []                             # and the temporary directory is gone
+
+
+def test_dump_outputs_is_a_fixed_sample_in_the_runs_precision(tmp_path, monkeypatch):
+    """--dump-outputs: u, v as the run's precision returns them, the same seeded sample on every run, within 64 MB; a plain
+    run is leg 1 only (--full off by default)"""
+    import numpy as np
+
+    class Pts:
+        def __init__(self, n):
+            self.u = np.arange(n, dtype=np.float64) * 0.5
+
+        def fetch(self, dtype=np.float64):
+            return self.u.astype(dtype), (-self.u).astype(dtype)
+
+    assert bench.DUMP_SAMPLE * 2 * 8 <= 64e6
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    for prec, dt in (("f32", np.float32), ("f64", np.float64)):
+        got = []
+        for k in range(2):
+            d = tmp_path / f"{prec}{k}"
+            bench.dump_outputs(str(d), Pts(50_000), prec)
+            u, v = np.load(d / "u.npy"), np.load(d / "v.npy")
+            assert u.dtype == dt == v.dtype and 900 < len(u) <= 1000 and np.all(np.diff(u) > 0) and np.array_equal(v, -u)
+            got.append(u)
+        assert np.array_equal(*got)
+    bench.dump_outputs(str(tmp_path / "all"), Pts(300), "f64")
+    assert np.array_equal(np.load(tmp_path / "all" / "u.npy"), Pts(300).u)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    args = bench.parse()
+    assert args.steps == 7 and not args.full and args.dump_outputs is None
