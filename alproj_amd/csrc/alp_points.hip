@@ -273,7 +273,7 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
         // 219.5 -> 215.2 | 95.7 -> 93.4 -- never slower, so it is the rule.  Stripes of k groups, k grown with the point count
         // (about two stripes per resident slot and tile column for small sets, up to 16 groups = ~25 000 points for large ones:
         // the timings are flat from 4 to 16 groups and the partial-sum buffer shrinks with the stripe count).
-        // The sums depend on the shape in the last bits only (1e-9 relative between shapes: other group boundaries).
+        // The sums depend on the shape in the last bits only (up to ~3e-8 relative between shapes: other group boundaries).
         const int tiles = (int)((P + POP_TC - 1) / POP_TC);
         if (tiles >= 2) {
             int64_t k = (int64_t)((double)rows / ((double)VV * 2.12 * (double)lo) + 0.5);      // groups of V rows per stripe
@@ -293,9 +293,9 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
         const int64_t lo = (int64_t)ctx().cu_count * 3;                  // one round of the three resident workgroups per CU
         if (nblk > cap) nblk = (int)(cap > lo ? cap : lo);
     }
-    // tuning hook: "stripes,ytiles".  float32: any value gives the same losses (float64 additions of float32 group sums of this
-    // magnitude are exact).  float64: the stripe count sets the ORDER of the float64 additions, so the last bits of the losses move
-    // with it -- a development switch, not a setting
+    // tuning hook: "stripes,ytiles".  The stripe count moves the last bits of the losses in either precision: it decides which rows
+    // go through the V-wide, the 2-wide and the masked single-row groups (float32: other group sums, up to ~3e-8 relative) and sets the
+    // ORDER of the float64 additions.  Same grid, same bits (tests/test_gpu_popeval_grid.py) -- a development switch, not a setting
     if (const char *e = getenv("ALP_POP_GRID")) {
         const int tiles = (int)((P + PopCfg<T>::TC - 1) / PopCfg<T>::TC);
         int a = 0, b = 0;

@@ -17,6 +17,7 @@ import pandas as pd
 import pytest
 
 from oracle import ref_numpy as orc
+from tests.popeval_cases import oracle_r2, pole_a2_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -459,20 +460,6 @@ def test_population_nan_semantics(L):
     assert np.isnan(losses[0]) and np.isfinite(losses[1]) and amin == 1
 
 
-def _oracle_r2(xyz, p):
-    """r2 of optimize.py:105-108 for every point, formed operation by operation as oracle.ref_numpy.project_points /
-    distort_points form it (so that a denominator built from it is zero in the ORACLE's arithmetic)"""
-    hom = np.vstack((np.asarray(xyz, dtype=np.float64).T, np.ones((1, len(xyz)))))
-    kmat = orc.intrinsic_mat(p["fov"], p["w"], p["h"], p["cx"], p["cy"])
-    emat = orc.extrinsic_mat(p["pan"], p["tilt"], p["roll"], p["x"], p["y"], p["z"])
-    img = np.dot(kmat, np.dot(emat, hom)[:3, :])
-    uv = np.array([p["w"] - img[0, :] / img[2, :], img[1, :] / img[2, :]]).T
-    c = np.array([(p["w"] - 1) / 2, (p["h"] - 1) / 2], dtype="float32")
-    x = (uv[:, 0] - c[0]) / c[0]
-    y = (uv[:, 1] - c[1]) / c[1]
-    return ((x ** 2 + y ** 2) ** 0.5) ** 2
-
-
 @pytest.mark.parametrize("variant", ["shared_pose", "general"])
 @pytest.mark.parametrize("kind,fs", [(0, 0.0), (1, 10.0)], ids=["mean_dist", "huber"])
 @pytest.mark.parametrize("prec", ["f64", "f32"])
@@ -490,7 +477,7 @@ def test_pole_of_one_lens_denominator_is_an_infinite_loss(L, prec, kind, fs, var
     from alproj_amd.cma import CMA
     truth = dict(syn.truth_params(316), k4=-0.5, k5=0.0, k6=0.0)
     xyz = syn.gcp_points(400, truth, seed=31, margin=-0.25)            # a quarter of the frame beyond each edge
-    r2 = _oracle_r2(xyz, truth)
+    r2 = oracle_r2(xyz, truth)
     i0 = int(np.argmin(np.abs(r2 - 1.4)))                               # den_x = 1 - r2/2 ~ 0.3 there
     assert 1.2 < r2[i0] < 1.6
     # nobody else near a pole of either denominator of the SANE candidates (den_x = 1 - r2/2, den_y = 1 + a2 - r2/2)
@@ -501,14 +488,7 @@ def test_pole_of_one_lens_denominator_is_an_infinite_loss(L, prec, kind, fs, var
     assert len(xyz) > 100
     uv = orc.project_points(xyz, truth) + np.random.default_rng(31).normal(0, 1.0, (len(xyz), 2))
     assert np.isfinite(uv).all()
-    # W: how far the device's r2 may lie from numpy's.  float64: the two fold the pose differently (R.(p - cam) against E.[p;1]
-    # with |t| ~ 4e6: ~1e-12 relative = thousands of ulps); float32: the stored coordinates are rounded (~1e-6 = some ten ulps)
-    T, I, W = (np.float64, np.int64, 1 << 17) if prec == "f64" else (np.float32, np.int32, 400)
-    centre = np.array([r2[i] / 2], dtype=T)
-    targets = (centre.view(I)[0] + np.arange(-W, W + 1, dtype=I)).view(T)   # positive floats: consecutive bit patterns
-    assert np.all(np.diff(targets) > 0) and 0.5 < targets[0] and targets[-1] < 2
-    a2 = targets.astype(np.float64) - 1.0                               # 1 + a2 == t exactly (Sterbenz: t in [0.5, 2])
-    assert np.array_equal((1.0 + a2).astype(T), targets)
+    a2 = pole_a2_steps(r2[i], -0.5, prec)                               # 1 + a2 steps ulp by ulp through r2 / 2
     cand = np.tile(L.params_vector(truth), (len(a2) + 2, 1))
     cand[2:, L.PARAM_KEYS.index("a2")] = a2
     cand[1, L.PARAM_KEYS.index("a1")] += 0.01                           # two sane candidates in front
@@ -775,11 +755,24 @@ def test_dsm_10m_properties(L, prec):
         cand = _cand_matrix(L, base, syn.TARGETS_D9, bounds, rng.uniform(0.4, 0.6, (256, 9)))
         whole, amin_w = pts.eval_population(cand, L.LOSS_HUBER, 10.0)
         assert whole.shape == (256,) and amin_w == int(np.argmin(whole))
-        # three of the 256 candidates against the float64 oracle on all 10 M vertices
+        # the only 10 M check against the oracle runs on the production grid: stripes of several rows (the V-wide and 2-wide
+        # groups of pop_walk_stripe) and, in float32, every candidate tile in a column of its own
+        _, stripes, ytiles = pts.eval_population_info()
+        rows = -(-N // 256)
+        assert -(-rows // stripes) >= 2, (stripes, ytiles)
+        if prec == "f32":
+            assert ytiles == 2, (stripes, ytiles)
+        mean_d, amin_m = pts.eval_population(cand, L.LOSS_MEAN_DIST, 0.0)
+        assert pts.eval_population_info()[1:] == (stripes, ytiles) and amin_m == int(np.argmin(mean_d))
+        # four of the 256 candidates against the float64 oracle on all 10 M vertices, both losses
         xyz64 = xyz_l.astype(np.float64)
         for c in (0, 131, 255, amin_w):
-            ref_l = orc.huber(obs, orc.project_points(xyz64, orc.vector_to_params(cand[c])), 10.0)
+            proj = orc.project_points(xyz64, orc.vector_to_params(cand[c]))
+            ref_l = orc.huber(obs, proj, 10.0)
             assert whole[c] == pytest.approx(ref_l, rel=1e-9 if prec == "f64" else 1e-5), c
+            ref_m = orc.mean_distance(obs, proj)
+            assert mean_d[c] == pytest.approx(ref_m, rel=1e-9 if prec == "f64" else 1e-5), c
+            del proj
         del xyz64
     cut = 3_777_777
     parts = []

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development: launch-shape sweep of the population kernel for populations of a few candidate tiles
-(ALP_POP_GRID = "stripes,ytiles"; the losses do not depend on it).   python3 tools/sweep_popeval_grid.py [N] [P ...]"""
+(ALP_POP_GRID = "stripes,ytiles"; it moves the last bits of the losses only).   python3 tools/sweep_popeval_grid.py [N] [P ...]"""
 import os
 import sys
 
