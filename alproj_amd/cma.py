@@ -131,6 +131,25 @@ class CMA:
     def sigma(self):
         return self._sigma
 
+    # ------------------------------------------------------------------ state
+    def get_state(self):
+        """The evolving state as a dict of copies: mean, sigma, C, p_sigma, pc, g (the device loop of the generation,
+        alproj_amd._lib.CmaDevice, takes and returns this)."""
+        return {"mean": self._mean.copy(), "sigma": float(self._sigma), "C": self._C.copy(), "p_sigma": self._p_sigma.copy(),
+                "pc": self._pc.copy(), "g": int(self._g)}
+
+    def set_state(self, state):
+        """Replace the evolving state by ``state`` (a dict of get_state's keys); the cached eigendecomposition is cleared."""
+        n = self._n
+        mean = np.array(state["mean"], dtype=np.float64).reshape(n)
+        C = np.array(state["C"], dtype=np.float64).reshape(n, n)
+        p_sigma = np.array(state["p_sigma"], dtype=np.float64).reshape(n)
+        pc = np.array(state["pc"], dtype=np.float64).reshape(n)
+        self._mean, self._C, self._p_sigma, self._pc = mean, C, p_sigma, pc
+        self._sigma = float(state["sigma"])
+        self._g = int(state["g"])
+        self._B, self._D = None, None
+
     # ------------------------------------------------------------------ sampling
     def _eigen(self):
         if self._B is not None and self._D is not None:

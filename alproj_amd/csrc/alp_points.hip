@@ -22,45 +22,10 @@
 #include <vector>
 
 #include "alp_point_kernels.h"
+#include "alp_points_internal.h"
 
 
 using namespace alp;
-
-// ------------------------------------------------------------------ the handle
-struct alp_points {
-    int64_t n = 0;
-    int64_t n_pad = 0;
-    int precision = ALP_F32;
-    double origin[3] = {0, 0, 0};
-    // the planes live in at most three allocations (a hipMalloc / hipFree pair of this size costs ~1 ms: seven of them were a
-    // third of what compute_residuals spent at 10 M points): coordinates at creation, observed pixels at alp_points_set_observed*,
-    // projected pixels at the first alp_project
-    void *slab_xyz = nullptr, *slab_obs = nullptr, *slab_uv = nullptr;
-    void *x = nullptr, *y = nullptr, *z = nullptr;
-    void *uo = nullptr, *vo = nullptr;
-    void *u = nullptr, *v = nullptr;
-    bool projected = false;
-    // population-evaluation scratch
-    int64_t cand_cap = 0;
-    void *cand_dev = nullptr;
-    void *cand_host = nullptr;     // pinned
-    double *partials = nullptr;
-    int64_t partials_cap = 0;
-    double *sums_dev = nullptr;    // cand_cap + 1
-    double *sums_host = nullptr;   // pinned, cand_cap + 1
-    int64_t last_info[3] = {0, 0, 0};     // alp_eval_population_info: variant, stripes, tile columns of the last launch
-    int64_t pending_P = 0;
-    int pending_loss = 0;
-    double pending_f_scale = 0;
-    std::vector<double> cand_copy;   // the P x 25 parameter vectors of the pending call (argmin confirmation)
-    // argmin confirmation (float32 sets): float64 records, partial sums and sums of up to CONFIRM_MAX candidates
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // last population evaluation: before the kernels, after them, after the all-reduce
-    bool timed = false;
-    void *conf_dev = nullptr;
-    int conf_nblk = 0;
-    double *conf_host = nullptr;   // pinned, CONFIRM_MAX + 1
-    size_t esize() const { return precision == ALP_F64 ? 8 : 4; }
-};
 
 // argmin confirmation of float32 point sets: CONFIRM_MAX, CONFIRM_GAP and the selection itself live in host/alp_host.h
 using alp::host::CONFIRM_MAX;
@@ -203,42 +168,9 @@ int ensure_pop_scratch(alp_points *p, int64_t P, int nblk) {
     return ALP_OK;
 }
 
+// the launch half of enqueue_popeval (alp_points_internal.h: popeval_launch): the records lie in p->cand_dev
 template <typename T>
-int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind, double f_scale) {
-    // one pinned staging buffer per handle: a second enqueue would rewrite it under the first one's
-    // asynchronous copy (and lose its result)
-    if (p->pending_P > 0)
-        return fail(ALP_ESTATE, "alp_eval_population_enqueue: the previous enqueue has not been waited for");
-    if (int rc = ensure_pop_scratch(p, P, 0)) return rc;
-    PoseRec<T> *h = (PoseRec<T> *)p->cand_host;
-    // the kernel centres the observations once per point: every candidate of a call must share
-    // the image size (the reference never optimises w, h: optimize.py:240-247)
-    for (int64_t i = 1; i < P; ++i)
-        if (cand[i * ALP_NPARAM + 21] != cand[21] || cand[i * ALP_NPARAM + 22] != cand[22])
-            return fail(ALP_EINVAL, "alp_eval_population: candidates %lld and 0 differ in w or h", (long long)i);
-    // lens-free populations (no candidate has a lens coefficient other than a1, a2: the reference's first phase, example.py:51-54;
-    // BASELINE config 3) take the kernel variant that runs on rows with the lens folded in: its records follow the general ones
-    bool lens_free = !getenv("ALP_POP_NO_LENS_FREE");
-    for (int64_t i = 0; i < P && lens_free; ++i) lens_free = pose_is_lens_free(cand + i * ALP_NPARAM);
-    for (int64_t i = 0; i < P; ++i) {
-        double g[POSE_WORDS], lf[POSE_WORDS];
-        fold_pose(cand + i * ALP_NPARAM, p->origin, g);
-        for (int k = 0; k < POSE_WORDS; ++k) h[i].v[k] = (T)g[k];
-        if (lens_free) {
-            lens_free_from_general(g, lf);
-            for (int k = 0; k < POSE_WORDS; ++k) h[p->cand_cap + i].v[k] = (T)lf[k];
-        }
-    }
-    ALP_HIP(hipMemcpyAsync(p->cand_dev, h, (size_t)P * sizeof(PoseRec<T>), hipMemcpyHostToDevice, ctx().stream));
-    if (lens_free)
-        ALP_HIP(hipMemcpyAsync((PoseRec<T> *)p->cand_dev + p->cand_cap, h + p->cand_cap, (size_t)P * sizeof(PoseRec<T>), hipMemcpyHostToDevice,
-                               ctx().stream));
-    // distortion-only populations (the reference's second phase, example.py:75-78) share the
-    // folded 3x4 matrix: its 12 words are identical in every record, and the kernel then
-    // computes the normalised coordinates once per point instead of once per candidate
-    bool shared_pose = P > 1 && !lens_free;
-    for (int64_t i = 1; i < P && shared_pose; ++i)
-        shared_pose = memcmp(h[i].v, h[0].v, 12 * sizeof(T)) == 0;
+int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose) {
     using Kernel = void (*)(const T *, const T *, const T *, const T *, const T *, int64_t, const PoseRec<T> *, int, T,
                             double *, const PoseRec<T> *);
     const int which = (loss_kind == ALP_LOSS_HUBER ? 3 : 0) + (lens_free ? 2 : (shared_pose ? 1 : 0));
@@ -329,6 +261,48 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
     if (int rc = comm_allreduce_sum_f64(p->sums_dev, P + 1)) return rc;
     ALP_HIP(hipEventRecord(p->ev[2], ctx().stream));
     p->timed = true;
+    return ALP_OK;
+}
+
+template <typename T>
+int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind, double f_scale) {
+    // one pinned staging buffer per handle: a second enqueue would rewrite it under the first one's
+    // asynchronous copy (and lose its result)
+    if (p->pending_P > 0)
+        return fail(ALP_ESTATE, "alp_eval_population_enqueue: the previous enqueue has not been waited for");
+    if (p->loop_pending)
+        return fail(ALP_ESTATE, "alp_eval_population_enqueue: a device loop on this point set has not been waited for (alp_cma_wait)");
+    if (int rc = ensure_pop_scratch(p, P, 0)) return rc;
+    PoseRec<T> *h = (PoseRec<T> *)p->cand_host;
+    // the kernel centres the observations once per point: every candidate of a call must share
+    // the image size (the reference never optimises w, h: optimize.py:240-247)
+    for (int64_t i = 1; i < P; ++i)
+        if (cand[i * ALP_NPARAM + 21] != cand[21] || cand[i * ALP_NPARAM + 22] != cand[22])
+            return fail(ALP_EINVAL, "alp_eval_population: candidates %lld and 0 differ in w or h", (long long)i);
+    // lens-free populations (no candidate has a lens coefficient other than a1, a2: the reference's first phase, example.py:51-54;
+    // BASELINE config 3) take the kernel variant that runs on rows with the lens folded in: its records follow the general ones
+    bool lens_free = !getenv("ALP_POP_NO_LENS_FREE");
+    for (int64_t i = 0; i < P && lens_free; ++i) lens_free = pose_is_lens_free(cand + i * ALP_NPARAM);
+    for (int64_t i = 0; i < P; ++i) {
+        double g[POSE_WORDS], lf[POSE_WORDS];
+        fold_pose(cand + i * ALP_NPARAM, p->origin, g);
+        for (int k = 0; k < POSE_WORDS; ++k) h[i].v[k] = (T)g[k];
+        if (lens_free) {
+            lens_free_from_general(g, lf);
+            for (int k = 0; k < POSE_WORDS; ++k) h[p->cand_cap + i].v[k] = (T)lf[k];
+        }
+    }
+    ALP_HIP(hipMemcpyAsync(p->cand_dev, h, (size_t)P * sizeof(PoseRec<T>), hipMemcpyHostToDevice, ctx().stream));
+    if (lens_free)
+        ALP_HIP(hipMemcpyAsync((PoseRec<T> *)p->cand_dev + p->cand_cap, h + p->cand_cap, (size_t)P * sizeof(PoseRec<T>), hipMemcpyHostToDevice,
+                               ctx().stream));
+    // distortion-only populations (the reference's second phase, example.py:75-78) share the
+    // folded 3x4 matrix: its 12 words are identical in every record, and the kernel then
+    // computes the normalised coordinates once per point instead of once per candidate
+    bool shared_pose = P > 1 && !lens_free;
+    for (int64_t i = 1; i < P && shared_pose; ++i)
+        shared_pose = memcmp(h[i].v, h[0].v, 12 * sizeof(T)) == 0;
+    if (int rc = popeval_launch_t<T>(p, P, loss_kind, f_scale, lens_free, shared_pose)) return rc;
     ALP_HIP(hipMemcpyAsync(p->sums_host, p->sums_dev, (size_t)(P + 1) * sizeof(double),
                            hipMemcpyDeviceToHost, ctx().stream));
     p->pending_P = P;
@@ -418,6 +392,14 @@ int residuals_impl(alp_points *p, const double *cand, int64_t B, double *out) {
 }
 
 }  // namespace
+
+namespace alp {
+int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose) {
+    return p->precision == ALP_F64 ? popeval_launch_t<double>(p, P, loss_kind, f_scale, lens_free, shared_pose)
+                                   : popeval_launch_t<float>(p, P, loss_kind, f_scale, lens_free, shared_pose);
+}
+int points_pop_reserve(alp_points *p, int64_t P) { return ensure_pop_scratch(p, P, 0); }
+}  // namespace alp
 
 // ---- fetch with a change of element type (float32 set -> float64 arrays, the reference's type; or the reverse)
 // The planes are converted ON THE HOST while they arrive: a chunk crosses PCIe in its stored type (a float32 set moves 4 bytes
@@ -555,6 +537,7 @@ int alp_points_create_columns(const void *x, const void *y, const void *z, int i
 
 int alp_points_destroy(alp_points_t *p) {
     if (!p) return ALP_OK;
+    for (alp_cma_t *h : p->loops) cma_points_gone(h);
     if (ctx().ready) hipStreamSynchronize(ctx().stream);
     for (void *q : {p->slab_xyz, p->slab_obs, p->slab_uv, p->cand_dev, (void *)p->partials, (void *)p->sums_dev})
         if (q) hipFree(q);

@@ -1,0 +1,61 @@
+// The point-set handle of alp_points.hip, shared with the device loop of the CMA-ES generation (alp_cma.hip), which feeds the
+// population kernels from device-resident records.  Not part of the ABI.
+#pragma once
+
+#include <vector>
+
+#include "alp_internal.h"
+
+// ------------------------------------------------------------------ the handle
+struct alp_points {
+    int64_t n = 0;
+    int64_t n_pad = 0;
+    int precision = ALP_F32;
+    double origin[3] = {0, 0, 0};
+    // the planes live in at most three allocations (a hipMalloc / hipFree pair of this size costs ~1 ms: seven of them were a
+    // third of what compute_residuals spent at 10 M points): coordinates at creation, observed pixels at alp_points_set_observed*,
+    // projected pixels at the first alp_project
+    void *slab_xyz = nullptr, *slab_obs = nullptr, *slab_uv = nullptr;
+    void *x = nullptr, *y = nullptr, *z = nullptr;
+    void *uo = nullptr, *vo = nullptr;
+    void *u = nullptr, *v = nullptr;
+    bool projected = false;
+    // population-evaluation scratch
+    int64_t cand_cap = 0;
+    void *cand_dev = nullptr;
+    void *cand_host = nullptr;     // pinned
+    double *partials = nullptr;
+    int64_t partials_cap = 0;
+    double *sums_dev = nullptr;    // cand_cap + 1
+    double *sums_host = nullptr;   // pinned, cand_cap + 1
+    int64_t last_info[3] = {0, 0, 0};     // alp_eval_population_info: variant, stripes, tile columns of the last launch
+    int64_t pending_P = 0;
+    int pending_loss = 0;
+    double pending_f_scale = 0;
+    std::vector<double> cand_copy;   // the P x 25 parameter vectors of the pending call (argmin confirmation)
+    // argmin confirmation (float32 sets): float64 records, partial sums and sums of up to CONFIRM_MAX candidates
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // last population evaluation: before the kernels, after them, after the all-reduce
+    bool timed = false;
+    void *conf_dev = nullptr;
+    int conf_nblk = 0;
+    double *conf_host = nullptr;   // pinned, CONFIRM_MAX + 1
+    // device loops of the CMA-ES generation (alp_cma.hip) built on this set: told when it is destroyed; while one of them has
+    // generations enqueued (loop_pending) they use the population scratch above, and an alp_eval_population_enqueue is refused
+    std::vector<alp_cma_t *> loops;
+    bool loop_pending = false;
+    size_t esize() const { return precision == ALP_F64 ? 8 : 4; }
+};
+
+namespace alp {
+
+// The population evaluation of P candidates whose pose records already lie in p->cand_dev (general records at [0, P), the
+// lens-free ones at [cand_cap, cand_cap + P) when `lens_free`): grid choice, popeval_kernel + reduce_partials_kernel into
+// p->sums_dev (P + 1 sums, the last one the vertex count), the all-reduce of those sums when a communicator exists, and
+// last_info / the timing events.  Enqueue only.  The caller has reserved the scratch for P (points_pop_reserve).
+int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose);
+// population scratch (records, sums) for P candidates
+int points_pop_reserve(alp_points *p, int64_t P);
+// alp_points_destroy: a device loop built on the set loses it (its later calls return ALP_ESTATE)
+void cma_points_gone(alp_cma_t *h);
+
+}  // namespace alp

@@ -26,75 +26,8 @@ int fail(int code, const char *fmt, ...) {
 }
 
 // ------------------------------------------------------------------ pose folding
-// Reference arithmetic being folded (all float64, src/alproj/optimize.py):
-//   intrinsic_mat :35-38   fov_x = fov*pi/180; fov_y = fov_x*h/w (Q5);
-//                          fx = w/(2 tan(fov_x/2)); fy = h/(2 tan(fov_y/2))
-//   extrinsic_mat :71-95   R = Rx(-(tilt+90)) . Ry(-roll) . Rz(pan);  t = R.(-cam)
-//   project :144-149       cam = R.p + t;  (x,y,z) = K.cam;  u = w - x/z (Q4);  v = y/z
-//   _distort :104-106      c = float32((w-1)/2, (h-1)/2);  x1 = (u-c0)/c0;  y1 = (v-c1)/c1
-// With p = origin + q:  cam = R.q + R.(origin - cam_pos), and
-//   x1 = ((w-c0)/c0) - (x/z)/c0 = ( ((w-c0)/c0).rowZ - rowx/c0 ) . [q;1] / (rowZ.[q;1])
-//   y1 = (y/z)/c1 - 1          = ( rowy/c1 - rowZ ) . [q;1] / (rowZ.[q;1])
-// where rowx = fx.R0 + cx.R2, rowy = fy.R1 + cy.R2, rowZ = R2 (4-vectors incl. translation).
-// The principal-point cancellation (cx.Z against c0.Z) therefore happens here in float64.
-void fold_pose(const double p[ALP_NPARAM], const double origin[3], double rec[POSE_WORDS]) {
-    const double X = p[0], Y = p[1], Z = p[2], fov = p[3], pan_d = p[4], tilt_d = p[5],
-                 roll_d = p[6];
-    const double w = p[21], h = p[22], cx = p[23], cy = p[24];
-    const double pi = M_PI;
-
-    const double fov_x = fov * pi / 180;
-    const double fov_y = fov_x * h / w;
-    const double fx = w / (2 * std::tan(fov_x / 2));
-    const double fy = h / (2 * std::tan(fov_y / 2));
-
-    const double a = pan_d * pi / 180;
-    const double b = -(tilt_d + 90) * pi / 180;
-    const double c = -roll_d * pi / 180;
-    const double rz[3][3] = {{std::cos(a), -std::sin(a), 0}, {std::sin(a), std::cos(a), 0}, {0, 0, 1}};
-    const double rx[3][3] = {{1, 0, 0}, {0, std::cos(b), -std::sin(b)}, {0, std::sin(b), std::cos(b)}};
-    const double ry[3][3] = {{std::cos(c), 0, std::sin(c)}, {0, 1, 0}, {-std::sin(c), 0, std::cos(c)}};
-    double rxy[3][3], R[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0;
-            for (int k = 0; k < 3; ++k) s += rx[i][k] * ry[k][j];
-            rxy[i][j] = s;
-        }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0;
-            for (int k = 0; k < 3; ++k) s += rxy[i][k] * rz[k][j];
-            R[i][j] = s;
-        }
-    const double d[3] = {origin[0] - X, origin[1] - Y, origin[2] - Z};
-    double row[3][4];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) row[i][j] = R[i][j];
-        row[i][3] = R[i][0] * d[0] + R[i][1] * d[1] + R[i][2] * d[2];
-    }
-    const double c0 = (double)(float)((w - 1) / 2);
-    const double c1 = (double)(float)((h - 1) / 2);
-    const double A = (w - c0) / c0;
-    for (int j = 0; j < 4; ++j) {
-        const double rowx = fx * row[0][j] + cx * row[2][j];
-        const double rowy = fy * row[1][j] + cy * row[2][j];
-        rec[0 + j] = A * row[2][j] - rowx / c0;
-        rec[4 + j] = rowy / c1 - row[2][j];
-        rec[8 + j] = row[2][j];
-    }
-    for (int i = 0; i < 6; ++i) rec[12 + i] = p[9 + i];   // k1..k6
-    rec[18] = 1 + p[7];                                    // 1 + a1
-    rec[19] = 1 + p[8];                                    // 1 + a2
-    rec[20] = 2 * p[15];                                   // 2 p1
-    rec[21] = 2 * p[16];                                   // 2 p2
-    for (int i = 0; i < 4; ++i) rec[22 + i] = p[17 + i];  // s1..s4
-    rec[26] = c0;
-    rec[27] = c1;
-    rec[28] = -c0;                                         // residual = (uo - c0) + (-c0) * x1_d
-    rec[29] = -c1;
-    rec[30] = rec[31] = 0;
-}
+// (the arithmetic itself is host/alp_fold.h, shared with the device loop of alp_cma.hip; compiled here exactly as before)
+void fold_pose(const double p[ALP_NPARAM], const double origin[3], double rec[POSE_WORDS]) { fold_pose_hd(p, origin, rec); }
 
 bool pose_is_lens_free(const double p[ALP_NPARAM]) {
     for (int i = 9; i <= 20; ++i)
@@ -102,17 +35,7 @@ bool pose_is_lens_free(const double p[ALP_NPARAM]) {
     return true;
 }
 
-void lens_free_from_general(const double g[POSE_WORDS], double rec[POSE_WORDS]) {
-    const double sy = g[18] / g[19];               // (1 + a1) / (1 + a2)  (a2 = -1: inf / NaN rows, and losses, like the reference's division)
-    for (int i = 0; i < POSE_WORDS; ++i) rec[i] = 0;
-    for (int j = 0; j < 4; ++j) {
-        rec[0 + j] = g[28] * g[0 + j];             // -c0 X'
-        rec[4 + j] = (g[29] * sy) * g[4 + j];      // -c1 (1 + a1) / (1 + a2) Y'
-        rec[8 + j] = g[8 + j];
-    }
-    rec[26] = g[26];
-    rec[27] = g[27];
-}
+void lens_free_from_general(const double g[POSE_WORDS], double rec[POSE_WORDS]) { lens_free_from_general_hd(g, rec); }
 
 void fold_pose_lens_free(const double p[ALP_NPARAM], const double origin[3], double rec[POSE_WORDS]) {
     double g[POSE_WORDS];

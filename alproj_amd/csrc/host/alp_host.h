@@ -65,6 +65,10 @@ struct alignas(16) PoseRec {
     T v[POSE_WORDS];
 };
 
+}  // namespace alp
+#include "host/alp_fold.h"      // fold_pose_hd / lens_free_from_general_hd: the arithmetic, host and device
+namespace alp {
+
 // params: the 25 ABI parameters; origin: local origin of the point set (absolute coords).
 void fold_pose(const double params[ALP_NPARAM], const double origin[3], double rec[POSE_WORDS]);
 

@@ -10,7 +10,7 @@ here                          reference                                device en
 ``rmse`` / ``huber_loss``     optimize.py:157-178 / :181-212           alp_loss_uv
 ``compute_residuals``         optimize.py:215-237                      alp_residuals
 ``bounds_to_array``           optimize.py:249-276                      (host, D <= 21 scalars)
-``CMAOptimizer.optimize``     optimize.py:359-439                      alp_eval_population
+``CMAOptimizer.optimize``     optimize.py:359-439                      alp_eval_population, alp_cma_*
 ``LsqOptimizer.optimize``     optimize.py:467-539                      alp_residuals
 ``intrinsic_mat`` etc.        optimize.py:8-96                         (host, 3x3 / 4x4)
 ============================  =======================================  ======================
@@ -299,11 +299,31 @@ class CMAOptimizer(BaseOptimizer):
         _proj_error.points = pts
         return _proj_error
 
+    DEVICE_LOOP_MAX_POPULATION = 4096
+    DEVICE_LOOP_MAX_TARGETS = 32
+
+    def _check_device_loop(self, generation, population_size):
+        """the configurations device_loop=True does not cover: ValueError before the GPU is touched"""
+        if int(generation) < 1:
+            raise ValueError("device_loop=True needs generation >= 1")
+        if int(population_size) > self.DEVICE_LOOP_MAX_POPULATION:
+            raise ValueError(f"device_loop=True supports population_size <= {self.DEVICE_LOOP_MAX_POPULATION}")
+        if len(self.target_params) > self.DEVICE_LOOP_MAX_TARGETS:
+            raise ValueError(f"device_loop=True supports at most {self.DEVICE_LOOP_MAX_TARGETS} targets")
+        if "w" in self.target_params or "h" in self.target_params:
+            raise ValueError("w and h cannot be optimised: every candidate must share the image size")
+
     def optimize(self, sigma=0.2, bound_widths=None, generation=1000, population_size=10,
-                 n_max_resampling=100, f_scale=None, precision=None, seed=None, progress=True):
+                 n_max_resampling=100, f_scale=None, precision=None, seed=None, progress=True, device_loop=False):
         """Run CMA-ES; returns ``(params, error)`` like the reference: the best candidate of
         the LAST generation (optimize.py:427, quirk Q9) and its mean reprojection distance.
-        ``precision=None``: float64 like the reference up to F64_MAX_POINTS points (per rank), float32 above."""
+        ``precision=None``: float64 like the reference up to F64_MAX_POINTS points (per rank), float32 above.
+        ``device_loop=True``: generations 0 .. G-2 run on the device with the optimiser's state there (alp_cma_run: draw,
+        candidate matrix, fold, evaluation, tell, no host round trip in between); the state then comes back into the host
+        CMA once and the LAST generation runs the host path below (device sampler, argmin with its float64 confirmation,
+        final error).  population_size <= 4096, at most 32 targets."""
+        if device_loop:
+            self._check_device_loop(generation, population_size)
         bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
         lower, upper = bounds[:, 0], bounds[:, 1]
         normalized_init = (self.target_params_init - lower) / (upper - lower)
@@ -332,8 +352,22 @@ class CMAOptimizer(BaseOptimizer):
                             # the device sampler costs a launch + a copy (~0.07 ms): it pays from a few thousand
                             # deviates per generation (pop 256 / D 21: 0.10 ms against 7 ms of numpy at sigma = 1);
                             # at GCP scale (pop 50 / D 9) the numpy path is the faster one (0.17 vs 0.24 ms / generation)
-                            sampler=_lib.cma_sample if (d <= 32 and population_size * d >= 2048) else None)
-            it = range(generation)
+                            sampler=_lib.cma_sample if (device_loop or (d <= 32 and population_size * d >= 2048)) else None)
+            first = 0
+            if device_loop and generation > 1:
+                # every rank runs the same replica: the sums are all-reduced, the tell is deterministic
+                loop = _lib.CmaDevice(pts, _lib.params_vector(self.params_init), [_lib.PARAM_KEYS.index(t) for t in self.target_params],
+                                      lower, upper, optimizer)
+                try:
+                    loop.set_state(optimizer.get_state())
+                    loop.run(generation - 1, _lib.LOSS_MEAN_DIST if f_scale is None else _lib.LOSS_HUBER,
+                             0.0 if f_scale is None else float(f_scale))
+                    loop.wait()
+                    optimizer.set_state(loop.get_state())
+                finally:
+                    loop.close()
+                first = generation - 1
+            it = range(first, generation)
             best_normalized = normalized_init
             for g in (tqdm(it) if progress else it):
                 X = np.ascontiguousarray(optimizer.ask_population())

@@ -263,6 +263,48 @@ int alp_cma_sample(const double *mean, double sigma, const double *BD, const dou
                    int D, int64_t P, int n_max_resampling, uint64_t seed, uint64_t generation, double *x_out,
                    int32_t *tries_out);
 
+/* ---------------------------------------------------------------- device loop of the CMA-ES generation --- */
+/* Generations of CMAOptimizer.optimize (src/alproj/optimize.py:410-427: ask, evaluate, tell) enqueued on the library stream
+ * with the optimiser's state on the device: no copy to the host and no synchronisation between generations
+ * (CMAOptimizer.optimize(..., device_loop=True); the host loop stays the default).  One generation is three launches:
+ * the draw of alp_cma_sample from the device state (the same bits for the same seed, generation, mean, sigma and BD) with
+ * the de-normalisation x * (upper - lower) + lower, the candidate matrix and the fold of every pose; the population
+ * evaluation of alp_eval_population (+ the all-reduce of its sums when a communicator exists); and the tell of cma.py
+ * (losses = sums / n_total, stable ascending order with NaN as +inf, mean / p_sigma / sigma / pc / C updates in numpy's
+ * order, then the eigendecomposition of C for the next generation), one workgroup in float64.
+ * The handle uses the population scratch of `pts`: while generations are enqueued, alp_eval_population_enqueue on `pts`
+ * returns ALP_ESTATE, and so does every call on the handle but alp_cma_wait / alp_cma_destroy.  A handle whose point set
+ * has been destroyed returns ALP_ESTATE from alp_cma_run. */
+typedef struct alp_cma alp_cma_t;
+/* hyper[ALP_CMA_NHYPER] = {mu, mu_eff, c1, cmu, cc, c_sigma, d_sigma, chi_n, cm, sum(weights)} and weights[P]: the constants of
+ * the host cma.CMA object (alproj_amd/cma.py), passed as it computed them. */
+#define ALP_CMA_NHYPER 10
+/* tmpl: the 25 ABI parameters of params_init; target_idx[D]: the ABI index of every target (not w, h); lower / upper[D]: the
+ * bounds of the targets (optimize.py bounds_to_array); P <= 4096, D <= 32.  The state starts as a fresh CMA's (mean 0.5,
+ * sigma 1, C = I); alp_cma_set_state sets it.  The kernel variant of the evaluation is chosen here, by the rules of
+ * alp_eval_population: lens-free (no target in k1..s4, the template's k1..s4 all 0; not under ALP_POP_NO_LENS_FREE), else
+ * shared pose (every target in a1..s4, P > 1), else general.  The handle keeps `pts`; destroy it before the point set. */
+int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                   const double *upper, int64_t P, const double *weights, const double hyper[ALP_CMA_NHYPER], int n_max_resampling,
+                   uint64_t seed, alp_cma_t **out);
+int alp_cma_destroy(alp_cma_t *h);
+/* mean[D], sigma, C[D x D] row-major, p_sigma[D], pc[D], generation (cma.py get_state / set_state); set_state then runs the
+ * eigendecomposition of C (cma.py _eigen: C is symmetrised and rewritten as B diag(d^2) B^T).  get_state: every output may be
+ * NULL; B[D x D] (eigenvectors as columns) and Dvec[D] are those the next draw uses (BD = B diag(Dvec)). */
+int alp_cma_set_state(alp_cma_t *h, const double *mean, double sigma, const double *C, const double *p_sigma, const double *pc,
+                      int64_t generation);
+int alp_cma_get_state(alp_cma_t *h, double *mean, double *sigma, double *C, double *p_sigma, double *pc, int64_t *generation, double *B,
+                      double *Dvec);
+/* Enqueue `generations` generations (enqueue only; alp_cma_wait synchronises).  A second run before the wait: ALP_ESTATE. */
+int alp_cma_run(alp_cma_t *h, int64_t generations, int loss_kind, double f_scale);
+int alp_cma_wait(alp_cma_t *h);
+/* One tell on given candidates X[P x D] (normalised) and losses[P], then the eigendecomposition; order_out (optional, P
+ * ints): the order the tell sorted by (cma.py tell_population's return value).  For tests. */
+int alp_cma_tell_host(alp_cma_t *h, const double *X, const double *losses, int32_t *order_out);
+/* The last device generation: X[P x D] (normalised draws), cand[P x 25] (the candidate matrix), losses[P]; any may be NULL.
+ * For tests. */
+int alp_cma_fetch_last(alp_cma_t *h, double *X, double *cand, double *losses);
+
 /* Loss of two host arrays of pixel coordinates (n x 2 row-major doubles each): replaces the
  * stand-alone rmse(), src/alproj/optimize.py:157-178 (loss_kind ALP_LOSS_MEAN_DIST) and
  * huber_loss(), :181-212 (ALP_LOSS_HUBER).  Float64 arithmetic on the device. */
