@@ -217,6 +217,10 @@ _SIGNATURES = {
     "alp_cma_wait": [_c_void_p],
     "alp_cma_tell_host": [_c_void_p, _c_dp, _c_dp, ctypes.POINTER(ctypes.c_int32)],
     "alp_cma_fetch_last": [_c_void_p, _c_dp, _c_dp, _c_dp],
+    "alp_cma_create_starts": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_dp,
+                              _c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_c_void_p)],
+    "alp_cma_set_state_at": [_c_void_p, _c_int, _c_dp, _c_double, _c_dp, _c_dp, _c_dp, _c_i64],
+    "alp_cma_get_state_at": [_c_void_p, _c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.POINTER(_c_i64), _c_dp, _c_dp],
     "alp_mesh_create": [_c_void_p, _c_int, _c_void_p, _c_int, _c_i64, _c_void_p, _c_int, _c_i64, _c_i64, _c_i64,
                         ctypes.POINTER(_c_void_p)],
     "alp_mesh_destroy": [_c_void_p],
@@ -891,9 +895,11 @@ class CmaDevice:
     """The device loop of the CMA-ES generation (RAII wrapper of alp_cma_t): the state of a host ``cma.CMA`` on the device,
     ``run(G)`` enqueues G generations (draw, candidate matrix, fold, population evaluation, tell) without the host in between.
     ``points``: the Points the candidates are evaluated on; ``template``: the 25-vector of params_init; ``targets``: ABI indices
-    of the targets; ``lower`` / ``upper``: their bounds; ``cma``: the host CMA whose constants (and seed) the loop takes."""
+    of the targets; ``lower`` / ``upper``: their bounds; ``cma``: the host CMA whose constants (and seed) the loop takes.
+    ``seeds`` (optional, length K): K independent starts that share those constants, start k drawing with seeds[k]
+    (alp_cma_create_starts); ``fetch_last`` / ``tell_host`` then take and return K * P rows in start order."""
 
-    def __init__(self, points, template, targets, lower, upper, cma):
+    def __init__(self, points, template, targets, lower, upper, cma, seeds=None):
         l = lib()
         tmpl = np.ascontiguousarray(template, dtype=np.float64)
         idx = np.ascontiguousarray(targets, dtype=np.int32)
@@ -905,9 +911,17 @@ class CmaDevice:
         hyper = np.array([cma._mu, cma._mu_eff, cma._c1, cma._cmu, cma._cc, cma._c_sigma, cma._d_sigma, cma._chi_n, cma._cm,
                           np.sum(cma._weights)], dtype=np.float64)
         h = _c_void_p()
-        check(l.alp_cma_create(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo), as_dp(hi),
-                               self.P, as_dp(w), as_dp(hyper), int(cma._n_max_resampling),
-                               ctypes.c_uint64(int(cma._sampler_seed) & (2**64 - 1)), ctypes.byref(h)))
+        if seeds is None:
+            self.K = 1
+            check(l.alp_cma_create(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo), as_dp(hi),
+                                   self.P, as_dp(w), as_dp(hyper), int(cma._n_max_resampling),
+                                   ctypes.c_uint64(int(cma._sampler_seed) & (2**64 - 1)), ctypes.byref(h)))
+        else:
+            sd = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+            self.K = int(len(sd))
+            check(l.alp_cma_create_starts(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo),
+                                          as_dp(hi), self.P, self.K, as_dp(w), as_dp(hyper), int(cma._n_max_resampling),
+                                          sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(h)))
         self._h = h
         self._lib = l
         self.points = points
@@ -925,23 +939,32 @@ class CmaDevice:
     def __exit__(self, *exc):
         self.close()
 
-    def set_state(self, state):
-        """``state``: the dict of cma.CMA.get_state()"""
+    def set_state(self, state, start=None):
+        """``state``: the dict of cma.CMA.get_state(); ``start``: the start it is for (None: start 0)"""
         D = self.D
         mean = np.ascontiguousarray(state["mean"], dtype=np.float64).reshape(D)
         C = np.ascontiguousarray(state["C"], dtype=np.float64).reshape(D, D)
         ps = np.ascontiguousarray(state["p_sigma"], dtype=np.float64).reshape(D)
         pc = np.ascontiguousarray(state["pc"], dtype=np.float64).reshape(D)
-        check(self._lib.alp_cma_set_state(self._h, as_dp(mean), float(state["sigma"]), as_dp(C), as_dp(ps), as_dp(pc), int(state["g"])))
+        if start is None:
+            check(self._lib.alp_cma_set_state(self._h, as_dp(mean), float(state["sigma"]), as_dp(C), as_dp(ps), as_dp(pc), int(state["g"])))
+        else:
+            check(self._lib.alp_cma_set_state_at(self._h, int(start), as_dp(mean), float(state["sigma"]), as_dp(C), as_dp(ps), as_dp(pc),
+                                                 int(state["g"])))
 
-    def get_state(self, eigen=False):
-        """the dict cma.CMA.set_state() takes; ``eigen=True`` adds "B" (eigenvectors as columns) and "D" of the next draw"""
+    def get_state(self, eigen=False, start=None):
+        """the dict cma.CMA.set_state() takes; ``eigen=True`` adds "B" (eigenvectors as columns) and "D" of the next draw;
+        ``start``: the start to read (None: start 0)"""
         D = self.D
         mean, ps, pc, d = (np.empty(D) for _ in range(4))
         C, B = np.empty((D, D)), np.empty((D, D))
         sigma, g = _c_double(), _c_i64()
-        check(self._lib.alp_cma_get_state(self._h, as_dp(mean), ctypes.byref(sigma), as_dp(C), as_dp(ps), as_dp(pc), ctypes.byref(g),
-                                          as_dp(B), as_dp(d)))
+        if start is None:
+            check(self._lib.alp_cma_get_state(self._h, as_dp(mean), ctypes.byref(sigma), as_dp(C), as_dp(ps), as_dp(pc), ctypes.byref(g),
+                                              as_dp(B), as_dp(d)))
+        else:
+            check(self._lib.alp_cma_get_state_at(self._h, int(start), as_dp(mean), ctypes.byref(sigma), as_dp(C), as_dp(ps), as_dp(pc),
+                                                 ctypes.byref(g), as_dp(B), as_dp(d)))
         st = {"mean": mean, "sigma": float(sigma.value), "C": C, "p_sigma": ps, "pc": pc, "g": int(g.value)}
         if eigen:
             st.update(B=B, D=d)
@@ -955,18 +978,21 @@ class CmaDevice:
         check(self._lib.alp_cma_wait(self._h))
 
     def tell_host(self, X, losses):
-        """one tell on the given (P, D) candidates and (P,) losses, then the eigendecomposition; returns the order"""
+        """one tell on the given (K P, D) candidates and (K P,) losses, then the eigendecomposition; returns the order (per start:
+        indices 0 .. P-1 within each start's P rows)"""
+        R = self.K * self.P
         X = np.ascontiguousarray(X, dtype=np.float64)
         losses = np.ascontiguousarray(losses, dtype=np.float64)
-        if X.shape != (self.P, self.D) or losses.shape != (self.P,):
-            raise ValueError("X must be (P, D) and losses (P,)")
-        order = np.empty(self.P, dtype=np.int32)
+        if X.shape != (R, self.D) or losses.shape != (R,):
+            raise ValueError("X must be (K P, D) and losses (K P,)")
+        order = np.empty(R, dtype=np.int32)
         check(self._lib.alp_cma_tell_host(self._h, as_dp(X), as_dp(losses), order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return order.astype(np.int64)
 
     def fetch_last(self):
-        """(X (P, D), candidate matrix (P, 25), losses (P,)) of the last device generation"""
-        X, cand, losses = np.empty((self.P, self.D)), np.empty((self.P, NPARAM)), np.empty(self.P)
+        """(X (K P, D), candidate matrix (K P, 25), losses (K P,)) of the last device generation, in start order"""
+        R = self.K * self.P
+        X, cand, losses = np.empty((R, self.D)), np.empty((R, NPARAM)), np.empty(R)
         check(self._lib.alp_cma_fetch_last(self._h, as_dp(X), as_dp(cand), as_dp(losses)))
         return X, cand, losses
 

@@ -19,6 +19,10 @@
 // This translation unit is compiled with -ffp-contract=off (alproj_amd/_build.py): the de-normalisation and the update
 // follow numpy's operation order, one rounding per operation.  Every rank runs the same replica: the sums are all-reduced,
 // the tell is one workgroup without atomics, so every rank computes the same state.
+// Multi-start (alp_cma_create_starts, CMAOptimizer.optimize(..., starts=K)): K independent states share the three launches of a
+// generation.  Candidate k * P + i of the draw is draw i of start k (start k's seed, state and generation: the bits of
+// alp_cma_sample(..., seeds[k], g)), the evaluation runs K * P candidates, and the tell is K workgroups, workgroup k on start k's
+// losses sums[k * P .. k * P + P) / sums[K * P], its state and its slice of the scratch.
 #include "alp_points_internal.h"
 #include "alp_sampler.h"
 
@@ -30,6 +34,8 @@ using namespace alp;
 
 constexpr int CMA_MAX_D = SAMPLER_MAX_D;      // 32
 constexpr int CMA_MAX_P = 4096;
+constexpr int CMA_MAX_STARTS = 1024;
+constexpr int64_t CMA_MAX_TOTAL = 65536;    // K * P
 constexpr int TELL_THREADS = 256;
 constexpr int JACOBI_MAX_SWEEPS = 40;
 constexpr double CMA_EPS = 1e-8;             // cma.py _EPS
@@ -42,11 +48,12 @@ struct CmaState {
     double BD[CMA_MAX_D * CMA_MAX_D];                              // B diag(d), rows of dmax columns, zero-padded (make_x)
     double sigma;
     long long g;
+    unsigned k0, k1;                                               // the sampler's key: this start's seed
 };
 
 // the constants of cma.py:CMA.__init__, as the host object computed them (nothing is recomputed here)
 struct CmaHyper {
-    int D, P, mu, dmax;
+    int D, P, mu, dmax, K;
     double mu_eff, c1, cmu, cc, c_sigma, d_sigma, chi_n, cm, sum_w;
 };
 
@@ -61,12 +68,15 @@ struct ExpandArgs {
 // ------------------------------------------------------------------ 1. sample + expand + fold
 // cma_sample_kernel (alp_sampler.hip) with mean, sigma and the generation counter taken from the device state; the lane
 // that holds the accepted draw then de-normalises, scatters and folds its candidate.
+// K starts: candidate `cand` of the grid is draw i = cand % P of start cand / P, from start k's state and key.
 template <typename T, int DMAX, bool LF>
-__global__ __launch_bounds__(256) void cma_generation_kernel(SamplerArgs a0, ExpandArgs e, const CmaState *__restrict__ st, long long P,
-                                                             double *__restrict__ x_out, double *__restrict__ cand_out,
+__global__ __launch_bounds__(256) void cma_generation_kernel(SamplerArgs a0, ExpandArgs e, const CmaState *__restrict__ states, long long P,
+                                                             long long total, double *__restrict__ x_out, double *__restrict__ cand_out,
                                                              PoseRec<T> *__restrict__ recs, long long lf_off) {
     const long long cand = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (cand >= P) return;
+    if (cand >= total) return;
+    const long long start = cand / P, draw = cand - start * P;
+    const CmaState *st = states + start;
     const int lane = (int)(threadIdx.x & 63);
     SamplerArgs a = a0;
 #pragma unroll
@@ -74,6 +84,8 @@ __global__ __launch_bounds__(256) void cma_generation_kernel(SamplerArgs a0, Exp
         if (i < a.D) a.mean[i] = st->mean[i];
     a.sigma = st->sigma;
     a.gen = (unsigned)st->g;
+    a.k0 = st->k0;
+    a.k1 = st->k1;
     const double *BD = st->BD;
     double z[DMAX], x[DMAX];
 #pragma unroll
@@ -83,7 +95,7 @@ __global__ __launch_bounds__(256) void cma_generation_kernel(SamplerArgs a0, Exp
         const int t = base + lane;
         bool ok = false;
         if (t < a.n_max) {
-            draw_normals<DMAX>(z, a.D, (unsigned)t, (unsigned)cand, a.gen, a.k0, a.k1);
+            draw_normals<DMAX>(z, a.D, (unsigned)t, (unsigned)draw, a.gen, a.k0, a.k1);
             ok = make_x<DMAX, false>(a, BD, z, x);
         }
         const unsigned long long m = __ballot(ok);
@@ -91,7 +103,7 @@ __global__ __launch_bounds__(256) void cma_generation_kernel(SamplerArgs a0, Exp
     }
     const int t_final = accepted >= 0 ? accepted : a.n_max;
     if (lane != (t_final & 63)) return;
-    draw_normals<DMAX>(z, a.D, (unsigned)t_final, (unsigned)cand, a.gen, a.k0, a.k1);
+    draw_normals<DMAX>(z, a.D, (unsigned)t_final, (unsigned)draw, a.gen, a.k0, a.k1);
     make_x<DMAX, true>(a, BD, z, x);
     double prm[ALP_NPARAM];
     for (int k = 0; k < ALP_NPARAM; ++k) prm[k] = e.tmpl[k];
@@ -247,14 +259,26 @@ __device__ void jacobi_eigen(int D, double *C, double *B, double *d2, double *A,
     __syncthreads();
 }
 
-// TELL: one tell_population on the candidates X (P x D) with losses sums[i] / sums[P] (vals == NULL) or vals[i];
+// TELL: one tell_population on the candidates X (P x D) with losses sums[i] / sums[K P] (vals == NULL) or vals[i];
 // then (always) cma.py:_eigen on the state's C.  loss_out / order_out: the losses used and the stable ascending order.
+// Workgroup k works on start k: its state and its P rows of X, sums, vals, loss_out, order_out, ys and wio (the order holds
+// indices 0 .. P-1 within the start); sums[h.K * P] is the vertex count every start divides by.
 template <bool TELL>
-__global__ __launch_bounds__(TELL_THREADS) void cma_tell_kernel(CmaHyper h, CmaState *__restrict__ st, const double *__restrict__ weights,
-                                                                const double *__restrict__ X, const double *__restrict__ sums,
-                                                                const double *__restrict__ vals, double *__restrict__ loss_out,
-                                                                int *__restrict__ order_out, double *__restrict__ ys,
-                                                                double *__restrict__ wio) {
+__global__ __launch_bounds__(TELL_THREADS) void cma_tell_kernel(CmaHyper h, CmaState *__restrict__ states, const double *__restrict__ weights,
+                                                                const double *__restrict__ X_all, const double *__restrict__ sums_all,
+                                                                const double *__restrict__ vals_all, double *__restrict__ loss_all,
+                                                                int *__restrict__ order_all, double *__restrict__ ys_all,
+                                                                double *__restrict__ wio_all) {
+    const long long k = blockIdx.x, kP = k * h.P, kPD = kP * h.D;
+    CmaState *__restrict__ st = states + k;
+    const double *__restrict__ X = X_all + kPD;
+    const double *__restrict__ sums = sums_all ? sums_all + kP : nullptr;
+    const double n_total = sums_all ? sums_all[(long long)h.K * h.P] : 0.0;
+    const double *__restrict__ vals = vals_all ? vals_all + kP : nullptr;
+    double *__restrict__ loss_out = loss_all + kP;
+    int *__restrict__ order_out = order_all + kP;
+    double *__restrict__ ys = ys_all + kPD;
+    double *__restrict__ wio = wio_all + kP;
     constexpr int M = CMA_MAX_D * CMA_MAX_D;
     __shared__ double C[M], B[M], A[M], A2[M], V[M], V2[M];
     __shared__ double mean[CMA_MAX_D], d[CMA_MAX_D], yw[CMA_MAX_D], ps[CMA_MAX_D], pc[CMA_MAX_D], d2[CMA_MAX_D];
@@ -278,7 +302,7 @@ __global__ __launch_bounds__(TELL_THREADS) void cma_tell_kernel(CmaHyper h, CmaS
     if (TELL) {
         const long long g = st->g + 1;                       // self._g += 1
         // losses (host/alp_host.h losses_and_argmin: sums[i] / n_total) and the order of np.argsort(where(isnan, inf, l), kind="stable")
-        for (int i = tid; i < P; i += blockDim.x) loss_out[i] = vals ? vals[i] : sums[i] / sums[P];
+        for (int i = tid; i < P; i += blockDim.x) loss_out[i] = vals ? vals[i] : sums[i] / n_total;
         __syncthreads();
         for (int i = tid; i < P; i += blockDim.x) {
             double ki = loss_out[i];
@@ -409,13 +433,15 @@ struct alp_cma {
     CmaHyper hy{};
     SamplerArgs sa{};
     ExpandArgs ex{};
+    std::vector<uint64_t> seeds;  // K: start k's sampler seed
     bool lens_free = false, shared_pose = false;
-    void *dev = nullptr;          // one allocation: state, weights, X, candidates, losses, order, y_k, w_io, told losses
+    void *dev = nullptr;          // one allocation: K states, weights, X, candidates, losses, order, y_k, w_io, told losses
     CmaState *st = nullptr;
     double *w = nullptr, *X = nullptr, *cand = nullptr, *loss = nullptr, *ys = nullptr, *wio = nullptr, *vals = nullptr;
     int *order = nullptr;
     bool pending = false;         // generations enqueued, alp_cma_wait not yet called
     bool have_last = false;       // a device generation has run (alp_cma_fetch_last)
+    int64_t rows() const { return (int64_t)hy.K * hy.P; }
 };
 
 namespace alp {
@@ -424,26 +450,33 @@ void cma_points_gone(alp_cma_t *h) { h->pts = nullptr; }
 
 namespace {
 
-int upload_state(alp_cma *h, const double *mean, double sigma, const double *C, const double *ps, const double *pc, int64_t g) {
+// the state of start k (mean, sigma, C, p_sigma, pc, g; B and d cold) with its seed, for upload_states
+void fill_state(const alp_cma *h, int k, CmaState *s, const double *mean, double sigma, const double *C, const double *ps, const double *pc,
+                int64_t g) {
     const int D = h->hy.D;
-    CmaState s;
-    memset(&s, 0, sizeof(s));
+    memset(s, 0, sizeof(*s));
     for (int i = 0; i < D; ++i) {
-        s.mean[i] = mean[i];
-        s.ps[i] = ps[i];
-        s.pc[i] = pc[i];
-        s.d[i] = 1.0;
-        s.B[i * D + i] = 1.0;            // the eigendecomposition below starts cold (cma.py: set_state clears B and D)
+        s->mean[i] = mean[i];
+        s->ps[i] = ps[i];
+        s->pc[i] = pc[i];
+        s->d[i] = 1.0;
+        s->B[i * D + i] = 1.0;           // the eigendecomposition below starts cold (cma.py: set_state clears B and D)
     }
-    for (int e = 0; e < D * D; ++e) s.C[e] = C[e];
-    s.sigma = sigma;
-    s.g = g;
+    for (int e = 0; e < D * D; ++e) s->C[e] = C[e];
+    s->sigma = sigma;
+    s->g = g;
+    s->k0 = (unsigned)h->seeds[(size_t)k];
+    s->k1 = (unsigned)(h->seeds[(size_t)k] >> 32);
+}
+
+// states k0 .. k0 + n - 1 from the host, then their eigendecompositions (n workgroups)
+int upload_states(alp_cma *h, int k0, int n, const CmaState *s) {
     hipStream_t st = ctx().stream;
-    ALP_HIP(hipMemcpyAsync(h->st, &s, sizeof(s), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(cma_tell_kernel<false>, dim3(1), dim3(TELL_THREADS), 0, st, h->hy, h->st, (const double *)h->w, (const double *)h->X,
-                       (const double *)nullptr, (const double *)nullptr, h->loss, h->order, h->ys, h->wio);
+    ALP_HIP(hipMemcpyAsync(h->st + k0, s, (size_t)n * sizeof(CmaState), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(cma_tell_kernel<false>, dim3(n), dim3(TELL_THREADS), 0, st, h->hy, h->st + k0, (const double *)h->w,
+                       (const double *)h->X, (const double *)nullptr, (const double *)nullptr, h->loss, h->order, h->ys, h->wio);
     ALP_HIP(hipGetLastError());
-    ALP_HIP(hipStreamSynchronize(st));    // s (stack) must outlive its copy
+    ALP_HIP(hipStreamSynchronize(st));    // s (host) must outlive its copy
     return ALP_OK;
 }
 
@@ -460,10 +493,10 @@ void launch_generation(alp_cma *h, unsigned grid, hipStream_t st) {
     PoseRec<T> *recs = (PoseRec<T> *)p->cand_dev;
     if (h->lens_free)
         hipLaunchKernelGGL((cma_generation_kernel<T, DMAX, true>), dim3(grid), dim3(256), 0, st, h->sa, h->ex, (const CmaState *)h->st,
-                           (long long)h->hy.P, h->X, h->cand, recs, (long long)p->cand_cap);
+                           (long long)h->hy.P, (long long)h->rows(), h->X, h->cand, recs, (long long)p->cand_cap);
     else
         hipLaunchKernelGGL((cma_generation_kernel<T, DMAX, false>), dim3(grid), dim3(256), 0, st, h->sa, h->ex, (const CmaState *)h->st,
-                           (long long)h->hy.P, h->X, h->cand, recs, (long long)p->cand_cap);
+                           (long long)h->hy.P, (long long)h->rows(), h->X, h->cand, recs, (long long)p->cand_cap);
 }
 
 template <typename T>
@@ -477,15 +510,17 @@ void launch_generation_t(alp_cma *h, unsigned grid, hipStream_t st) {
 
 extern "C" {
 
-int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
-                   const double *upper, int64_t P, const double *weights, const double hyper[ALP_CMA_NHYPER], int n_max_resampling,
-                   uint64_t seed, alp_cma_t **out) {
+int alp_cma_create_starts(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                          const double *upper, int64_t P, int K, const double *weights, const double hyper[ALP_CMA_NHYPER],
+                          int n_max_resampling, const uint64_t *seeds, alp_cma_t **out) {
     if (int rc = require_init()) return rc;
     ALP_REQUIRE(out, "out is NULL");
     *out = nullptr;
-    ALP_REQUIRE(pts && tmpl && target_idx && lower && upper && weights && hyper, "NULL argument");
+    ALP_REQUIRE(pts && tmpl && target_idx && lower && upper && weights && hyper && seeds, "NULL argument");
     ALP_REQUIRE(D >= 1 && D <= CMA_MAX_D, "D must be in [1, 32]");
     ALP_REQUIRE(P >= 1 && P <= CMA_MAX_P, "P must be in [1, 4096]");
+    ALP_REQUIRE(K >= 1 && K <= CMA_MAX_STARTS, "K must be in [1, 1024]");
+    ALP_REQUIRE((int64_t)K * P <= CMA_MAX_TOTAL, "K * P must be at most 65536");
     ALP_REQUIRE(n_max_resampling >= 0 && n_max_resampling <= (1 << 20), "n_max_resampling out of range");
     if (!pts->uo) return fail(ALP_ESTATE, "alp_cma_create: observed uv not set");
     for (int i = 0; i < D; ++i) {
@@ -497,7 +532,8 @@ int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32
     alp_cma *h = new alp_cma();
     h->pts = pts;
     const int dmax = D <= 12 ? 12 : (D <= 24 ? 24 : 32);
-    h->hy = CmaHyper{D, (int)P, mu, dmax, hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], hyper[7], hyper[8], hyper[9]};
+    h->hy = CmaHyper{D, (int)P, mu, dmax, K, hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], hyper[7], hyper[8], hyper[9]};
+    h->seeds.assign(seeds, seeds + K);
     memset(&h->sa, 0, sizeof(h->sa));
     for (int i = 0; i < D; ++i) {
         h->sa.lower[i] = 0.0;            // the normalised box of optimize.py: [0, 1]^D
@@ -505,9 +541,7 @@ int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32
     }
     h->sa.D = D;
     h->sa.n_max = n_max_resampling;
-    h->sa.bounded = 1;
-    h->sa.k0 = (unsigned)seed;
-    h->sa.k1 = (unsigned)(seed >> 32);
+    h->sa.bounded = 1;                   // (the key comes from each start's state)
     memset(&h->ex, 0, sizeof(h->ex));
     for (int k = 0; k < ALP_NPARAM; ++k) h->ex.tmpl[k] = tmpl[k];
     for (int i = 0; i < D; ++i) {
@@ -526,14 +560,15 @@ int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32
     for (int i = 0; i < D && shared; ++i) shared = target_idx[i] >= 7 && target_idx[i] <= 20;
     h->lens_free = lf;
     h->shared_pose = shared;
-    const size_t sz_state = round_up(sizeof(CmaState), 256), sz_p = round_up(P * 8, 256), sz_pd = round_up(P * D * 8, 256),
-                 sz_cand = round_up(P * ALP_NPARAM * 8, 256), sz_ord = round_up(P * 4, 256);
+    const int64_t R = (int64_t)K * P;
+    const size_t sz_state = round_up((int64_t)K * sizeof(CmaState), 256), sz_w = round_up(P * 8, 256), sz_p = round_up(R * 8, 256),
+                 sz_pd = round_up(R * D * 8, 256), sz_cand = round_up(R * ALP_NPARAM * 8, 256), sz_ord = round_up(R * 4, 256);
     int rc = ALP_OK;
-    if (hipMalloc(&h->dev, sz_state + 4 * sz_p + 2 * sz_pd + sz_cand + sz_ord) != hipSuccess) rc = fail(ALP_EHIP, "alp_cma_create: hipMalloc failed");
+    if (hipMalloc(&h->dev, sz_state + sz_w + 3 * sz_p + 2 * sz_pd + sz_cand + sz_ord) != hipSuccess) rc = fail(ALP_EHIP, "alp_cma_create: hipMalloc failed");
     if (!rc) {
         char *q = (char *)h->dev;
         h->st = (CmaState *)q; q += sz_state;
-        h->w = (double *)q; q += sz_p;
+        h->w = (double *)q; q += sz_w;
         h->loss = (double *)q; q += sz_p;
         h->wio = (double *)q; q += sz_p;
         h->vals = (double *)q; q += sz_p;
@@ -543,11 +578,13 @@ int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32
         h->order = (int *)q;
         if (hipMemcpy(h->w, weights, (size_t)P * 8, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ALP_EHIP, "alp_cma_create: weights upload failed");
     }
-    if (!rc) rc = points_pop_reserve(pts, P);
-    if (!rc) {                           // the state of a fresh cma.CMA(mean = 0.5, sigma = 1): set_state replaces it
+    if (!rc) rc = points_pop_reserve(pts, R);
+    if (!rc) {                           // the state of a fresh cma.CMA(mean = 0.5, sigma = 1) per start: set_state replaces it
         std::vector<double> mean(D, 0.5), C((size_t)D * D, 0.0), zero(D, 0.0);
         for (int i = 0; i < D; ++i) C[(size_t)i * D + i] = 1.0;
-        rc = upload_state(h, mean.data(), 1.0, C.data(), zero.data(), zero.data(), 0);
+        std::vector<CmaState> s((size_t)K);
+        for (int k = 0; k < K; ++k) fill_state(h, k, &s[(size_t)k], mean.data(), 1.0, C.data(), zero.data(), zero.data(), 0);
+        rc = upload_states(h, 0, K, s.data());
     }
     if (rc) {
         if (h->dev) hipFree(h->dev);
@@ -557,6 +594,12 @@ int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32
     pts->loops.push_back(h);
     *out = h;
     return ALP_OK;
+}
+
+int alp_cma_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                   const double *upper, int64_t P, const double *weights, const double hyper[ALP_CMA_NHYPER], int n_max_resampling,
+                   uint64_t seed, alp_cma_t **out) {
+    return alp_cma_create_starts(pts, tmpl, target_idx, D, lower, upper, P, 1, weights, hyper, n_max_resampling, &seed, out);
 }
 
 int alp_cma_destroy(alp_cma_t *h) {
@@ -576,20 +619,29 @@ int alp_cma_destroy(alp_cma_t *h) {
     return ALP_OK;
 }
 
-int alp_cma_set_state(alp_cma_t *h, const double *mean, double sigma, const double *C, const double *p_sigma, const double *pc,
-                      int64_t generation) {
+int alp_cma_set_state_at(alp_cma_t *h, int k, const double *mean, double sigma, const double *C, const double *p_sigma, const double *pc,
+                         int64_t generation) {
     if (int rc = usable(h, "alp_cma_set_state")) return rc;
+    ALP_REQUIRE(k >= 0 && k < h->hy.K, "start index out of range");
     ALP_REQUIRE(mean && C && p_sigma && pc, "NULL argument");
     ALP_REQUIRE(sigma > 0, "sigma must be positive");
     ALP_REQUIRE(generation >= 0, "generation is negative");
-    return upload_state(h, mean, sigma, C, p_sigma, pc, generation);
+    CmaState s;
+    fill_state(h, k, &s, mean, sigma, C, p_sigma, pc, generation);
+    return upload_states(h, k, 1, &s);
 }
 
-int alp_cma_get_state(alp_cma_t *h, double *mean, double *sigma, double *C, double *p_sigma, double *pc, int64_t *generation, double *B,
-                      double *Dvec) {
+int alp_cma_set_state(alp_cma_t *h, const double *mean, double sigma, const double *C, const double *p_sigma, const double *pc,
+                      int64_t generation) {
+    return alp_cma_set_state_at(h, 0, mean, sigma, C, p_sigma, pc, generation);
+}
+
+int alp_cma_get_state_at(alp_cma_t *h, int k, double *mean, double *sigma, double *C, double *p_sigma, double *pc, int64_t *generation,
+                         double *B, double *Dvec) {
     if (int rc = usable(h, "alp_cma_get_state")) return rc;
+    ALP_REQUIRE(k >= 0 && k < h->hy.K, "start index out of range");
     CmaState s;
-    ALP_HIP(hipMemcpyAsync(&s, h->st, sizeof(s), hipMemcpyDeviceToHost, ctx().stream));
+    ALP_HIP(hipMemcpyAsync(&s, h->st + k, sizeof(s), hipMemcpyDeviceToHost, ctx().stream));
     ALP_HIP(hipStreamSynchronize(ctx().stream));
     const int D = h->hy.D;
     for (int i = 0; i < D; ++i) {
@@ -607,6 +659,11 @@ int alp_cma_get_state(alp_cma_t *h, double *mean, double *sigma, double *C, doub
     return ALP_OK;
 }
 
+int alp_cma_get_state(alp_cma_t *h, double *mean, double *sigma, double *C, double *p_sigma, double *pc, int64_t *generation, double *B,
+                      double *Dvec) {
+    return alp_cma_get_state_at(h, 0, mean, sigma, C, p_sigma, pc, generation, B, Dvec);
+}
+
 int alp_cma_run(alp_cma_t *h, int64_t generations, int loss_kind, double f_scale) {
     if (int rc = usable(h, "alp_cma_run")) return rc;
     ALP_REQUIRE(generations >= 0, "generations is negative");
@@ -616,9 +673,10 @@ int alp_cma_run(alp_cma_t *h, int64_t generations, int loss_kind, double f_scale
     if (p->pending_P > 0 || p->loop_pending)
         return fail(ALP_ESTATE, "alp_cma_run: the point set has an evaluation enqueued that has not been waited for");
     if (generations == 0) return ALP_OK;
-    if (int rc = points_pop_reserve(p, h->hy.P)) return rc;
-    const int64_t P = h->hy.P;
-    const unsigned grid = (unsigned)((P * 64 + 255) / 256);
+    const int64_t R = h->rows();
+    if (int rc = points_pop_reserve(p, R)) return rc;
+    const unsigned grid = (unsigned)((R * 64 + 255) / 256);
+    const bool batched = h->hy.K > 1;    // one start: the grid of alp_eval_population, as before multi-start
     hipStream_t st = ctx().stream;
     h->pending = true;                   // from the first launch on: a failure below still needs alp_cma_wait
     p->loop_pending = true;
@@ -626,9 +684,9 @@ int alp_cma_run(alp_cma_t *h, int64_t generations, int loss_kind, double f_scale
         if (p->precision == ALP_F64) launch_generation_t<double>(h, grid, st);
         else launch_generation_t<float>(h, grid, st);
         ALP_HIP(hipGetLastError());
-        if (int rc = popeval_launch(p, P, loss_kind, f_scale, h->lens_free, h->shared_pose)) return rc;
-        hipLaunchKernelGGL(cma_tell_kernel<true>, dim3(1), dim3(TELL_THREADS), 0, st, h->hy, h->st, (const double *)h->w, (const double *)h->X,
-                           (const double *)p->sums_dev, (const double *)nullptr, h->loss, h->order, h->ys, h->wio);
+        if (int rc = popeval_launch(p, R, loss_kind, f_scale, h->lens_free, h->shared_pose, batched)) return rc;
+        hipLaunchKernelGGL(cma_tell_kernel<true>, dim3(h->hy.K), dim3(TELL_THREADS), 0, st, h->hy, h->st, (const double *)h->w,
+                           (const double *)h->X, (const double *)p->sums_dev, (const double *)nullptr, h->loss, h->order, h->ys, h->wio);
         ALP_HIP(hipGetLastError());
     }
     h->have_last = true;
@@ -648,14 +706,14 @@ int alp_cma_wait(alp_cma_t *h) {
 int alp_cma_tell_host(alp_cma_t *h, const double *X, const double *losses, int32_t *order_out) {
     if (int rc = usable(h, "alp_cma_tell_host")) return rc;
     ALP_REQUIRE(X && losses, "NULL argument");
-    const int P = h->hy.P, D = h->hy.D;
+    const int64_t R = h->rows(), D = h->hy.D;
     hipStream_t st = ctx().stream;
-    ALP_HIP(hipMemcpyAsync(h->X, X, (size_t)P * D * 8, hipMemcpyHostToDevice, st));
-    ALP_HIP(hipMemcpyAsync(h->vals, losses, (size_t)P * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(cma_tell_kernel<true>, dim3(1), dim3(TELL_THREADS), 0, st, h->hy, h->st, (const double *)h->w, (const double *)h->X,
-                       (const double *)nullptr, (const double *)h->vals, h->loss, h->order, h->ys, h->wio);
+    ALP_HIP(hipMemcpyAsync(h->X, X, (size_t)(R * D) * 8, hipMemcpyHostToDevice, st));
+    ALP_HIP(hipMemcpyAsync(h->vals, losses, (size_t)R * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(cma_tell_kernel<true>, dim3(h->hy.K), dim3(TELL_THREADS), 0, st, h->hy, h->st, (const double *)h->w,
+                       (const double *)h->X, (const double *)nullptr, (const double *)h->vals, h->loss, h->order, h->ys, h->wio);
     ALP_HIP(hipGetLastError());
-    if (order_out) ALP_HIP(hipMemcpyAsync(order_out, h->order, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+    if (order_out) ALP_HIP(hipMemcpyAsync(order_out, h->order, (size_t)R * 4, hipMemcpyDeviceToHost, st));
     ALP_HIP(hipStreamSynchronize(st));
     h->have_last = false;                // X no longer holds a device generation
     return ALP_OK;
@@ -664,11 +722,11 @@ int alp_cma_tell_host(alp_cma_t *h, const double *X, const double *losses, int32
 int alp_cma_fetch_last(alp_cma_t *h, double *X, double *cand, double *losses) {
     if (int rc = usable(h, "alp_cma_fetch_last")) return rc;
     if (!h->have_last) return fail(ALP_ESTATE, "alp_cma_fetch_last: no device generation has run");
-    const int P = h->hy.P, D = h->hy.D;
+    const int64_t R = h->rows(), D = h->hy.D;
     hipStream_t st = ctx().stream;
-    if (X) ALP_HIP(hipMemcpyAsync(X, h->X, (size_t)P * D * 8, hipMemcpyDeviceToHost, st));
-    if (cand) ALP_HIP(hipMemcpyAsync(cand, h->cand, (size_t)P * ALP_NPARAM * 8, hipMemcpyDeviceToHost, st));
-    if (losses) ALP_HIP(hipMemcpyAsync(losses, h->loss, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+    if (X) ALP_HIP(hipMemcpyAsync(X, h->X, (size_t)(R * D) * 8, hipMemcpyDeviceToHost, st));
+    if (cand) ALP_HIP(hipMemcpyAsync(cand, h->cand, (size_t)R * ALP_NPARAM * 8, hipMemcpyDeviceToHost, st));
+    if (losses) ALP_HIP(hipMemcpyAsync(losses, h->loss, (size_t)R * 8, hipMemcpyDeviceToHost, st));
     ALP_HIP(hipStreamSynchronize(st));
     return ALP_OK;
 }

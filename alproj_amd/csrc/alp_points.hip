@@ -170,7 +170,7 @@ int ensure_pop_scratch(alp_points *p, int64_t P, int nblk) {
 
 // the launch half of enqueue_popeval (alp_points_internal.h: popeval_launch): the records lie in p->cand_dev
 template <typename T>
-int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose) {
+int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false) {
     using Kernel = void (*)(const T *, const T *, const T *, const T *, const T *, int64_t, const PoseRec<T> *, int, T,
                             double *, const PoseRec<T> *);
     const int which = (loss_kind == ALP_LOSS_HUBER ? 3 : 0) + (lens_free ? 2 : (shared_pose ? 1 : 0));
@@ -234,6 +234,15 @@ int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bo
         if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 1 && b >= 1 && b <= tiles) { nblk = a; ytiles = b; }
     }
     if (rows < nblk) nblk = (int)(rows > 0 ? rows : 1);
+    if (batched) {
+        const int64_t cap = POP_BATCHED_PARTIALS_BYTES / (8 * P);
+        if (nblk > cap) nblk = (int)(cap > 1 ? cap : 1);
+        const int64_t tiles = (P + PopCfg<T>::TC - 1) / PopCfg<T>::TC, fill = (int64_t)ctx().cu_count * 4;
+        if (ytiles == 1 && tiles >= 2 && nblk < fill) {
+            const int64_t cols = (fill + nblk - 1) / nblk;
+            ytiles = (int)(cols < tiles ? cols : tiles);
+        }
+    }
     if (int rc = ensure_pop_scratch(p, P, nblk)) return rc;
     if (!p->ev[0]) {            // all three or none: a partial failure must not leave ev[1] / ev[2] NULL for good
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -394,9 +403,9 @@ int residuals_impl(alp_points *p, const double *cand, int64_t B, double *out) {
 }  // namespace
 
 namespace alp {
-int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose) {
-    return p->precision == ALP_F64 ? popeval_launch_t<double>(p, P, loss_kind, f_scale, lens_free, shared_pose)
-                                   : popeval_launch_t<float>(p, P, loss_kind, f_scale, lens_free, shared_pose);
+int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched) {
+    return p->precision == ALP_F64 ? popeval_launch_t<double>(p, P, loss_kind, f_scale, lens_free, shared_pose, batched)
+                                   : popeval_launch_t<float>(p, P, loss_kind, f_scale, lens_free, shared_pose, batched);
 }
 int points_pop_reserve(alp_points *p, int64_t P) { return ensure_pop_scratch(p, P, 0); }
 }  // namespace alp

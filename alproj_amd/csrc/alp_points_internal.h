@@ -52,7 +52,11 @@ namespace alp {
 // lens-free ones at [cand_cap, cand_cap + P) when `lens_free`): grid choice, popeval_kernel + reduce_partials_kernel into
 // p->sums_dev (P + 1 sums, the last one the vertex count), the all-reduce of those sums when a communicator exists, and
 // last_info / the timing events.  Enqueue only.  The caller has reserved the scratch for P (points_pop_reserve).
-int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose);
+// `batched` (the device loop's multi-start launch, K starts x P candidates): the stripe count is capped so that the partial sums
+// (stripes x P doubles) stay within POP_BATCHED_PARTIALS_BYTES, and when the stripes alone do not fill the GPU (a GCP-sized set
+// has a handful of rows) the grid gets candidate-tile columns up to four workgroups per CU.  Every other launch keeps its grid.
+constexpr int64_t POP_BATCHED_PARTIALS_BYTES = (int64_t)128 << 20;
+int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false);
 // population scratch (records, sums) for P candidates
 int points_pop_reserve(alp_points *p, int64_t P);
 // alp_points_destroy: a device loop built on the set loses it (its later calls return ALP_ESTATE)

@@ -20,7 +20,8 @@ Extra keyword arguments (all optional, defaults keep the reference behaviour):
 -- None, the default, is the reference's own float64 arithmetic (optimize.py:329-357) for every
 point set of up to ``F64_MAX_POINTS`` = 4 M points (any GCP-scale use of the reference: float64
 costs nothing there) and float32 (20 B/vertex, ~1e-3 px) for DSM-sized sets above it;
-``seed`` makes the CMA-ES trajectory reproducible.  There is no CPU fallback: without the
+``seed`` makes the CMA-ES trajectory reproducible; ``starts=K`` runs K seeded CMA-ES starts side by side and keeps the
+best (``CMAOptimizer.optimize``).  There is no CPU fallback: without the
 HIP library / a GPU every function that touches points raises ``AlprojHipError``.
 """
 from math import cos, pi, sin, tan
@@ -35,7 +36,7 @@ from .cma import CMA
 
 __all__ = ["intrinsic_mat", "extrinsic_mat", "project", "rmse", "huber_loss",
            "compute_residuals", "DEFAULT_BOUND_WIDTHS", "bounds_to_array", "BaseOptimizer",
-           "CMAOptimizer", "LsqOptimizer"]
+           "CMAOptimizer", "LsqOptimizer", "start_seeds", "best_start"]
 
 
 # ------------------------------------------------------------------------------------------
@@ -275,6 +276,21 @@ class BaseOptimizer:
         return params
 
 
+def start_seeds(seed, starts):
+    """The seeds of ``CMAOptimizer.optimize(..., starts=K)``: start k uses ``seed + k`` mod 2**63.  ``seed=None`` draws one
+    base seed the way ``cma.CMA`` draws its own (with a communicator, rank 0's is broadcast before this is called)."""
+    base = int(np.random.SeedSequence().entropy % (1 << 63)) if seed is None else int(seed)
+    return [(base + k) % (1 << 63) for k in range(int(starts))]
+
+
+def best_start(errors):
+    """The start ``CMAOptimizer.optimize(..., starts=K)`` returns: the smallest final error, the lowest index on ties; a NaN
+    error never wins unless every error is NaN, and then start 0 does."""
+    e = np.asarray(errors, dtype=np.float64)
+    ok = ~np.isnan(e)
+    return int(np.flatnonzero(ok)[np.argmin(e[ok])]) if ok.any() else 0
+
+
 class CMAOptimizer(BaseOptimizer):
     """CMA-ES optimiser of the camera parameters (reference optimize.py:322-439).
 
@@ -313,15 +329,33 @@ class CMAOptimizer(BaseOptimizer):
         if "w" in self.target_params or "h" in self.target_params:
             raise ValueError("w and h cannot be optimised: every candidate must share the image size")
 
+    MAX_STARTS = 1024
+    MAX_START_CANDIDATES = 65536
+
+    def _check_starts(self, starts, population_size):
+        """the multi-start configurations optimize() refuses: ValueError before the GPU is touched"""
+        if int(starts) != starts or int(starts) < 1:
+            raise ValueError("starts must be a positive integer")
+        if int(starts) > self.MAX_STARTS:
+            raise ValueError(f"starts must be at most {self.MAX_STARTS}")
+        if int(starts) * int(population_size) > self.MAX_START_CANDIDATES:
+            raise ValueError(f"starts * population_size must be at most {self.MAX_START_CANDIDATES}")
+
     def optimize(self, sigma=0.2, bound_widths=None, generation=1000, population_size=10,
-                 n_max_resampling=100, f_scale=None, precision=None, seed=None, progress=True, device_loop=False):
+                 n_max_resampling=100, f_scale=None, precision=None, seed=None, progress=True, device_loop=False, starts=1):
         """Run CMA-ES; returns ``(params, error)`` like the reference: the best candidate of
         the LAST generation (optimize.py:427, quirk Q9) and its mean reprojection distance.
         ``precision=None``: float64 like the reference up to F64_MAX_POINTS points (per rank), float32 above.
         ``device_loop=True``: generations 0 .. G-2 run on the device with the optimiser's state there (alp_cma_run: draw,
         candidate matrix, fold, evaluation, tell, no host round trip in between); the state then comes back into the host
         CMA once and the LAST generation runs the host path below (device sampler, argmin with its float64 confirmation,
-        final error).  population_size <= 4096, at most 32 targets."""
+        final error).  population_size <= 4096, at most 32 targets.
+        ``starts=K``: K independent starts, start k the run ``optimize(seed=seed + k)`` (``start_seeds``) would make, with the
+        candidates of all K evaluated together each generation (device loop: K tells side by side); returns the start with
+        the smallest final error (``best_start``).  1 <= K <= 1024, K * population_size <= 65536.  ``self.start_results``: the
+        ``(seed, params, error)`` of every start in start order (one entry when starts=1)."""
+        if starts != 1:
+            self._check_starts(starts, population_size)
         if device_loop:
             self._check_device_loop(generation, population_size)
         bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
@@ -345,6 +379,12 @@ class CMAOptimizer(BaseOptimizer):
             seed, precision = int(s[0]), ("f64" if s[1] else "f32")
         loss_function = self._loss_function(bounds, f_scale, precision)
         pts = loss_function.points
+        if starts != 1:
+            try:
+                return self._optimize_starts(loss_function, start_seeds(seed, starts), bounds, normalized_init, sigma, generation,
+                                             population_size, n_max_resampling, f_scale, progress, device_loop, world)
+            finally:
+                pts.close()
         try:
             optimizer = CMA(mean=normalized_init.astype("float64"), sigma=float(sigma),
                             bounds=normalized_bounds, population_size=population_size,
@@ -392,7 +432,63 @@ class CMAOptimizer(BaseOptimizer):
                 err, _ = pts.eval_population(final, _lib.LOSS_MEAN_DIST, 0.0)
         finally:
             pts.close()
+        self.start_results = [(seed, params, float(err[0]))]
         return params, float(err[0])
+
+    def _optimize_starts(self, loss_function, seeds, bounds, normalized_init, sigma, generation, population_size, n_max_resampling,
+                         f_scale, progress, device_loop, world):
+        """optimize(..., starts=K > 1): K host CMAs, one evaluation of the K * P candidates per generation (one broadcast of them
+        with a communicator) and K tells; with device_loop generations 0 .. G-2 of all starts run in ONE device loop (K tells
+        side by side).  The last generation evaluates each start on its own, with its argmin (and that argmin's float64
+        confirmation on a float32 set) exactly as a single run."""
+        pts = loss_function.points
+        lower, upper = bounds[:, 0], bounds[:, 1]
+        d, K, P = len(self.target_params), len(seeds), int(population_size)
+        normalized_bounds = np.column_stack([np.zeros(d), np.ones(d)])
+        device_sampler = device_loop or (d <= 32 and population_size * d >= 2048)       # the single run's rule
+        opts = [CMA(mean=normalized_init.astype("float64"), sigma=float(sigma), bounds=normalized_bounds, population_size=population_size,
+                    n_max_resampling=n_max_resampling, seed=s, sampler=_lib.cma_sample if device_sampler else None) for s in seeds]
+        kind = _lib.LOSS_MEAN_DIST if f_scale is None else _lib.LOSS_HUBER
+        first = 0
+        if device_loop and generation > 1:
+            loop = _lib.CmaDevice(pts, _lib.params_vector(self.params_init), [_lib.PARAM_KEYS.index(t) for t in self.target_params],
+                                  lower, upper, opts[0], seeds=[o._sampler_seed for o in opts])
+            try:
+                for k, o in enumerate(opts):
+                    loop.set_state(o.get_state(), start=k)
+                loop.run(generation - 1, kind, 0.0 if f_scale is None else float(f_scale))
+                loop.wait()
+                for k, o in enumerate(opts):
+                    o.set_state(loop.get_state(start=k))
+            finally:
+                loop.close()
+            first = generation - 1
+        it = range(first, generation)
+        best_normalized = [normalized_init] * K
+        for g in (tqdm(it) if progress else it):
+            X = np.ascontiguousarray(np.concatenate([o.ask_population() for o in opts]))
+            if world > 1:
+                _lib.comm_bcast(X, root=0)
+            if g == generation - 1:
+                for k, o in enumerate(opts):
+                    Xk = X[k * P:(k + 1) * P]
+                    losses, amin = loss_function(Xk, True)
+                    best_normalized[k] = Xk[amin].copy()
+                    o.tell_population(Xk, losses)
+            else:
+                losses, _ = loss_function(X, False)
+                for k, o in enumerate(opts):
+                    o.tell_population(X[k * P:(k + 1) * P], losses[k * P:(k + 1) * P])
+        best_values = [b * (upper - lower) + lower for b in best_normalized]
+        # the final float64 mean distance of every start, one evaluation each as in a single run
+        if pts.precision == _lib.ALP_F32 and pts.n <= self.F64_FINAL_MAX_POINTS:
+            with self._device_points("f64") as p64:
+                errs = [float(p64.eval_population(self._candidate_matrix(v), _lib.LOSS_MEAN_DIST, 0.0)[0][0]) for v in best_values]
+        else:
+            errs = [float(pts.eval_population(self._candidate_matrix(v), _lib.LOSS_MEAN_DIST, 0.0)[0][0]) for v in best_values]
+        self.start_results = [(s, self._result_params(v), e) for s, v, e in zip(seeds, best_values, errs)]
+        b = best_start(errs)
+        return self.start_results[b][1], self.start_results[b][2]
 
     F64_FINAL_MAX_POINTS = F64_MAX_POINTS
 

@@ -304,6 +304,21 @@ int alp_cma_tell_host(alp_cma_t *h, const double *X, const double *losses, int32
 /* The last device generation: X[P x D] (normalised draws), cand[P x 25] (the candidate matrix), losses[P]; any may be NULL.
  * For tests. */
 int alp_cma_fetch_last(alp_cma_t *h, double *X, double *cand, double *losses);
+/* Multi-start (CMAOptimizer.optimize(..., starts=K)): K independent states that share D, P, the targets, bounds, weights and
+ * hyperparameters; start k draws with seeds[k].  One generation is still three launches: the draw of K * P candidates (row
+ * k * P + i is draw i of start k, the bits of alp_cma_sample(..., seeds[k], g) from start k's state), one evaluation of K * P
+ * candidates (+ one all-reduce of K * P + 1 sums), and a tell of K workgroups, one per start.  1 <= K <= 1024, K * P <= 65536;
+ * alp_cma_create is the case K = 1.  On a K-start handle alp_cma_tell_host and alp_cma_fetch_last take and return K * P rows
+ * in start order (the order is per start: indices 0 .. P-1 within each start's rows); alp_cma_set_state / alp_cma_get_state
+ * are start 0.  The evaluation scratch of `pts` grows to K * P candidates; for K > 1 its partial sums stay within 128 MB. */
+int alp_cma_create_starts(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                          const double *upper, int64_t P, int K, const double *weights, const double hyper[ALP_CMA_NHYPER],
+                          int n_max_resampling, const uint64_t *seeds, alp_cma_t **out);
+/* alp_cma_set_state / alp_cma_get_state of start k (0 <= k < K, else ALP_EINVAL). */
+int alp_cma_set_state_at(alp_cma_t *h, int k, const double *mean, double sigma, const double *C, const double *p_sigma, const double *pc,
+                         int64_t generation);
+int alp_cma_get_state_at(alp_cma_t *h, int k, double *mean, double *sigma, double *C, double *p_sigma, double *pc, int64_t *generation,
+                         double *B, double *Dvec);
 
 /* Loss of two host arrays of pixel coordinates (n x 2 row-major doubles each): replaces the
  * stand-alone rmse(), src/alproj/optimize.py:157-178 (loss_kind ALP_LOSS_MEAN_DIST) and
