@@ -896,8 +896,8 @@ class CmaDevice:
     ``run(G)`` enqueues G generations (draw, candidate matrix, fold, population evaluation, tell) without the host in between.
     ``points``: the Points the candidates are evaluated on; ``template``: the 25-vector of params_init; ``targets``: ABI indices
     of the targets; ``lower`` / ``upper``: their bounds; ``cma``: the host CMA whose constants (and seed) the loop takes.
-    ``seeds`` (optional, length K): K independent starts that share those constants, start k drawing with seeds[k]
-    (alp_cma_create_starts); ``fetch_last`` / ``tell_host`` then take and return K * P rows in start order."""
+    ``seeds`` (length K, default ``[cma._sampler_seed]``): K independent starts that share those constants, start k drawing
+    with seeds[k] (alp_cma_create_starts); ``fetch_last`` / ``tell_host`` take and return K * P rows in start order."""
 
     def __init__(self, points, template, targets, lower, upper, cma, seeds=None):
         l = lib()
@@ -911,17 +911,11 @@ class CmaDevice:
         hyper = np.array([cma._mu, cma._mu_eff, cma._c1, cma._cmu, cma._cc, cma._c_sigma, cma._d_sigma, cma._chi_n, cma._cm,
                           np.sum(cma._weights)], dtype=np.float64)
         h = _c_void_p()
-        if seeds is None:
-            self.K = 1
-            check(l.alp_cma_create(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo), as_dp(hi),
-                                   self.P, as_dp(w), as_dp(hyper), int(cma._n_max_resampling),
-                                   ctypes.c_uint64(int(cma._sampler_seed) & (2**64 - 1)), ctypes.byref(h)))
-        else:
-            sd = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
-            self.K = int(len(sd))
-            check(l.alp_cma_create_starts(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo),
-                                          as_dp(hi), self.P, self.K, as_dp(w), as_dp(hyper), int(cma._n_max_resampling),
-                                          sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(h)))
+        sd = np.array([int(s) & (2**64 - 1) for s in ([cma._sampler_seed] if seeds is None else seeds)], dtype=np.uint64)
+        self.K = int(len(sd))
+        check(l.alp_cma_create_starts(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo),
+                                      as_dp(hi), self.P, self.K, as_dp(w), as_dp(hyper), int(cma._n_max_resampling),
+                                      sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(h)))
         self._h = h
         self._lib = l
         self.points = points
@@ -939,32 +933,25 @@ class CmaDevice:
     def __exit__(self, *exc):
         self.close()
 
-    def set_state(self, state, start=None):
-        """``state``: the dict of cma.CMA.get_state(); ``start``: the start it is for (None: start 0)"""
+    def set_state(self, state, start=0):
+        """``state``: the dict of cma.CMA.get_state(); ``start``: the start it is for"""
         D = self.D
         mean = np.ascontiguousarray(state["mean"], dtype=np.float64).reshape(D)
         C = np.ascontiguousarray(state["C"], dtype=np.float64).reshape(D, D)
         ps = np.ascontiguousarray(state["p_sigma"], dtype=np.float64).reshape(D)
         pc = np.ascontiguousarray(state["pc"], dtype=np.float64).reshape(D)
-        if start is None:
-            check(self._lib.alp_cma_set_state(self._h, as_dp(mean), float(state["sigma"]), as_dp(C), as_dp(ps), as_dp(pc), int(state["g"])))
-        else:
-            check(self._lib.alp_cma_set_state_at(self._h, int(start), as_dp(mean), float(state["sigma"]), as_dp(C), as_dp(ps), as_dp(pc),
-                                                 int(state["g"])))
+        check(self._lib.alp_cma_set_state_at(self._h, int(start), as_dp(mean), float(state["sigma"]), as_dp(C), as_dp(ps), as_dp(pc),
+                                             int(state["g"])))
 
-    def get_state(self, eigen=False, start=None):
+    def get_state(self, eigen=False, start=0):
         """the dict cma.CMA.set_state() takes; ``eigen=True`` adds "B" (eigenvectors as columns) and "D" of the next draw;
-        ``start``: the start to read (None: start 0)"""
+        ``start``: the start to read"""
         D = self.D
         mean, ps, pc, d = (np.empty(D) for _ in range(4))
         C, B = np.empty((D, D)), np.empty((D, D))
         sigma, g = _c_double(), _c_i64()
-        if start is None:
-            check(self._lib.alp_cma_get_state(self._h, as_dp(mean), ctypes.byref(sigma), as_dp(C), as_dp(ps), as_dp(pc), ctypes.byref(g),
-                                              as_dp(B), as_dp(d)))
-        else:
-            check(self._lib.alp_cma_get_state_at(self._h, int(start), as_dp(mean), ctypes.byref(sigma), as_dp(C), as_dp(ps), as_dp(pc),
-                                                 ctypes.byref(g), as_dp(B), as_dp(d)))
+        check(self._lib.alp_cma_get_state_at(self._h, int(start), as_dp(mean), ctypes.byref(sigma), as_dp(C), as_dp(ps), as_dp(pc),
+                                             ctypes.byref(g), as_dp(B), as_dp(d)))
         st = {"mean": mean, "sigma": float(sigma.value), "C": C, "p_sigma": ps, "pc": pc, "g": int(g.value)}
         if eigen:
             st.update(B=B, D=d)

@@ -24,6 +24,7 @@ costs nothing there) and float32 (20 B/vertex, ~1e-3 px) for DSM-sized sets abov
 best (``CMAOptimizer.optimize``).  There is no CPU fallback: without the
 HIP library / a GPU every function that touches points raises ``AlprojHipError``.
 """
+from contextlib import nullcontext
 from math import cos, pi, sin, tan
 
 import numpy as np
@@ -312,7 +313,7 @@ class CMAOptimizer(BaseOptimizer):
             cand = self._candidate_matrix(x * (upper - lower) + lower)
             return pts.eval_population(cand, kind, fs, want_argmin)
 
-        _proj_error.points = pts
+        _proj_error.points, _proj_error.kind, _proj_error.f_scale = pts, kind, fs
         return _proj_error
 
     DEVICE_LOOP_MAX_POPULATION = 4096
@@ -333,12 +334,13 @@ class CMAOptimizer(BaseOptimizer):
     MAX_START_CANDIDATES = 65536
 
     def _check_starts(self, starts, population_size):
-        """the multi-start configurations optimize() refuses: ValueError before the GPU is touched"""
+        """the multi-start configurations optimize() refuses: ValueError before the GPU is touched (a single start keeps
+        alp_eval_population's own population limit)"""
         if int(starts) != starts or int(starts) < 1:
             raise ValueError("starts must be a positive integer")
         if int(starts) > self.MAX_STARTS:
             raise ValueError(f"starts must be at most {self.MAX_STARTS}")
-        if int(starts) * int(population_size) > self.MAX_START_CANDIDATES:
+        if int(starts) > 1 and int(starts) * int(population_size) > self.MAX_START_CANDIDATES:
             raise ValueError(f"starts * population_size must be at most {self.MAX_START_CANDIDATES}")
 
     def optimize(self, sigma=0.2, bound_widths=None, generation=1000, population_size=10,
@@ -346,16 +348,14 @@ class CMAOptimizer(BaseOptimizer):
         """Run CMA-ES; returns ``(params, error)`` like the reference: the best candidate of
         the LAST generation (optimize.py:427, quirk Q9) and its mean reprojection distance.
         ``precision=None``: float64 like the reference up to F64_MAX_POINTS points (per rank), float32 above.
-        ``device_loop=True``: generations 0 .. G-2 run on the device with the optimiser's state there (alp_cma_run: draw,
-        candidate matrix, fold, evaluation, tell, no host round trip in between); the state then comes back into the host
-        CMA once and the LAST generation runs the host path below (device sampler, argmin with its float64 confirmation,
-        final error).  population_size <= 4096, at most 32 targets.
-        ``starts=K``: K independent starts, start k the run ``optimize(seed=seed + k)`` (``start_seeds``) would make, with the
-        candidates of all K evaluated together each generation (device loop: K tells side by side); returns the start with
-        the smallest final error (``best_start``).  1 <= K <= 1024, K * population_size <= 65536.  ``self.start_results``: the
-        ``(seed, params, error)`` of every start in start order (one entry when starts=1)."""
-        if starts != 1:
-            self._check_starts(starts, population_size)
+        ``starts=K``: K independent starts, start k the run ``optimize(seed=seed + k)`` (``start_seeds``) would make: one
+        evaluation of all K * population_size candidates and K tells per generation, the last generation one evaluation (with
+        its argmin) per start; returns the start with the smallest final error (``best_start``).  1 <= K <= 1024, K *
+        population_size <= 65536 for K > 1.  ``self.start_results``: the ``(seed, params, error)`` of every start in start order.
+        ``device_loop=True``: generations 0 .. G-2 of all starts run in one device loop (alp_cma_run: draw, candidate matrix,
+        fold, evaluation, K tells, no host round trip in between); the states then come back into the host CMAs once and the
+        LAST generation runs on the host.  population_size <= 4096, at most 32 targets."""
+        self._check_starts(starts, population_size)
         if device_loop:
             self._check_device_loop(generation, population_size)
         bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
@@ -379,113 +379,58 @@ class CMAOptimizer(BaseOptimizer):
             seed, precision = int(s[0]), ("f64" if s[1] else "f32")
         loss_function = self._loss_function(bounds, f_scale, precision)
         pts = loss_function.points
-        if starts != 1:
-            try:
-                return self._optimize_starts(loss_function, start_seeds(seed, starts), bounds, normalized_init, sigma, generation,
-                                             population_size, n_max_resampling, f_scale, progress, device_loop, world)
-            finally:
-                pts.close()
         try:
-            optimizer = CMA(mean=normalized_init.astype("float64"), sigma=float(sigma),
-                            bounds=normalized_bounds, population_size=population_size,
-                            n_max_resampling=n_max_resampling, seed=seed,
-                            # the device sampler costs a launch + a copy (~0.07 ms): it pays from a few thousand
-                            # deviates per generation (pop 256 / D 21: 0.10 ms against 7 ms of numpy at sigma = 1);
-                            # at GCP scale (pop 50 / D 9) the numpy path is the faster one (0.17 vs 0.24 ms / generation)
-                            sampler=_lib.cma_sample if (device_loop or (d <= 32 and population_size * d >= 2048)) else None)
+            seeds = start_seeds(seed, starts)
+            K, P = len(seeds), int(population_size)
+            # the device sampler costs a launch + a copy (~0.07 ms): it pays from a few thousand
+            # deviates per generation (pop 256 / D 21: 0.10 ms against 7 ms of numpy at sigma = 1);
+            # at GCP scale (pop 50 / D 9) the numpy path is the faster one (0.17 vs 0.24 ms / generation)
+            sampler = _lib.cma_sample if (device_loop or (d <= 32 and population_size * d >= 2048)) else None
+            opts = [CMA(mean=normalized_init.astype("float64"), sigma=float(sigma), bounds=normalized_bounds,
+                        population_size=population_size, n_max_resampling=n_max_resampling, seed=s, sampler=sampler) for s in seeds]
             first = 0
             if device_loop and generation > 1:
                 # every rank runs the same replica: the sums are all-reduced, the tell is deterministic
                 loop = _lib.CmaDevice(pts, _lib.params_vector(self.params_init), [_lib.PARAM_KEYS.index(t) for t in self.target_params],
-                                      lower, upper, optimizer)
+                                      lower, upper, opts[0], seeds=[o._sampler_seed for o in opts])
                 try:
-                    loop.set_state(optimizer.get_state())
-                    loop.run(generation - 1, _lib.LOSS_MEAN_DIST if f_scale is None else _lib.LOSS_HUBER,
-                             0.0 if f_scale is None else float(f_scale))
+                    for k, o in enumerate(opts):
+                        loop.set_state(o.get_state(), start=k)
+                    loop.run(generation - 1, loss_function.kind, loss_function.f_scale)
                     loop.wait()
-                    optimizer.set_state(loop.get_state())
+                    for k, o in enumerate(opts):
+                        o.set_state(loop.get_state(start=k))
                 finally:
                     loop.close()
                 first = generation - 1
             it = range(first, generation)
-            best_normalized = normalized_init
+            best_normalized = [normalized_init] * K
             for g in (tqdm(it) if progress else it):
-                X = np.ascontiguousarray(optimizer.ask_population())
+                X = np.ascontiguousarray(np.concatenate([o.ask_population() for o in opts]))
                 if world > 1:
                     _lib.comm_bcast(X, root=0)
-                # the result is the best candidate of the LAST generation (optimize.py:427, quirk Q9): only there is the
-                # argmin itself needed -- and confirmed in float64 among near-tied candidates of a float32 point set
-                losses, amin = loss_function(X, g == generation - 1)
-                best_normalized = X[amin].copy()
-                optimizer.tell_population(X, losses)
-            best_values = best_normalized * (upper - lower) + lower
-            params = self._result_params(best_values)
+                if g == generation - 1:
+                    # the result is the best candidate of the LAST generation (optimize.py:427, quirk Q9): only there is the
+                    # argmin itself needed -- and confirmed in float64 among near-tied candidates of a float32 point set
+                    for k, o in enumerate(opts):
+                        Xk = X[k * P:(k + 1) * P]
+                        losses, amin = loss_function(Xk, True)
+                        best_normalized[k] = Xk[amin].copy()
+                        o.tell_population(Xk, losses)
+                else:
+                    losses, _ = loss_function(X, False)
+                    for k, o in enumerate(opts):
+                        o.tell_population(X[k * P:(k + 1) * P], losses[k * P:(k + 1) * P])
+            best_values = [b * (upper - lower) + lower for b in best_normalized]
             # final error is always the mean distance (optimize.py:435-437), and float64 like the
             # reference's (and like LsqOptimizer's): a float32 point set of GCP size is evaluated once
             # more from a float64 copy; DSM-sized sets keep their float32 residency (a collective when
-            # several ranks hold shards: every rank must reach this line)
-            final = self._candidate_matrix(best_values)
-            if pts.precision == _lib.ALP_F32 and pts.n <= self.F64_FINAL_MAX_POINTS:
-                with self._device_points("f64") as p64:
-                    err, _ = p64.eval_population(final, _lib.LOSS_MEAN_DIST, 0.0)
-            else:
-                err, _ = pts.eval_population(final, _lib.LOSS_MEAN_DIST, 0.0)
+            # several ranks hold shards: every rank must reach this line).  One evaluation per start.
+            f64_copy = pts.precision == _lib.ALP_F32 and pts.n <= self.F64_FINAL_MAX_POINTS
+            with (self._device_points("f64") if f64_copy else nullcontext(pts)) as p:
+                errs = [float(p.eval_population(self._candidate_matrix(v), _lib.LOSS_MEAN_DIST, 0.0)[0][0]) for v in best_values]
         finally:
             pts.close()
-        self.start_results = [(seed, params, float(err[0]))]
-        return params, float(err[0])
-
-    def _optimize_starts(self, loss_function, seeds, bounds, normalized_init, sigma, generation, population_size, n_max_resampling,
-                         f_scale, progress, device_loop, world):
-        """optimize(..., starts=K > 1): K host CMAs, one evaluation of the K * P candidates per generation (one broadcast of them
-        with a communicator) and K tells; with device_loop generations 0 .. G-2 of all starts run in ONE device loop (K tells
-        side by side).  The last generation evaluates each start on its own, with its argmin (and that argmin's float64
-        confirmation on a float32 set) exactly as a single run."""
-        pts = loss_function.points
-        lower, upper = bounds[:, 0], bounds[:, 1]
-        d, K, P = len(self.target_params), len(seeds), int(population_size)
-        normalized_bounds = np.column_stack([np.zeros(d), np.ones(d)])
-        device_sampler = device_loop or (d <= 32 and population_size * d >= 2048)       # the single run's rule
-        opts = [CMA(mean=normalized_init.astype("float64"), sigma=float(sigma), bounds=normalized_bounds, population_size=population_size,
-                    n_max_resampling=n_max_resampling, seed=s, sampler=_lib.cma_sample if device_sampler else None) for s in seeds]
-        kind = _lib.LOSS_MEAN_DIST if f_scale is None else _lib.LOSS_HUBER
-        first = 0
-        if device_loop and generation > 1:
-            loop = _lib.CmaDevice(pts, _lib.params_vector(self.params_init), [_lib.PARAM_KEYS.index(t) for t in self.target_params],
-                                  lower, upper, opts[0], seeds=[o._sampler_seed for o in opts])
-            try:
-                for k, o in enumerate(opts):
-                    loop.set_state(o.get_state(), start=k)
-                loop.run(generation - 1, kind, 0.0 if f_scale is None else float(f_scale))
-                loop.wait()
-                for k, o in enumerate(opts):
-                    o.set_state(loop.get_state(start=k))
-            finally:
-                loop.close()
-            first = generation - 1
-        it = range(first, generation)
-        best_normalized = [normalized_init] * K
-        for g in (tqdm(it) if progress else it):
-            X = np.ascontiguousarray(np.concatenate([o.ask_population() for o in opts]))
-            if world > 1:
-                _lib.comm_bcast(X, root=0)
-            if g == generation - 1:
-                for k, o in enumerate(opts):
-                    Xk = X[k * P:(k + 1) * P]
-                    losses, amin = loss_function(Xk, True)
-                    best_normalized[k] = Xk[amin].copy()
-                    o.tell_population(Xk, losses)
-            else:
-                losses, _ = loss_function(X, False)
-                for k, o in enumerate(opts):
-                    o.tell_population(X[k * P:(k + 1) * P], losses[k * P:(k + 1) * P])
-        best_values = [b * (upper - lower) + lower for b in best_normalized]
-        # the final float64 mean distance of every start, one evaluation each as in a single run
-        if pts.precision == _lib.ALP_F32 and pts.n <= self.F64_FINAL_MAX_POINTS:
-            with self._device_points("f64") as p64:
-                errs = [float(p64.eval_population(self._candidate_matrix(v), _lib.LOSS_MEAN_DIST, 0.0)[0][0]) for v in best_values]
-        else:
-            errs = [float(pts.eval_population(self._candidate_matrix(v), _lib.LOSS_MEAN_DIST, 0.0)[0][0]) for v in best_values]
         self.start_results = [(s, self._result_params(v), e) for s, v, e in zip(seeds, best_values, errs)]
         b = best_start(errs)
         return self.start_results[b][1], self.start_results[b][2]

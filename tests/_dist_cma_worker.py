@@ -1,10 +1,11 @@
-"""Worker of tests/test_dist_gloo.py::test_optimisers_*: one rank of a world_size-N gloo group on CPU running the
-PRODUCT's optimiser loops (alproj_amd.optimize.CMAOptimizer.optimize / LsqOptimizer.optimize, including their
-multi-rank branches: seed broadcast, per-generation candidate broadcast, final collective) over its shard of the
-points.  Only the device is stood in for: the communicator calls of alproj_amd._lib go to gloo, and the point set
-is a CPU object whose evaluation is the oracle on the shard + ONE all-reduce of P + 1 doubles, packed and combined
-like the library does (alproj_amd.dist).  Test infrastructure: the product has no such path.
-usage: _dist_cma_worker.py RANK WORLD PORT OUT_NPZ
+"""Worker of tests/test_dist_gloo.py::test_optimisers_* and tests/test_cma_starts.py::test_host_multi_start_over_gloo: one
+rank of a world_size-N gloo group on CPU running the PRODUCT's optimiser loops (alproj_amd.optimize.CMAOptimizer.optimize /
+LsqOptimizer.optimize, including their multi-rank branches: seed broadcast, per-generation candidate broadcast, final
+collective) over its shard of the points.  Only the device is stood in for: the communicator calls of alproj_amd._lib go to
+gloo, and the point set is a CPU object whose evaluation is the oracle on the shard + ONE all-reduce of P + 1 doubles, packed
+and combined like the library does (alproj_amd.dist).  Test infrastructure: the product has no such path.
+usage: _dist_cma_worker.py RANK WORLD PORT OUT_NPZ [MODE]
+MODE "single" (the default): one CMA-ES start and three least-squares solves; "starts": CMAOptimizer.optimize(..., starts=3).
 """
 import os
 import sys
@@ -17,6 +18,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     rank, world, port, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
+    mode = sys.argv[5] if len(sys.argv) > 5 else "single"
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = port
     import pandas as pd
@@ -87,39 +89,49 @@ def main():
         def close(self):
             pass
 
-    aopt.BaseOptimizer._device_points = lambda self, precision: ShardPoints()
+    aopt.BaseOptimizer._device_points = lambda self, precision=None: ShardPoints()
     obj = pd.DataFrame(xyz, columns=["x", "y", "z"])
     img = pd.DataFrame(uv, columns=["u", "v"])
-    res = {"init_err": orc.mean_distance(uv, orc.project_points(xyz, init))}
-    # ---- CMA-ES, nobody passes a seed (the reference's call): rank 0's entropy must reach every rank
-    o = aopt.CMAOptimizer(obj, img, init)
-    o.set_target(syn.TARGETS_D9)
-    X_seen = []
-    ask = aopt.CMA.ask_population
-    tell = aopt.CMA.tell_population
+    if mode == "starts":
+        o = aopt.CMAOptimizer(obj, img, init)
+        o.set_target(syn.TARGETS_D9)
+        params, err = o.optimize(generation=15, sigma=0.3, population_size=12, f_scale=10.0, seed=None, progress=False, starts=3)
+        keys = syn.TARGETS_D9
+        res = dict(params=np.array([params[k] for k in keys]), err=err,
+                   seeds=np.array([s for s, _, _ in o.start_results], dtype=np.uint64),
+                   start_params=np.array([[p[k] for k in keys] for _, p, _ in o.start_results]),
+                   start_errors=np.array([e for _, _, e in o.start_results]), log=np.array([repr(e) for e in log]))
+    else:
+        res = {"init_err": orc.mean_distance(uv, orc.project_points(xyz, init))}
+        # ---- CMA-ES, nobody passes a seed (the reference's call): rank 0's entropy must reach every rank
+        o = aopt.CMAOptimizer(obj, img, init)
+        o.set_target(syn.TARGETS_D9)
+        X_seen = []
+        ask = aopt.CMA.ask_population
+        tell = aopt.CMA.tell_population
 
-    def tell_spy(self, X, losses):
-        X_seen.append(np.array(X, copy=True))
-        return tell(self, X, losses)
+        def tell_spy(self, X, losses):
+            X_seen.append(np.array(X, copy=True))
+            return tell(self, X, losses)
 
-    aopt.CMA.tell_population = tell_spy
-    params, err = o.optimize(generation=20, sigma=0.3, population_size=12, f_scale=10.0, seed=None, progress=False)
-    aopt.CMA.tell_population = tell
-    res["cma_params"] = np.array([params[k] for k in _lib.PARAM_KEYS], dtype=np.float64)
-    res["cma_err"] = err
-    res["cma_X"] = np.stack(X_seen)
-    res["cma_log"] = np.array([repr(e) for e in log])
-    # ---- least squares: every rank gathers all shards' residuals / Jacobian rows and solves the reference's ONE problem
-    for tag, kw in (("lsq", dict(method="trf", loss="linear", max_nfev=30)),
-                    ("lsq_huber", dict(method="trf", loss="huber", f_scale=2.0, max_nfev=30)),
-                    ("lsq_2point", dict(method="dogbox", loss="linear", jac="2-point", max_nfev=30))):
-        del log[:]
-        q = aopt.LsqOptimizer(obj, img, init)
-        q.set_target(["fov", "pan", "tilt", "roll"])
-        lp, lerr = q.optimize(**kw)
-        res[tag + "_params"] = np.array([lp[k] for k in _lib.PARAM_KEYS], dtype=np.float64)
-        res[tag + "_err"] = lerr
-        res[tag + "_log"] = np.array([repr(e) for e in log])
+        aopt.CMA.tell_population = tell_spy
+        params, err = o.optimize(generation=20, sigma=0.3, population_size=12, f_scale=10.0, seed=None, progress=False)
+        aopt.CMA.tell_population = tell
+        res["cma_params"] = np.array([params[k] for k in _lib.PARAM_KEYS], dtype=np.float64)
+        res["cma_err"] = err
+        res["cma_X"] = np.stack(X_seen)
+        res["cma_log"] = np.array([repr(e) for e in log])
+        # ---- least squares: every rank gathers all shards' residuals / Jacobian rows and solves the reference's ONE problem
+        for tag, kw in (("lsq", dict(method="trf", loss="linear", max_nfev=30)),
+                        ("lsq_huber", dict(method="trf", loss="huber", f_scale=2.0, max_nfev=30)),
+                        ("lsq_2point", dict(method="dogbox", loss="linear", jac="2-point", max_nfev=30))):
+            del log[:]
+            q = aopt.LsqOptimizer(obj, img, init)
+            q.set_target(["fov", "pan", "tilt", "roll"])
+            lp, lerr = q.optimize(**kw)
+            res[tag + "_params"] = np.array([lp[k] for k in _lib.PARAM_KEYS], dtype=np.float64)
+            res[tag + "_err"] = lerr
+            res[tag + "_log"] = np.array([repr(e) for e in log])
     np.savez(out, **res)
     dist.barrier()
     dist.destroy_process_group()

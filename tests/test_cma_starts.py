@@ -1,6 +1,6 @@
 """CMAOptimizer.optimize(..., starts=K) on the host: its refusals (before any device call), the seed rule, the best-start rule,
 and the host multi-start against K single runs -- in one process and over gloo in world 2 and 3
-(tests/_dist_cma_starts_worker.py), the oracle standing in for the device's population evaluation."""
+(tests/_dist_cma_worker.py), the oracle standing in for the device's population evaluation."""
 import os
 import subprocess
 import sys
@@ -140,7 +140,10 @@ def test_host_multi_start_is_k_single_runs(oracle_device):
     assert log == [("eval", 30, False)] * 11 + [("eval", 10, True)] * 3 + [("eval", 1, True)] * 3
     assert [s for s, _, _ in multi] == [41, 42, 43]
     for k in range(3):
+        del log[:]
         p1, e1 = o.optimize(seed=41 + k, **kw)
+        # a single run: one evaluation per generation, the argmin asked for only on the last, then the final error
+        assert log == [("eval", 10, False)] * 11 + [("eval", 10, True)] + [("eval", 1, True)]
         assert o.start_results == [(41 + k, p1, e1)]
         assert multi[k][1] == p1 and multi[k][2] == e1
     b = aopt.best_start([e for _, _, e in multi])
@@ -148,14 +151,17 @@ def test_host_multi_start_is_k_single_runs(oracle_device):
     assert err == min(e for _, _, e in multi)
 
 
-def test_host_multi_start_without_seed(oracle_device):
+@pytest.mark.parametrize("starts", [1, 4])
+def test_host_multi_start_without_seed(oracle_device, starts):
     obj, img, init, _ = oracle_device
     o = aopt.CMAOptimizer(obj, img, init)
     o.set_target(["fov", "pan", "tilt"])
-    o.optimize(generation=3, sigma=0.3, population_size=6, progress=False, starts=4)
+    params, err = o.optimize(generation=3, sigma=0.3, population_size=6, progress=False, starts=starts)
     seeds = [s for s, _, _ in o.start_results]
-    assert len(o.start_results) == 4 and len(set(seeds)) == 4
+    assert len(o.start_results) == starts and len(set(seeds)) == starts
+    assert all(isinstance(s, int) and 0 <= s < (1 << 63) for s in seeds)             # the drawn base seed, also for one start
     assert all((b - seeds[0]) % (1 << 63) == k for k, b in enumerate(seeds))
+    assert (params, err) == o.start_results[aopt.best_start([e for _, _, e in o.start_results])][1:]
 
 
 def _single_process_starts(seed, starts):
@@ -180,7 +186,7 @@ def test_host_multi_start_over_gloo(tmp_path, world):
     from tests.test_dist_gloo import _free_port
     port = _free_port()
     outs = [str(tmp_path / f"s{r}.npz") for r in range(world)]
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_dist_cma_starts_worker.py"), str(r), str(world), port, outs[r]],
+    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_dist_cma_worker.py"), str(r), str(world), port, outs[r], "starts"],
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(world)]
     for p in procs:
         out, _ = p.communicate(timeout=900)

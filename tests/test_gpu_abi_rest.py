@@ -1,6 +1,7 @@
 """The entry points of the C ABI that no other GPU test calls (found with ALP_ABI_COVERAGE, tests/conftest.py): the
 synchronous render, the (index, xyz) fetch of the visible pixels, the interleaved stand-alone loss, the handle's count, the
-timing / event helpers the benchmark uses, device count, and shutdown + re-initialisation (in a process of its own)."""
+timing / event helpers the benchmark uses, device count, shutdown + re-initialisation (in a process of its own), and the K = 1
+forms of the CMA-ES device loop's create / set-state / get-state."""
 import ctypes
 import os
 import subprocess
@@ -63,6 +64,58 @@ def test_interleaved_loss_entry_equals_the_column_entry(L):
         u, v, pu, pv = (np.ascontiguousarray(c) for c in (obs[:, 0], obs[:, 1], prj[:, 0], prj[:, 1]))
         L.check(L.lib().alp_loss_uv_columns(L.as_dp(u), L.as_dp(v), L.as_dp(pu), L.as_dp(pv), len(obs), kind, fs, ctypes.byref(b)))
         assert a.value == b.value and a.value == pytest.approx(ref, rel=1e-13)
+
+
+def test_single_start_cma_entry_points_are_the_k1_forms(L):
+    """alp_cma_create / _set_state / _get_state against alp_cma_create_starts / _set_state_at / _get_state_at (k = 0, through
+    CmaDevice) on the same points, seed and state: two generations leave bit-identical states"""
+    from alproj_amd import synthetic as syn
+    from alproj_amd.cma import CMA
+    truth = syn.truth_params(316)
+    xyz = syn.gcp_points(700, truth, seed=4)
+    uv = orc.project_points(xyz, truth) + np.random.default_rng(4).normal(0, 1.0, (700, 2))
+    targets, D, P, seed = syn.TARGETS_D9, 9, 50, 23
+    b = orc.bounds_to_array(truth, targets)
+    lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+    idx = np.array([L.PARAM_KEYS.index(t) for t in targets], dtype=np.int32)
+    cma = CMA(mean=np.full(D, 0.5), sigma=1.0, bounds=np.column_stack([np.zeros(D), np.ones(D)]), population_size=P,
+              n_max_resampling=100, seed=seed, sampler=L.cma_sample)
+    rng = np.random.default_rng(5)
+    q, _ = np.linalg.qr(rng.normal(size=(D, D)))
+    C = (q * rng.uniform(0.05, 0.5, D)) @ q.T
+    st = {"mean": rng.uniform(0.3, 0.7, D), "sigma": 0.2, "C": (C + C.T) / 2, "p_sigma": rng.normal(0, 0.5, D),
+          "pc": rng.normal(0, 0.2, D), "g": 3}
+    with L.Points(xyz, [truth["x"], truth["y"], truth["z"]], "f64") as pts:
+        pts.set_observed(uv)
+        lib = L.lib()
+        w = np.ascontiguousarray(cma._weights, dtype=np.float64)
+        hyper = np.array([cma._mu, cma._mu_eff, cma._c1, cma._cmu, cma._cc, cma._c_sigma, cma._d_sigma, cma._chi_n, cma._cm,
+                          np.sum(cma._weights)], dtype=np.float64)
+        h = ctypes.c_void_p()
+        L.check(lib.alp_cma_create(pts._h, L.as_dp(L.params_vector(truth)), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), D,
+                                   L.as_dp(lo), L.as_dp(hi), P, L.as_dp(w), L.as_dp(hyper), 100, ctypes.c_uint64(seed), ctypes.byref(h)))
+        try:
+            L.check(lib.alp_cma_set_state(h, L.as_dp(st["mean"]), st["sigma"], L.as_dp(st["C"]), L.as_dp(st["p_sigma"]),
+                                          L.as_dp(st["pc"]), st["g"]))
+            L.check(lib.alp_cma_run(h, 2, L.LOSS_HUBER, 10.0))
+            L.check(lib.alp_cma_wait(h))
+            one = {k: np.empty(D) for k in ("mean", "p_sigma", "pc", "D")}
+            one.update(C=np.empty((D, D)), B=np.empty((D, D)))
+            sigma, g = ctypes.c_double(), ctypes.c_int64()
+            L.check(lib.alp_cma_get_state(h, L.as_dp(one["mean"]), ctypes.byref(sigma), L.as_dp(one["C"]), L.as_dp(one["p_sigma"]),
+                                          L.as_dp(one["pc"]), ctypes.byref(g), L.as_dp(one["B"]), L.as_dp(one["D"])))
+            one.update(sigma=sigma.value, g=g.value)
+        finally:
+            lib.alp_cma_destroy(h)
+        with L.CmaDevice(pts, L.params_vector(truth), idx, lo, hi, cma) as loop:
+            assert loop.K == 1
+            loop.set_state(st)
+            loop.run(2, L.LOSS_HUBER, 10.0)
+            loop.wait()
+            starts = loop.get_state(eigen=True)
+    assert one["g"] == starts["g"] == 5 and one["sigma"] == starts["sigma"]
+    for key in ("mean", "C", "p_sigma", "pc", "B", "D"):
+        np.testing.assert_array_equal(one[key], starts[key], err_msg=key)
 
 
 def test_synchronous_render_and_the_visible_pixel_list(L):

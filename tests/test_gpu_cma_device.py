@@ -1,5 +1,6 @@
 """The device loop of the CMA-ES generation (alp_cma_*, CMAOptimizer.optimize(..., device_loop=True)): the tell against
-cma.py's, generation 0 against the host path, end-to-end convergence on the synthetic GCP problem, and the refusals."""
+cma.py's, generation 0 against the host path, end-to-end convergence on the synthetic GCP problem with one start and with
+several, and the refusals."""
 import numpy as np
 import pandas as pd
 import pytest
@@ -167,20 +168,19 @@ def test_generations_match_the_host_path(problem, variant, targets, precision, l
                 np.testing.assert_allclose(losses, want, rtol=tol, atol=0)
 
 
-def _two_phases(obj, img, init, seed, **kw):
+@pytest.mark.parametrize("seed,starts", [(1, 1), (2, 1), (3, 1), (1, 8)])
+def test_two_phases_converge(problem, seed, starts):
+    obj, img, init = problem
+    kw = dict(generation=300, sigma=1.0, population_size=50, f_scale=10.0, seed=seed, progress=False, device_loop=True, starts=starts)
     o1 = CMAOptimizer(obj, img, init)
     o1.set_target(list(syn.TARGETS_D9))
-    p1, e1 = o1.optimize(generation=300, sigma=1.0, population_size=50, f_scale=10.0, seed=seed, progress=False, device_loop=True, **kw)
+    p1, e1 = o1.optimize(**kw)
+    assert len(o1.start_results) == starts
     o2 = CMAOptimizer(obj, img, p1)
     o2.set_target(list(TARGETS_D12))
-    p2, e2 = o2.optimize(generation=300, sigma=1.0, population_size=50, f_scale=10.0, seed=seed, progress=False, device_loop=True, **kw)
-    return p1, e1, p2, e2
-
-
-@pytest.mark.parametrize("seed", [1, 2, 3])
-def test_two_phases_converge(problem, seed):
-    p1, e1, p2, e2 = _two_phases(*problem, seed)
+    p2, e2 = o2.optimize(**kw)
     assert e2 <= 1.30, (e1, e2)
+    assert e2 == min(e for _, _, e in o2.start_results)
 
 
 def test_same_seed_same_result(problem):
@@ -192,22 +192,26 @@ def test_same_seed_same_result(problem):
     assert a == b
 
 
-def test_float32_million_points_converges():
+@pytest.mark.parametrize("starts", [1, 4])
+def test_float32_million_points_converges(starts):
     L.init(0)
     obj, img, init = _gcp_problem(n=1_000_000)
     o = CMAOptimizer(obj, img, init)
     o.set_target(list(syn.TARGETS_D9))
     _, err = o.optimize(generation=300, sigma=1.0, population_size=50, f_scale=10.0, seed=1, precision="f32", progress=False,
-                        device_loop=True)
+                        device_loop=True, starts=starts)
     assert err <= 1.30, err
+    assert len(o.start_results) == starts
 
 
-def test_world1_communicator_changes_nothing(problem):
+@pytest.mark.parametrize("starts", [1, 4])
+def test_world1_communicator_changes_nothing(problem, starts):
     obj, img, init = problem
     o = CMAOptimizer(obj, img, init)
     o.set_target(list(syn.TARGETS_D9))
-    kw = dict(generation=100, sigma=1.0, population_size=50, f_scale=10.0, seed=1, progress=False, device_loop=True)
+    kw = dict(generation=100, sigma=1.0, population_size=50, f_scale=10.0, seed=1, progress=False, device_loop=True, starts=starts)
     alone = o.optimize(**kw)
+    alone_starts = list(o.start_results)
     L.comm_init(L.comm_unique_id(), 0, 1)
     try:
         assert L.comm_info() == (0, 1)
@@ -215,6 +219,7 @@ def test_world1_communicator_changes_nothing(problem):
     finally:
         L.comm_destroy()
     assert alone == with_comm
+    assert alone_starts == o.start_results
 
 
 def test_refusals(problem, small_points):

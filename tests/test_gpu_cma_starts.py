@@ -1,15 +1,13 @@
 """Multi-start CMA-ES (alp_cma_create_starts / _set_state_at / _get_state_at, CMAOptimizer.optimize(..., starts=K)): one batched
 generation of K starts against K single-start handles, the K-workgroup tell against cma.py, K starts end to end against K
-single runs, convergence, the world-1 communicator and the handle's refusals."""
+single runs and the handle's refusals (convergence and the world-1 communicator with several starts: tests/test_gpu_cma_device.py)."""
 import numpy as np
 import pytest
 
 from alproj_amd import _lib as L
 from alproj_amd import synthetic as syn
-from alproj_amd.cma import CMA
 from alproj_amd.optimize import CMAOptimizer, best_start, bounds_to_array
-from tests.test_gpu_cma_device import (ALLOWED, TARGETS_D12, VARIANT_CASES, _close, _gcp_problem, _h_margin, _host_cma, _loop,
-                                       _random_state)
+from tests.test_gpu_cma_device import ALLOWED, VARIANT_CASES, _close, _gcp_problem, _h_margin, _host_cma, _random_state
 
 pytestmark = pytest.mark.gpu
 
@@ -170,48 +168,6 @@ def test_starts_are_single_runs(problem, device_loop):
         assert abs(multi[k][2] - e1) <= 1e-12 * e1, (k, multi[k][2], e1)
     b = best_start([e for _, _, e in multi])
     assert (params, err) == (multi[b][1], multi[b][2])
-
-
-def test_two_phases_converge_with_starts(problem):
-    obj, img, init = problem
-    kw = dict(generation=300, sigma=1.0, population_size=50, f_scale=10.0, seed=1, progress=False, device_loop=True, starts=8)
-    o1 = CMAOptimizer(obj, img, init)
-    o1.set_target(list(syn.TARGETS_D9))
-    p1, e1 = o1.optimize(**kw)
-    assert len(o1.start_results) == 8
-    o2 = CMAOptimizer(obj, img, p1)
-    o2.set_target(list(TARGETS_D12))
-    p2, e2 = o2.optimize(**kw)
-    assert e2 <= 1.30, (e1, e2)
-    assert e2 == min(e for _, _, e in o2.start_results)
-
-
-def test_float32_million_points_converges_with_starts():
-    L.init(0)
-    obj, img, init = _gcp_problem(n=1_000_000)
-    o = CMAOptimizer(obj, img, init)
-    o.set_target(list(syn.TARGETS_D9))
-    _, err = o.optimize(generation=300, sigma=1.0, population_size=50, f_scale=10.0, seed=1, precision="f32", progress=False,
-                        device_loop=True, starts=4)
-    assert err <= 1.30, err
-    assert len(o.start_results) == 4
-
-
-def test_world1_communicator_changes_nothing_with_starts(problem):
-    obj, img, init = problem
-    o = CMAOptimizer(obj, img, init)
-    o.set_target(list(syn.TARGETS_D9))
-    kw = dict(generation=100, sigma=1.0, population_size=50, f_scale=10.0, seed=1, progress=False, device_loop=True, starts=4)
-    alone = o.optimize(**kw)
-    alone_starts = list(o.start_results)
-    L.comm_init(L.comm_unique_id(), 0, 1)
-    try:
-        assert L.comm_info() == (0, 1)
-        with_comm = o.optimize(**kw)
-    finally:
-        L.comm_destroy()
-    assert alone == with_comm
-    assert alone_starts == o.start_results
 
 
 def test_multi_start_handle_refusals(problem):
