@@ -192,6 +192,7 @@ _SIGNATURES = {
     "alp_points_create_columns": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_i64, _c_dp, _c_int, ctypes.POINTER(_c_void_p)],
     "alp_points_destroy": [_c_void_p],
     "alp_points_count": [_c_void_p, ctypes.POINTER(_c_i64)],
+    "alp_points_layout": [_c_void_p, ctypes.POINTER(_c_i64)],
     "alp_points_set_observed": [_c_void_p, _c_void_p, _c_int],
     "alp_points_set_observed_columns": [_c_void_p, _c_void_p, _c_void_p, _c_int],
     "alp_project": [_c_void_p, _c_dp],
@@ -438,6 +439,13 @@ class Points:
 
     def __exit__(self, *exc):
         self.close()
+
+    def row_length(self):
+        """W > 0 when the set was recognised as a raster of rows of W points (the projection streams z alone), 0 for the
+        plane path: alp_points_layout"""
+        w = _c_i64()
+        check(self._lib.alp_points_layout(self._h, ctypes.byref(w)))
+        return int(w.value)
 
     def set_observed(self, uv):
         """uv: (N, 2), row-major or with contiguous columns (uploaded column by column then)"""

@@ -29,6 +29,11 @@ template <> struct Num<float> {
         const native4 t = __builtin_nontemporal_load(reinterpret_cast<const native4 *>(p));
         return make_float4(t.x, t.y, t.z, t.w);
     }
+    // a cached (default-policy) 16-byte load: K1's grid form reads its column table with it
+    static __device__ __forceinline__ float4 load(const float4 *p) {
+        const native4 t = *reinterpret_cast<const native4 *>(p);
+        return make_float4(t.x, t.y, t.z, t.w);
+    }
     static __device__ __forceinline__ void nt_store(const float4 &a, float4 *p) {
         const native4 t = {a.x, a.y, a.z, a.w};
         __builtin_nontemporal_store(t, reinterpret_cast<native4 *>(p));
@@ -88,6 +93,10 @@ template <> struct Num<double> {
     typedef double native2 __attribute__((ext_vector_type(2)));
     static __device__ __forceinline__ double2 nt_load(const double2 *p) {
         const native2 t = __builtin_nontemporal_load(reinterpret_cast<const native2 *>(p));
+        return make_double2(t.x, t.y);
+    }
+    static __device__ __forceinline__ double2 load(const double2 *p) {
+        const native2 t = *reinterpret_cast<const native2 *>(p);
         return make_double2(t.x, t.y);
     }
     static __device__ __forceinline__ void nt_store(const double2 &a, double2 *p) {
@@ -182,6 +191,56 @@ __global__ __launch_bounds__(256) void project_kernel(const T *__restrict__ x, c
     }
     Num<T>::nt_store(ou, u4 + i);
     Num<T>::nt_store(ov, v4 + i);
+}
+
+// K1's grid form: the points are the rows of a raster laid out row-major, every row W points long (the last one may be
+// shorter), so x[i] = x[i % W] and y[i] = y[(i / W) * W] bit for bit (checked on the device at creation).  z streams in
+// non-temporally as above; x comes from the first W values of the x plane and y from one value per row, both with default
+// (cached) loads: at W <= 64 Ki the column table is at most 256 KB (float32) / 512 KB (float64) and stays in L2.
+// 4 + 8 = 12 B/vertex streamed (float), 24 (double).  Same launch shape, same arithmetic, same bits as the plane form.
+// Row and column come from a multiply by a host-computed magic number (RowDiv) rather than from a 2-D launch with one
+// row range per workgroup: the launch keeps one vector per lane over the flat index, whatever W is and wherever a row ends.
+// `last` = n - 1.  The elements of the last vector past n are padding that nothing reads (the fetches copy n values): the
+// per-element form clamps their indices to `last`, the aligned form reads them from e0's row; neither leaves the planes.
+template <typename T>
+__global__ __launch_bounds__(256) void project_kernel(const T *__restrict__ x, const T *__restrict__ y,
+                                                      const T *__restrict__ z, T *__restrict__ u,
+                                                      T *__restrict__ v, int64_t nvec, RowDiv rd, uint32_t last,
+                                                      PoseRec<T> pose) {
+    using Vt = typename Num<T>::vec;
+    constexpr int VEC = Num<T>::VEC;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nvec) return;
+    Vt qz = Num<T>::nt_load(reinterpret_cast<const Vt *>(z) + i);
+    const uint32_t e0 = (uint32_t)i * VEC;        // < n_pad <= 2^31
+    Vt qx, qy;
+    if (rd.w % VEC == 0) {
+        // the vector lies in one row, and its x values are one aligned vector of the column table
+        const uint32_t r = rd.div(e0);
+        const uint32_t c = e0 - r * rd.w;
+        qx = Num<T>::load(reinterpret_cast<const Vt *>(x + c));
+        const T yr = y[r * rd.w];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) vget<T>(qy, k) = yr;
+    } else {
+        // the vector may cross a row end (or, at W < VEC, several): row and column element by element
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const uint32_t e = e0 + k < last ? e0 + k : last;
+            const uint32_t r = rd.div(e);
+            vget<T>(qx, k) = x[e - r * rd.w];
+            vget<T>(qy, k) = y[r * rd.w];
+        }
+    }
+    Vt ou, ov;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        T xd, yd;
+        project_norm<T>(pose.v, vget<T>(qx, k), vget<T>(qy, k), vget<T>(qz, k), xd, yd);
+        to_pixels<T>(pose.v, xd, yd, vget<T>(ou, k), vget<T>(ov, k));
+    }
+    Num<T>::nt_store(ou, reinterpret_cast<Vt *>(u) + i);
+    Num<T>::nt_store(ov, reinterpret_cast<Vt *>(v) + i);
 }
 
 // ------------------------------------------------------------------ K3: residual vectors

@@ -127,14 +127,100 @@ int stream_grid(int64_t items) {
     return (int)(want < 1 ? 1 : (want < cap ? want : cap));
 }
 
+// ------------------------------------------------------------------ grid recognition (K1's grid form)
+// A DSM's vertex list is its raster flattened row-major (meshgrid(x, y)): x depends on the column alone and y on the row alone,
+// and since the planes are float(double(in) - origin) element by element, a column's x and a row's y have the same bits in
+// every point that shares them.  The check runs on the planes as uploaded, so it sees exactly what K1 reads:
+//   W = the first index i with bits(y[i]) != bits(y[0]);
+//   every i < n: bits(x[i]) == bits(x[i % W]) and bits(y[i]) == bits(y[(i / W) * W])  (a shorter last row is fine).
+// The plane path stays when: ALP_NO_POINTS_GRID is set; n < 2 or every y equals y[0] (a single row); W > GRID_MAX_ROW (the
+// column table would no longer stay in L2); n_pad > 2^31 (the kernel's row / column arithmetic is 32-bit: RowDiv).
+constexpr uint32_t GRID_MAX_ROW = 64 << 10;
+constexpr uint32_t GRID_NONE = 0xffffffffu;
+
+// bits: uint32_t (float planes) or uint64_t (double planes).  flags[0] (GRID_NONE beforehand) = the first index i < n whose y
+// differs from y[0]: a thread stops at its first such index, the wave takes the minimum, one atomic per wave.
+template <typename B>
+__global__ __launch_bounds__(256) void grid_row_length_kernel(const B *__restrict__ y, uint32_t n, uint32_t *flags) {
+    const B y0 = y[0];
+    uint32_t first = GRID_NONE;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        if (y[i] != y0) {
+            first = i;
+            break;
+        }
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)first, m);
+        first = o < first ? o : first;
+    }
+    if ((threadIdx.x & 63) == 0 && first != GRID_NONE) atomicMin(flags, first);
+}
+
+// flags[1] (0 beforehand) = 1 when some point is off the grid of row length rd.w
+template <typename B>
+__global__ __launch_bounds__(256) void grid_verify_kernel(const B *__restrict__ x, const B *__restrict__ y, uint32_t n, RowDiv rd,
+                                                          uint32_t *flags) {
+    bool ok = true;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t r = rd.div(i);
+        ok &= (x[i] == x[i - r * rd.w]) & (y[i] == y[r * rd.w]);
+    }
+    if (!ok) atomicOr(flags + 1, 1u);
+}
+
+RowDiv row_div(uint32_t w) {
+    RowDiv rd;
+    uint32_t l = 0;
+    while ((1u << l) < w) ++l;                    // ceil(log2 w)
+    rd.w = w;
+    rd.shift = 31 + l;
+    rd.mul = (uint32_t)((((uint64_t)1 << rd.shift) + w - 1) / w);
+    return rd;
+}
+
+template <typename B>
+int grid_detect_t(alp_points *p, uint32_t *flags, RowDiv *out) {
+    hipStream_t st = ctx().stream;
+    const uint32_t n = (uint32_t)p->n;
+    uint32_t h[2] = {GRID_NONE, 0};
+    ALP_HIP(hipMemcpyAsync(flags, h, sizeof(h), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(grid_row_length_kernel<B>, dim3(stream_grid(n)), dim3(256), 0, st, (const B *)p->y, n, flags);
+    ALP_HIP(hipGetLastError());
+    ALP_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st));
+    ALP_HIP(hipStreamSynchronize(st));
+    if (h[0] == GRID_NONE || h[0] > GRID_MAX_ROW) return ALP_OK;     // a single row, or too wide
+    const RowDiv rd = row_div(h[0]);
+    hipLaunchKernelGGL(grid_verify_kernel<B>, dim3(stream_grid(n)), dim3(256), 0, st, (const B *)p->x, (const B *)p->y, n, rd, flags);
+    ALP_HIP(hipGetLastError());
+    ALP_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st));
+    ALP_HIP(hipStreamSynchronize(st));
+    if (h[1] == 0) *out = rd;
+    return ALP_OK;
+}
+
+// p->rd = the grid of the uploaded planes, or w = 0 (the plane path)
+int points_grid_detect(alp_points *p) {
+    p->rd = RowDiv();
+    if (getenv("ALP_NO_POINTS_GRID") || p->n < 2 || p->n_pad > ((int64_t)1 << 31)) return ALP_OK;
+    uint32_t *flags = nullptr;
+    if (int rc = scratch_reserve(2 * sizeof(uint32_t), (void **)&flags)) return rc;
+    return p->precision == ALP_F64 ? grid_detect_t<uint64_t>(p, flags, &p->rd) : grid_detect_t<uint32_t>(p, flags, &p->rd);
+}
+
 template <typename T>
 int launch_project(alp_points *p, const double params[ALP_NPARAM]) {
     PoseRec<T> pose;
     fold_pose_t<T>(params, p->origin, &pose);
     const int64_t nvec = (p->n + Num<T>::VEC - 1) / Num<T>::VEC;
     const unsigned grid = (unsigned)((nvec + 255) / 256);        // one 16-byte vector per lane
-    hipLaunchKernelGGL((project_kernel<T>), dim3(grid), dim3(256), 0, ctx().stream,
-                       (const T *)p->x, (const T *)p->y, (const T *)p->z, (T *)p->u, (T *)p->v, nvec, pose);
+    if (p->rd.w)        // a grid: z alone streams in (points_grid_detect)
+        hipLaunchKernelGGL((project_kernel<T>), dim3(grid), dim3(256), 0, ctx().stream, (const T *)p->x, (const T *)p->y,
+                           (const T *)p->z, (T *)p->u, (T *)p->v, nvec, p->rd, (uint32_t)(p->n - 1), pose);
+    else
+        hipLaunchKernelGGL((project_kernel<T>), dim3(grid), dim3(256), 0, ctx().stream,
+                           (const T *)p->x, (const T *)p->y, (const T *)p->z, (T *)p->u, (T *)p->v, nvec, pose);
     ALP_HIP(hipGetLastError());
     return ALP_OK;
 }
@@ -525,6 +611,7 @@ static int points_create(const void *xyz, const void *const *cols, int in_dtype,
         hipError_t e = hipStreamSynchronize(ctx().stream);
         if (e != hipSuccess) rc = fail(ALP_EHIP, "points upload: %s", hipGetErrorString(e));
     }
+    if (!rc) rc = points_grid_detect(p);
     if (rc) {
         alp_points_destroy(p);
         return rc;
@@ -563,6 +650,12 @@ int alp_points_destroy(alp_points_t *p) {
 int alp_points_count(const alp_points_t *p, int64_t *n) {
     ALP_REQUIRE(p && n, "NULL argument");
     *n = p->n;
+    return ALP_OK;
+}
+
+int alp_points_layout(const alp_points_t *p, int64_t *row_length) {
+    ALP_REQUIRE(p && row_length, "NULL argument");
+    *row_length = p->rd.w;
     return ALP_OK;
 }
 

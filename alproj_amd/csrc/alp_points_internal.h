@@ -12,6 +12,9 @@ struct alp_points {
     int64_t n_pad = 0;
     int precision = ALP_F32;
     double origin[3] = {0, 0, 0};
+    // row length of a grid point set (rd.w > 0: the projection reads z alone and takes x, y from the first row / one value per
+    // row; alp_points.hip: points_grid_detect); rd.w = 0: the plane path
+    alp::RowDiv rd;
     // the planes live in at most three allocations (a hipMalloc / hipFree pair of this size costs ~1 ms: seven of them were a
     // third of what compute_residuals spent at 10 M points): coordinates at creation, observed pixels at alp_points_set_observed*,
     // projected pixels at the first alp_project

@@ -166,6 +166,11 @@ int alp_points_create_columns(const void *x, const void *y, const void *z, int i
                               const double origin[3], int precision, alp_points_t **out);
 int alp_points_destroy(alp_points_t *pts);
 int alp_points_count(const alp_points_t *pts, int64_t *n);
+/* Which form of the projection the set takes.  *row_length = W > 0: the points are a raster flattened row-major, rows of W
+ * points (the last one may be shorter; recognised on the device at creation, bit for bit), and alp_project streams the
+ * elevations alone (12 B/vertex in float32 instead of 20); 0: the x, y, z planes (a single row, a row longer than 65 536
+ * points, anything off the grid, or ALP_NO_POINTS_GRID set).  The projected pixels are the same bits either way. */
+int alp_points_layout(const alp_points_t *pts, int64_t *row_length);
 /* uv: n x 2 row-major host array of observed pixel coordinates (u, v). */
 int alp_points_set_observed(alp_points_t *pts, const void *uv, int in_dtype);
 /* ... or the two columns u[n], v[n] as they lie (img_points[["u", "v"]], optimize.py:173-174). */
