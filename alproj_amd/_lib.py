@@ -200,6 +200,7 @@ _SIGNATURES = {
     "alp_projected_fetch_strided": [_c_void_p, _c_i64, _c_i64, _c_i64, _c_dp, _c_dp],
     "alp_residuals": [_c_void_p, _c_dp, _c_dp],
     "alp_residuals_batch": [_c_void_p, _c_dp, _c_i64, _c_dp],
+    "alp_jacobian": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_int, _c_dp],
     "alp_eval_population": [_c_void_p, _c_dp, _c_i64, _c_int, _c_double, _c_dp, ctypes.POINTER(_c_i64)],
     "alp_eval_population_enqueue": [_c_void_p, _c_dp, _c_i64, _c_int, _c_double],
     "alp_eval_population_wait": [_c_void_p, _c_dp, ctypes.POINTER(_c_i64)],
@@ -497,6 +498,19 @@ class Points:
             raise ValueError("cand must have shape (B, 25)")
         out = result_empty((cand.shape[0], 2 * self.n), np.float64)
         check(self._lib.alp_residuals_batch(self._h, as_dp(cand), cand.shape[0], as_dp(out)))
+        return out
+
+    def jacobian(self, pvec, target_idx, of_residuals=True):
+        """(2N, D) float64 exact Jacobian at the parameter vector ``pvec`` (alp_jacobian): column j is the derivative with respect
+        to parameter ``target_idx[j]`` (an index into PARAM_KEYS; w and h are refused), rows in compute_residuals' order (u_0,
+        v_0, u_1, ...).  ``of_residuals``: of the residual vector observed - projected (the default), else of the projection."""
+        pvec = np.ascontiguousarray(pvec, dtype=np.float64)
+        if pvec.shape != (NPARAM,):
+            raise ValueError("pvec must have shape (25,)")
+        idx = np.ascontiguousarray(np.asarray(target_idx).reshape(-1), dtype=np.int32)
+        out = result_empty((2 * self.n, len(idx)), np.float64)
+        check(self._lib.alp_jacobian(self._h, as_dp(pvec), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx),
+                                     int(bool(of_residuals)), as_dp(out)))
         return out
 
     def eval_population(self, cand, loss_kind, f_scale=10.0, want_argmin=True):

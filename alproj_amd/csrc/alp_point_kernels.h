@@ -1,7 +1,7 @@
 // Device code of the point-set path (included by alp_points.hip and by the development
 // micro-benchmarks under tools/): element-type helpers, the projection arithmetic, and the
 // kernels K1 project_kernel, K2 popeval_kernel (+ reduce_partials_kernel), K3 residual_batch_kernel,
-// the stand-alone loss kernel and the upload helpers.
+// K3j jacobian_kernel, the stand-alone loss kernel and the upload helpers.
 //
 // Reference arithmetic: src/alproj/optimize.py  project :122-155, _distort :98-120,
 // rmse :157-178, huber_loss :181-212, compute_residuals :215-237, and the generation loop
@@ -584,6 +584,114 @@ __global__ __launch_bounds__(256) void residual_batch_kernel(const T *__restrict
                     Num<double>::nt_store(make_double2((double)(ou[j] - u), (double)(ov[j] - v)), out + ((int64_t)b * n + idx[j]));
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------ K3j: exact Jacobian of the projection
+// out[2i][j] = d u_i / d theta_j, out[2i + 1][j] = d v_i / d theta_j (row-major (2n, D), the row order of compute_residuals,
+// optimize.py:233-236), negated for the residual vector (plan->su, sv carry the sign).  Float64 arithmetic whatever the
+// planes hold (TS = float: widened on load).  The chain is project_norm / to_pixels above differentiated as written,
+// quirks Q1 (2 p1 x y on both axes, 2 p2 r2 x^2 / r2 y^2) and Q8 (a1, a2 on the y ratio alone) included:
+//   (xn, yn, zc) = rows 0..11 . [q; 1],  x1 = xn / zc,  d x1 = (d xn - x1 d zc) / zc  (y1 likewise)
+//   (xd, yd) = distortion(x1, y1; rec[12..25]):  its 2 x 2 partials in (x1, y1), and its partials in the one lens word a
+//   lens target moves,  d u = c0 d xd,  d v = c1 d yd.
+// A pose / intrinsic target j contracts plan->drow[j] (12 words) with [q; 1] three times; a lens target is one product.
+// The targets are wave-uniform (the plan lives in constant memory reached by scalar loads).  A point's 2D outputs are one
+// contiguous run of 16 D bytes, written as D 16-byte non-temporal stores: value k of the run is target k mod D, of u
+// (k < D) or v (k >= D).  Non-finite values (a point on the camera plane, a lens pole) propagate as they do in K3.
+struct JacPoint {
+    double qx, qy, qz, x1, y1, iz;
+    double au, bu, cu, av, bv, cv;        // d u = au d xn + bu d yn + cu d zc; v likewise
+    double xx, yy, xy, r2, r4, r6, gx, gy, idx, idy;
+};
+
+__device__ __forceinline__ void jac_point(const JacPlan *__restrict__ plan, double qx, double qy, double qz, JacPoint &P) {
+    using N = Num<double>;
+    const double *r = plan->rec;
+    P.qx = qx; P.qy = qy; P.qz = qz;
+    const double zc = N::fma(r[8], qx, N::fma(r[9], qy, N::fma(r[10], qz, r[11])));
+    const double xn = N::fma(r[0], qx, N::fma(r[1], qy, N::fma(r[2], qz, r[3])));
+    const double yn = N::fma(r[4], qx, N::fma(r[5], qy, N::fma(r[6], qz, r[7])));
+    const double iz = N::rcp(zc);
+    const double x1 = xn * iz, y1 = yn * iz;
+    const double xx = x1 * x1, yy = y1 * y1;
+    const double rr = N::sqrt(xx + yy);
+    const double r2 = rr * rr, r4 = r2 * r2;
+    const double tn = N::fma(N::fma(r[14], r2, r[13]), r2, r[12]);   // k1 + k2 r2 + k3 r4
+    const double td = N::fma(N::fma(r[17], r2, r[16]), r2, r[15]);   // k4 + k5 r2 + k6 r4
+    const double idx = N::rcp(N::fma(td, r2, 1.0));                  // 1 / (1 + td r2)
+    const double idy = N::rcp(N::fma(td, r2, r[19]));                // 1 / (1 + a2 + td r2)
+    const double gx = N::fma(tn, r2, 1.0) * idx;
+    const double gy = N::fma(tn, r2, r[18]) * idy;
+    // d/d r2 of the numerator and the denominator polynomials (tn r2 and td r2), then of the two ratios
+    const double nn = N::fma(N::fma(2 * r[14], r2, r[13]), r2, tn);
+    const double nd = N::fma(N::fma(2 * r[17], r2, r[16]), r2, td);
+    const double gxr = (nn - gx * nd) * idx;
+    const double gyr = (nn - gy * nd) * idy;
+    // d xd / d r2 and d yd / d r2 at fixed (x1, y1)
+    const double axr = x1 * gxr + r[21] * xx + r[22] + 2 * r[23] * r2;
+    const double ayr = y1 * gyr + r[21] * yy + r[24] + 2 * r[25] * r2;
+    // the distortion's 2 x 2 partials in (x1, y1)   (d r2 = 2 x1 d x1 + 2 y1 d y1)
+    const double jxx = gx + r[20] * y1 + 2 * r[21] * r2 * x1 + 2 * x1 * axr;
+    const double jxy = r[20] * x1 + 2 * y1 * axr;
+    const double jyx = r[20] * y1 + 2 * x1 * ayr;
+    const double jyy = gy + r[20] * x1 + 2 * r[21] * r2 * y1 + 2 * y1 * ayr;
+    // d x1 = (d xn - x1 d zc) iz,  d y1 = (d yn - y1 d zc) iz
+    const double su = plan->su * iz, sv = plan->sv * iz;
+    P.au = su * jxx; P.bu = su * jxy; P.cu = -(P.au * x1 + P.bu * y1);
+    P.av = sv * jyx; P.bv = sv * jyy; P.cv = -(P.av * x1 + P.bv * y1);
+    P.x1 = x1; P.y1 = y1; P.iz = iz;
+    P.xx = xx; P.yy = yy; P.xy = x1 * y1; P.r2 = r2; P.r4 = r4; P.r6 = r4 * r2;
+    P.gx = gx; P.gy = gy; P.idx = idx; P.idy = idy;
+}
+
+// value k (0 <= k < 2D) of a point's output run
+__device__ __forceinline__ double jac_value(const JacPlan *__restrict__ plan, const JacPoint &P, int k) {
+    using N = Num<double>;
+    const int D = plan->D;
+    const bool is_v = k >= D;
+    const int j = is_v ? k - D : k;
+    const int w = plan->lens_w[j];
+    if (w < 0) {
+        const double *d = plan->drow[j];
+        const double dx = N::fma(d[0], P.qx, N::fma(d[1], P.qy, N::fma(d[2], P.qz, d[3])));
+        const double dy = N::fma(d[4], P.qx, N::fma(d[5], P.qy, N::fma(d[6], P.qz, d[7])));
+        const double dz = N::fma(d[8], P.qx, N::fma(d[9], P.qy, N::fma(d[10], P.qz, d[11])));
+        return is_v ? N::fma(P.av, dx, N::fma(P.bv, dy, P.cv * dz)) : N::fma(P.au, dx, N::fma(P.bu, dy, P.cu * dz));
+    }
+    // d xd / d word, d yd / d word  (word = rec[12 + w])
+    double lx = 0, ly = 0;
+    switch (w) {
+        case 0: lx = P.x1 * P.r2 * P.idx; ly = P.y1 * P.r2 * P.idy; break;                  // k1
+        case 1: lx = P.x1 * P.r4 * P.idx; ly = P.y1 * P.r4 * P.idy; break;                  // k2
+        case 2: lx = P.x1 * P.r6 * P.idx; ly = P.y1 * P.r6 * P.idy; break;                  // k3
+        case 3: lx = -P.x1 * P.gx * P.r2 * P.idx; ly = -P.y1 * P.gy * P.r2 * P.idy; break;  // k4
+        case 4: lx = -P.x1 * P.gx * P.r4 * P.idx; ly = -P.y1 * P.gy * P.r4 * P.idy; break;  // k5
+        case 5: lx = -P.x1 * P.gx * P.r6 * P.idx; ly = -P.y1 * P.gy * P.r6 * P.idy; break;  // k6
+        case 6: ly = P.y1 * P.idy; break;                                                   // 1 + a1
+        case 7: ly = -P.y1 * P.gy * P.idy; break;                                           // 1 + a2
+        case 8: lx = P.xy; ly = P.xy; break;                                                // 2 p1
+        case 9: lx = P.r2 * P.xx; ly = P.r2 * P.yy; break;                                  // 2 p2
+        case 10: lx = P.r2; break;                                                          // s1
+        case 11: lx = P.r4; break;                                                          // s2
+        case 12: ly = P.r2; break;                                                          // s3
+        default: ly = P.r4; break;                                                          // s4
+    }
+    return is_v ? (plan->sv * plan->lens_f[j]) * ly : (plan->su * plan->lens_f[j]) * lx;
+}
+
+template <typename TS>
+__global__ __launch_bounds__(256) void jacobian_kernel(const TS *__restrict__ x, const TS *__restrict__ y,
+                                                       const TS *__restrict__ z, double2 *__restrict__ out, int64_t n,
+                                                       const JacPlan *__restrict__ plan) {
+    const int D = plan->D;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        JacPoint P;
+        jac_point(plan, (double)x[i], (double)y[i], (double)z[i], P);
+        double2 *o = out + i * D;                 // 2D doubles = D double2 per point
+        for (int m = 0; m < D; ++m)
+            Num<double>::nt_store(make_double2(jac_value(plan, P, 2 * m), jac_value(plan, P, 2 * m + 1)), o + m);
     }
 }
 

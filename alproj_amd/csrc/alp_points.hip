@@ -3,6 +3,7 @@
 //   popeval_kernel   P candidate poses x every point -> per-candidate loss sums
 //                    (VALU-bound; candidates staged in LDS, wave64 DPP reductions)
 //   residual_batch_kernel  observed - projected for B poses, interleaved (least-squares path)
+//   jacobian_kernel  d projected / d parameters for one pose, exact (least-squares path)
 //
 // Reference arithmetic: src/alproj/optimize.py  project :122-155, _distort :98-120,
 // rmse :157-178, huber_loss :181-212, compute_residuals :215-237, and the generation loop
@@ -486,6 +487,35 @@ int residuals_impl(alp_points *p, const double *cand, int64_t B, double *out) {
     return ALP_OK;
 }
 
+// alp_jacobian: chunks of whole points (a chunk's rows are one contiguous block of the output: one copy each), at most
+// RES_CHUNK_BYTES of output per launch as for the residuals
+template <typename TS>
+int jacobian_impl(alp_points *p, const JacPlan &plan, double *out) {
+    const int64_t D = plan.D;
+    const size_t plan_bytes = round_up((int64_t)sizeof(JacPlan), 256);
+    int64_t chunk = (int64_t)(RES_CHUNK_BYTES / ((size_t)D * sizeof(double2)));
+    chunk = chunk / 1024 * 1024;
+    if (chunk < 1024) chunk = 1024;
+    if (chunk > p->n) chunk = p->n;
+    char *dev = nullptr;
+    if (int rc = scratch_reserve(plan_bytes + (size_t)chunk * D * sizeof(double2), (void **)&dev)) return rc;
+    JacPlan *plan_dev = (JacPlan *)dev;
+    double2 *jac_dev = (double2 *)(dev + plan_bytes);
+    hipStream_t st = ctx().stream;
+    ALP_HIP(hipMemcpyAsync(plan_dev, &plan, sizeof(JacPlan), hipMemcpyHostToDevice, st));
+    for (int64_t off = 0; off < p->n; off += chunk) {
+        const int64_t cnt = p->n - off < chunk ? p->n - off : chunk;
+        ktime_begin();
+        hipLaunchKernelGGL(jacobian_kernel<TS>, dim3(stream_grid(cnt)), dim3(256), 0, st, (const TS *)p->x + off,
+                           (const TS *)p->y + off, (const TS *)p->z + off, jac_dev, cnt, (const JacPlan *)plan_dev);
+        ktime_end();
+        ALP_HIP(hipGetLastError());
+        ALP_HIP(hipMemcpyAsync(out + 2 * D * off, jac_dev, (size_t)cnt * D * sizeof(double2), hipMemcpyDeviceToHost, st));
+        ALP_HIP(hipStreamSynchronize(st));       // the staging buffer is reused; the plan must outlive its copy
+    }
+    return ALP_OK;
+}
+
 }  // namespace
 
 namespace alp {
@@ -764,6 +794,17 @@ int alp_residuals_batch(alp_points_t *p, const double *cand, int64_t B, double *
     if (p->n == 0) return ALP_OK;
     ALP_REQUIRE(out, "out is NULL");
     return p->precision == ALP_F64 ? residuals_impl<double>(p, cand, B, out) : residuals_impl<float>(p, cand, B, out);
+}
+
+int alp_jacobian(alp_points_t *p, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int of_residuals,
+                 double *out) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p && params, "NULL argument");
+    JacPlan plan;
+    if (int rc = jacobian_plan(params, p->origin, target_idx, D, of_residuals, &plan)) return rc;
+    if (p->n == 0) return ALP_OK;
+    ALP_REQUIRE(out, "out is NULL");
+    return p->precision == ALP_F64 ? jacobian_impl<double>(p, plan, out) : jacobian_impl<float>(p, plan, out);
 }
 
 // obs_b / prj_b NULL: that array is interleaved (n x 2 row-major); else a = the u column, b = the v column

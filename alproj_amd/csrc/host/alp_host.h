@@ -90,6 +90,31 @@ inline void fold_pose_t(const double params[ALP_NPARAM], const double origin[3],
     for (int i = 0; i < POSE_WORDS; ++i) out->v[i] = (T)r[i];
 }
 
+// ------------------------------------------------------------------ derivative of the fold (alp_jacobian)
+// Targets: any of the 25 ABI parameters but w and h (indices 21, 22), which enter c0 / c1 through a float32 rounding.
+// Only rec[0..25] depend on them (rec[26..31] are c0, c1 and constants).
+constexpr int JAC_MAX = ALP_NPARAM - 2;
+constexpr int JAC_WORDS = 26;
+// ALP_OK when 1 <= D <= JAC_MAX and target[0..D) are distinct parameter indices other than w and h; else ALP_EINVAL
+int jacobian_targets_check(const int32_t *target, int D);
+// jac[m * D + j] = d rec[m] / d params[target[j]] for m < JAC_WORDS: fold_pose_any run on a forward-mode dual number, so
+// the derivative is of the very arithmetic fold_pose does
+int fold_pose_jacobian(const double params[ALP_NPARAM], const double origin[3], const int32_t *target, int D, double *jac);
+
+// What jacobian_kernel reads (one copy, wave-uniform).  A pose or intrinsic target (x .. roll, cx, cy) moves rows 0..11 of the
+// record alone: drow[j] holds their derivative.  A lens target moves ONE lens word by a constant factor (k1 -> rec[12] by 1,
+// p1 -> rec[20] by 2, ...): lens_w[j] = that word - 12, lens_f[j] = the factor, read off the fold's own derivative table.
+struct alignas(16) JacPlan {
+    double rec[POSE_WORDS];       // fold_pose of the parameters
+    double drow[JAC_MAX][12];
+    double lens_f[JAC_MAX];
+    double su, sv;                // c0, c1, negated for the Jacobian of the residual vector (observed - projected)
+    int32_t lens_w[JAC_MAX];      // -1: pose / intrinsic target
+    int32_t D;
+};
+int jacobian_plan(const double params[ALP_NPARAM], const double origin[3], const int32_t *target, int D, int of_residuals,
+                  JacPlan *plan);
+
 namespace host {
 
 // ------------------------------------------------------------------ threaded array helpers (alp_host_* entry points)

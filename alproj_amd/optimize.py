@@ -12,6 +12,7 @@ here                          reference                                device en
 ``bounds_to_array``           optimize.py:249-276                      (host, D <= 21 scalars)
 ``CMAOptimizer.optimize``     optimize.py:359-439                      alp_eval_population, alp_cma_*
 ``LsqOptimizer.optimize``     optimize.py:467-539                      alp_residuals
+``parameter_covariance``      (none: standard errors of a fit)         alp_jacobian, alp_residuals
 ``intrinsic_mat`` etc.        optimize.py:8-96                         (host, 3x3 / 4x4)
 ============================  =======================================  ======================
 
@@ -21,7 +22,7 @@ Extra keyword arguments (all optional, defaults keep the reference behaviour):
 point set of up to ``F64_MAX_POINTS`` = 4 M points (any GCP-scale use of the reference: float64
 costs nothing there) and float32 (20 B/vertex, ~1e-3 px) for DSM-sized sets above it;
 ``seed`` makes the CMA-ES trajectory reproducible; ``starts=K`` runs K seeded CMA-ES starts side by side and keeps the
-best (``CMAOptimizer.optimize``).  There is no CPU fallback: without the
+best (``CMAOptimizer.optimize``); ``jac="analytic"`` gives ``LsqOptimizer.optimize`` the exact Jacobian (alp_jacobian).  There is no CPU fallback: without the
 HIP library / a GPU every function that touches points raises ``AlprojHipError``.
 """
 from contextlib import nullcontext
@@ -213,6 +214,57 @@ def compute_residuals(obj_points, img_points, params):
     with _points(xyz, _camera_origin(params), "f64") as pts:
         _set_observed(pts, _uv_array(img_points))
         return pts.residuals(_lib.params_vector(params))
+
+
+def _jacobian_targets(target_params):
+    """PARAM_KEYS indices of the targets of an exact Jacobian (alp_jacobian); ValueError, before any GPU call, for w / h,
+    an unknown key or a repeated one"""
+    targets = list(target_params)
+    for t in targets:
+        if t in ("w", "h"):
+            raise ValueError(f"{t!r} cannot be a target of the exact Jacobian (w and h are image sizes, not fitted)")
+        if t not in _lib.PARAM_KEYS:
+            raise ValueError(f"unknown parameter {t!r}")
+    if len(set(targets)) != len(targets):
+        raise ValueError("the targets of the exact Jacobian must be distinct")
+    if not 1 <= len(targets) <= _lib.NPARAM - 2:
+        raise ValueError("the exact Jacobian needs 1 to 23 targets")
+    return np.array([_lib.PARAM_KEYS.index(t) for t in targets], dtype=np.int32)
+
+
+def parameter_covariance(obj_points, img_points, params, target_params):
+    """Covariance and standard errors of the camera parameters ``target_params`` fitted to the GCPs, at ``params``:
+    ``cov`` = s^2 (J^T J)^-1 with s^2 = r^T r / (2N - D), J the exact (2N, D) Jacobian of the residual vector r (one
+    ``alp_jacobian`` and one ``alp_residuals`` call on a float64 point set), formed from the SVD of J.  Returns
+    ``(cov, std)`` with ``std = {target: sqrt(cov[j, j])}``.  When J is rank-deficient to working precision (a singular
+    value <= max(2N, D) eps sigma_max, numpy's matrix_rank rule) the targets cannot all be determined from these GCPs:
+    ``cov`` and ``std`` are inf.  With several ranks J and r are gathered first: every rank returns the same numbers.
+    ValueError for w / h or repeated targets, or for 2N <= D."""
+    targets = list(target_params)
+    cols = _jacobian_targets(targets)
+    xyz = _xyz_array(obj_points)
+    _, world = _lib.comm_info()
+    if world == 1 and 2 * _rows(xyz) <= len(targets):
+        raise ValueError(f"{_rows(xyz)} points give {2 * _rows(xyz)} residuals: not more than the {len(targets)} targets")
+    pvec = _lib.params_vector(params)
+    with _points(xyz, _camera_origin(params), "f64") as pts:
+        _set_observed(pts, _uv_array(img_points))
+        J = pts.jacobian(pvec, cols, of_residuals=True)
+        r = pts.residuals(pvec)
+    if world > 1:
+        J, r = _lib.comm_allgather(J), _lib.comm_allgather(r)
+    m, d = J.shape
+    if m <= d:
+        raise ValueError(f"{m} residuals: not more than the {d} targets")
+    if not (np.isfinite(J).all() and np.isfinite(r).all()):
+        raise ValueError("the residuals or their Jacobian are not finite at these parameters")
+    _, sv, vt = np.linalg.svd(J, full_matrices=False)
+    if sv[-1] <= max(m, d) * np.finfo(np.float64).eps * sv[0]:
+        cov = np.full((d, d), np.inf)
+    else:
+        s2 = float(r @ r) / (m - d)
+        cov = (vt.T / sv ** 2) @ vt * s2
+    return cov, {t: float(np.sqrt(cov[j, j])) for j, t in enumerate(targets)}
 
 
 # ------------------------------------------------------------------------------------------
@@ -440,7 +492,8 @@ class CMAOptimizer(BaseOptimizer):
 
 class LsqOptimizer(BaseOptimizer):
     """scipy.optimize.least_squares driver (reference optimize.py:442-539); the residual
-    vector of every trial point comes from ``alp_residuals`` on a float64 point set.
+    vector of every trial point comes from ``alp_residuals`` on a float64 point set, and with
+    ``jac="analytic"`` its exact Jacobian from ``alp_jacobian``.
 
     Several ranks (points sharded, one process per GPU): the reference solves ONE problem over all points
     (optimize.py:510-528), so every rank all-gathers the residual vector -- and the rows of the batched Jacobian -- of
@@ -487,7 +540,23 @@ class LsqOptimizer(BaseOptimizer):
 
         return _jac
 
+    def _analytic_jacobian_function(self, pts, cols):
+        """The exact Jacobian of the residual vector at ``values`` (alp_jacobian): one launch, no step, nothing to do at a
+        bound.  With several ranks the rows are all-gathered in rank order as in the batched path."""
+        _, world = _lib.comm_info()
+
+        def _jac(values, *args, **kw):
+            jac = pts.jacobian(self._candidate_matrix(values)[0], cols, of_residuals=True)
+            return _lib.comm_allgather(jac) if world > 1 else jac
+
+        return _jac
+
     def optimize(self, method="trf", bound_widths=None, loss="linear", f_scale=1.0, **kwargs):
+        """scipy.optimize.least_squares on the device residuals.  ``jac``: "batched" (the default for trf and dogbox: 2-point
+        differences, D + 1 trial points per launch), "analytic" (the exact Jacobian, alp_jacobian; targets w / h refused),
+        anything scipy accepts (for lm the default stays MINPACK's own differences)."""
+        analytic = kwargs.get("jac") == "analytic"
+        cols = _jacobian_targets(self.target_params) if analytic else None
         if method == "lm" and bound_widths is not None:
             raise ValueError("method='lm' does not support bounds. Set bound_widths=None or use 'trf'/'dogbox'.")
         if method == "lm" and loss != "linear":
@@ -500,11 +569,15 @@ class LsqOptimizer(BaseOptimizer):
                 # MINPACK's own forward differences unless the caller asks for the batched ones
                 if kwargs.get("jac") == "batched":
                     kwargs = dict(kwargs, jac=self._jacobian_function(pts))
+                elif analytic:
+                    kwargs = dict(kwargs, jac=self._analytic_jacobian_function(pts, cols))
                 result = least_squares(residual_func, self.target_params_init, method=method, **kwargs)
             else:
                 bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
                 if kwargs.get("jac", "batched") == "batched":
                     kwargs = dict(kwargs, jac=self._jacobian_function(pts, (bounds[:, 0], bounds[:, 1])))
+                elif analytic:
+                    kwargs = dict(kwargs, jac=self._analytic_jacobian_function(pts, cols))
                 result = least_squares(residual_func, self.target_params_init, method=method,
                                        bounds=(bounds[:, 0], bounds[:, 1]), loss=loss,
                                        f_scale=f_scale, **kwargs)

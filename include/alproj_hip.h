@@ -198,6 +198,15 @@ int alp_residuals(alp_points_t *pts, const double params[ALP_NPARAM], double *ou
  * row b = residual vector of pose b): the D+1 evaluations of a 2-point finite-difference
  * Jacobian for LsqOptimizer, src/alproj/optimize.py:461-463, :510-528. */
 int alp_residuals_batch(alp_points_t *pts, const double *cand, int64_t B, double *out);
+/* Exact Jacobian of the projection at one parameter vector, for LsqOptimizer's jac="analytic" and for the standard errors
+ * of fitted parameters: src/alproj/optimize.py:215-237 (the residual vector, its row order) and :442-539 (the least-squares
+ * solve it feeds).  target_idx: D distinct indices into the 25 parameters, w (21) and h (22) excluded, 1 <= D <= 23.
+ * out: (2n, D) row-major doubles, row 2i = d u_i / d params[target_idx[j]], row 2i + 1 = d v_i / ...; of_residuals != 0
+ * gives the Jacobian of observed - projected instead (its negation; no observed uv needed).  Float64 arithmetic on either
+ * set; the derivative of exactly the model alp_project evaluates (the reference's distortion, its quirks included).
+ * ALP_EINVAL for NULL, a bad D, a bad or repeated target.  n = 0: nothing happens. */
+int alp_jacobian(alp_points_t *pts, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int of_residuals,
+                 double *out);
 
 /* Population-wide reprojection error: replaces the inner loop of CMAOptimizer.optimize,
  * src/alproj/optimize.py:420-423, i.e. P calls of _proj_error (:347-356) = project +
