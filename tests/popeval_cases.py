@@ -41,6 +41,33 @@ def stripe_bounds(stripes, n=N):
     return out
 
 
+def mark_positions(stripes, V, n=N):
+    """points on the boundaries the grid creates: first and last point of every stripe, lanes 0 and 255 of the last row of every
+    V-group, the first and the last point of every 2-wide group, n - 256 and n - 1 (walked as pop_walk_stripe walks)"""
+    idx = {n - 1, n - 256}
+    for beg, end in stripe_bounds(stripes, n):
+        idx |= {beg, end - 1}
+        base = beg
+        while base + 256 * V <= end:
+            idx |= {base + 256 * (V - 1), base + 256 * V - 1}
+            base += 256 * V
+        while base + 512 <= end:
+            idx |= {base, base + 511}
+            base += 512
+    return sorted(idx)
+
+
+def mark_counts(total, n_marks, unit=1.0):
+    """how often each of n_marks marked points was counted in a mean-distance sum `total` (loss * n) whose marks are off by
+    unit * 4^k pixels and every other point by (almost) nothing: the base-4 digits of total / unit, or None when that is not
+    within 0.25 of an integer below 4^n_marks"""
+    q = total / unit
+    code = int(round(q))
+    if not (abs(q - code) < 0.25 and 0 <= code < 4 ** n_marks):
+        return None
+    return [(code >> (2 * k)) & 3 for k in range(n_marks)]
+
+
 def truth(variant):
     """the pose that produced the observations: a lens for the general and shared-pose variants, k = p = s = 0 (a1, a2 kept)
     for the lens-free one"""

@@ -73,8 +73,8 @@ def _close(a, b, tol, scale=None):
     assert np.max(np.abs(np.asarray(a) - np.asarray(b))) <= tol * s, (np.max(np.abs(np.asarray(a) - np.asarray(b))), s)
 
 
-@pytest.mark.parametrize("P", [4, 50, 141, 256, 2048])
-@pytest.mark.parametrize("D", [1, 2, 9, 12, 21, 25])
+@pytest.mark.parametrize("P", [4, 50, 141, 256, 2048, 4096])
+@pytest.mark.parametrize("D", [1, 2, 9, 12, 13, 21, 24, 25, 32])
 def test_tell_parity(small_points, D, P):
     for seed in range(10):                                          # the first state not within 1e-9 of the h_sigma threshold
         rng = np.random.default_rng(1000 * D + P + seed)

@@ -114,22 +114,6 @@ def test_oracle_parity_on_every_grid(L, cases, variant, prec, loss, monkeypatch)
 
 
 # ------------------------------------------------------------------ 2: every point counted once
-def mark_positions(stripes, V, n=pc.N):
-    """points on the boundaries the grid creates: first and last point of every stripe, lanes 0 and 255 of the last row of every
-    V-group, the first and the last point of every 2-wide group, n - 256 and n - 1 (walked as pop_walk_stripe walks)"""
-    idx = {n - 1, n - 256}
-    for beg, end in pc.stripe_bounds(stripes, n):
-        idx |= {beg, end - 1}
-        base = beg
-        while base + 256 * V <= end:
-            idx |= {base + 256 * (V - 1), base + 256 * V - 1}
-            base += 256 * V
-        while base + 512 <= end:
-            idx |= {base, base + 511}
-            base += 512
-    return sorted(idx)
-
-
 @pytest.mark.parametrize("prec", ["f64", "f32"])
 @pytest.mark.parametrize("variant", pc.VARIANTS)
 def test_every_point_counted_once_in_every_tile(L, cases, variant, prec, monkeypatch):
@@ -152,7 +136,7 @@ def test_every_point_counted_once_in_every_tile(L, cases, variant, prec, monkeyp
     with L.Points(xyz, cases["o"], prec) as pts:
         for gi, s in enumerate(GRIDS):
             cols = 1 + gi % 3
-            marks = mark_positions(s, V)
+            marks = pc.mark_positions(s, V)
             for k0 in range(0, len(marks), per_call):
                 chunk = marks[k0:k0 + per_call]
                 d = 4.0 ** np.arange(len(chunk)) if prec == "f64" else np.array([2.0 ** 14])
@@ -165,13 +149,10 @@ def test_every_point_counted_once_in_every_tile(L, cases, variant, prec, monkeyp
                 assert np.array_equal(bits(truth_l), bits(np.full(P, truth_l[0]))), (s, cols)   # identical candidates
                 total = truth_l[0] * n
                 if prec == "f64":
-                    code = int(round(total))
-                    assert abs(total - code) < 0.25, (s, cols, total)
-                    counts = [(code >> (2 * k)) & 3 for k in range(len(chunk))]
-                    assert code < 4 ** len(chunk) and counts == [1] * len(chunk), \
-                        (s, cols, [(i, c) for i, c in zip(chunk, counts) if c != 1], code)
+                    counts = pc.mark_counts(total, len(chunk))
+                    assert counts == [1] * len(chunk), (s, cols, chunk, counts, total)
                 else:
-                    assert round(total / d[0]) == 1, (s, cols, chunk, total / d[0])
+                    assert pc.mark_counts(total, 1, d[0]) == [1], (s, cols, chunk, total / d[0])
                 calls += 1
     assert calls > len(GRIDS)
 
