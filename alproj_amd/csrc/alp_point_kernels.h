@@ -389,7 +389,10 @@ __device__ __forceinline__ void norm_coords(const T *r, const T (&qx)[V], const 
         o.y1[j] *= zc[j];
         o.xx[j] = o.x1[j] * o.x1[j];
         o.yy[j] = o.y1[j] * o.y1[j];
-        o.r2[j] = o.xx[j] + o.yy[j];
+        // one fma in every slot j: written as xx + yy, the compiler contracted it into an fma in the slot it did not pack with
+        // another (v_pk_mul_f32) and kept two roundings in the packed ones, so a point's float32 pixels depended on its place in
+        // the launch (K3: a batch whose chunks start off a multiple of 768 points differed from the B = 1 call by an ulp)
+        o.r2[j] = N::fma(o.x1[j], o.x1[j], o.yy[j]);
         if constexpr (sizeof(T) == 8 && POP_F64_Q2) {            // Q2: the reference squares sqrt(x^2+y^2)
             const T rr = N::sqrt_pop(o.r2[j]);
             o.r2[j] = rr * rr;

@@ -8,6 +8,7 @@ import pandas as pd
 import pytest
 
 from oracle import ref_numpy as orc
+from tests import residual_cases as rc
 from tests.test_jacobian_oracle import KEYS, TARGETS, cs_jacobian, cs_project
 
 pytestmark = pytest.mark.gpu
@@ -146,16 +147,25 @@ def test_shapes(L, n):
 
 
 def test_ten_million_points_take_several_staging_chunks(L):
-    """10 M points at D = 21: 3.4 GB of output, 13 launches of at most 256 MB; compared on a strided sample of rows"""
+    """10 M points at D = 21: 3.4 GB of output, 13 launches of at most 256 MB (chunk = max(1024, (256 MiB // (16 D)) // 1024
+    * 1024) points, tests/residual_cases.py); compared on a strided sample of rows, the last 300 and every row within 3 of a
+    chunk boundary"""
     n = 10_000_000
     g = g5()
     targets = [str(t) for t in g["d21_targets"]]
     xyz, p = synthetic(n, seed=11)
     p = dict(p, pan=p["pan"] + 0.3, k1=p["k1"] * 1.1)
     with L.Points(xyz, [p["x"], p["y"], p["z"]], "f64") as pts:
-        J = pts.jacobian(L.params_vector(p), idx(targets))
+        L.kernel_timing(True)
+        try:
+            L.kernel_time_ms()
+            J = pts.jacobian(L.params_vector(p), idx(targets))
+            _, sections = L.kernel_time_ms()
+        finally:
+            L.kernel_timing(False)
     assert J.shape == (2 * n, 21)
-    rows = np.unique(np.r_[np.arange(0, n, 4099), np.arange(n - 300, n)])
+    assert sections == rc.launches(n, 21) == 13
+    rows = np.unique(np.r_[np.arange(0, n, 4099), np.arange(n - 300, n), rc.boundary_points(n, rc.chunk_points(n, 21))])
     got = J.reshape(n, 2, 21)[rows].reshape(-1, 21)
     del J
     assert_columns_close(got, cs_jacobian(xyz[rows], orc.params_to_vector(p), targets), 1e-9)
