@@ -4,7 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "host/alp_host.h"      // errors (set_error / fail / ALP_REQUIRE), pose record + fold_pose, the HIP-free host helpers
+#include "host/alp_host.h"      // errors (set_error / fail / ALP_REQUIRE), pose record + fold_pose, RowDiv + launch planning, the HIP-free host helpers
 
 namespace alp {
 
@@ -15,17 +15,6 @@ namespace alp {
             return ::alp::fail(ALP_EHIP, "%s failed: %s (%s:%d)", #expr,                  \
                                hipGetErrorString(e__), __FILE__, __LINE__);               \
     } while (0)
-
-// Division by the row length W of a grid point set (alp_points.hip: points_grid_detect; K1's grid form: alp_point_kernels.h).
-// q = (e * mul) >> shift equals e / W for every e < 2^31 when 1 <= W <= 2^16, with shift = 31 + ceil(log2 W) and
-// mul = ceil(2^shift / W) < 2^32: mul exceeds 2^shift / W by less than 1, so e * mul / 2^shift exceeds e / W by less than
-// e / 2^shift < 2^31 / 2^shift <= 1 / W, which never reaches the next integer (the fraction of e / W is at most (W - 1) / W).
-struct RowDiv {
-    uint32_t w = 0;          // 0: not a grid (K1 reads the x and y planes)
-    uint32_t shift = 0;
-    uint32_t mul = 0;
-    __host__ __device__ __forceinline__ uint32_t div(uint32_t e) const { return (uint32_t)(((uint64_t)e * mul) >> shift); }
-};
 
 // ------------------------------------------------------------------ global context
 struct Context {

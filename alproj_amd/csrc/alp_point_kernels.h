@@ -451,26 +451,11 @@ __device__ __forceinline__ void distort_group(const T *r, const NormCoords<T, V>
     }
 }
 
-// SHARED_POSE: every candidate of the call has the same rows 0..11 (only distortion
-// coefficients are optimised, the reference's second phase, example.py:75-78): the
-// normalised coordinates `pre` were computed once per point outside the candidate loop.
-template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, bool EXACT_POLES = false>
-__device__ __forceinline__ T group_loss_sum(const T *r, const T (&qx)[V], const T (&qy)[V], const T (&qz)[V],
-                                            const NormCoords<T, V> &pre, const T (&uoc)[V], const T (&voc)[V],
-                                            const bool (&ok)[V], T f_scale) {
+// The loss of a group of V points from their squared pixel distances d2, summed: the tail of both group_loss_sum forms.
+template <typename T, int LOSS, int V, bool MASKED>
+__device__ __forceinline__ T group_loss_tail(const T (&d2)[V], const bool (&ok)[V], T f_scale) {
     using N = Num<T>;
-    NormCoords<T, V> own;
-    if constexpr (!SHARED_POSE) norm_coords<T, V>(r, qx, qy, qz, own);
-    const NormCoords<T, V> &nc = SHARED_POSE ? pre : own;
-    T a[V], b[V], d2[V], dist[V];
-    distort_group<T, V, EXACT_POLES>(r, nc, a, b);
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-        // pixels u = a c0 + c0 (optimize.py:117-118): residual uo - u = (uo - c0) - c0 a
-        const T du = N::fma(a[j], r[28], uoc[j]);
-        const T dv = N::fma(b[j], r[29], voc[j]);
-        d2[j] = N::fma(dv, dv, du * du);
-    }
+    T dist[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) dist[j] = N::sqrt_pop(d2[j]);
     T acc = 0;
@@ -493,6 +478,29 @@ __device__ __forceinline__ T group_loss_sum(const T *r, const T (&qx)[V], const 
     return acc;
 }
 
+// SHARED_POSE: every candidate of the call has the same rows 0..11 (only distortion
+// coefficients are optimised, the reference's second phase, example.py:75-78): the
+// normalised coordinates `pre` were computed once per point outside the candidate loop.
+template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, bool EXACT_POLES = false>
+__device__ __forceinline__ T group_loss_sum(const T *r, const T (&qx)[V], const T (&qy)[V], const T (&qz)[V],
+                                            const NormCoords<T, V> &pre, const T (&uoc)[V], const T (&voc)[V],
+                                            const bool (&ok)[V], T f_scale) {
+    using N = Num<T>;
+    NormCoords<T, V> own;
+    if constexpr (!SHARED_POSE) norm_coords<T, V>(r, qx, qy, qz, own);
+    const NormCoords<T, V> &nc = SHARED_POSE ? pre : own;
+    T a[V], b[V], d2[V];
+    distort_group<T, V, EXACT_POLES>(r, nc, a, b);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        // pixels u = a c0 + c0 (optimize.py:117-118): residual uo - u = (uo - c0) - c0 a
+        const T du = N::fma(a[j], r[28], uoc[j]);
+        const T dv = N::fma(b[j], r[29], voc[j]);
+        d2[j] = N::fma(dv, dv, du * du);
+    }
+    return group_loss_tail<T, LOSS, V, MASKED>(d2, ok, f_scale);
+}
+
 // LENS-FREE populations (every candidate has k1..k6 = p1 = p2 = s1..s4 = 0: the reference's first optimisation phase,
 // example.py:51-54, BASELINE config 3).  optimize.py:112-118 then reduces to u = c0 x1 + c0, v = c1 y1 (1 + a1) / (1 + a2) + c1,
 // and the host folds -c0 and -c1 (1 + a1) / (1 + a2) into the X' and Y' rows in float64 (host/alp_host.cpp:
@@ -504,7 +512,7 @@ template <typename T, int LOSS, int V, bool MASKED>
 __device__ __forceinline__ T group_loss_sum_lens_free(const T *r, const T (&qx)[V], const T (&qy)[V], const T (&qz)[V],
                                                       const T (&uoc)[V], const T (&voc)[V], const bool (&ok)[V], T f_scale) {
     using N = Num<T>;
-    T zc[V], xn[V], yn[V], d2[V], dist[V];
+    T zc[V], xn[V], yn[V], d2[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
         zc[j] = N::fma(r[8], qx[j], N::fma(r[9], qy[j], N::fma(r[10], qz[j], r[11])));
@@ -519,22 +527,7 @@ __device__ __forceinline__ T group_loss_sum_lens_free(const T *r, const T (&qx)[
         const T dv = N::fma(yn[j], zc[j], voc[j]);
         d2[j] = N::fma(dv, dv, du * du);
     }
-#pragma unroll
-    for (int j = 0; j < V; ++j) dist[j] = N::sqrt_pop(d2[j]);
-    T acc = 0;
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-        if constexpr (LOSS == ALP_LOSS_MEAN_DIST) {
-            acc += (MASKED && !ok[j]) ? (T)0 : dist[j];
-        } else {                                          // Huber as in group_loss_sum
-            const T c = sizeof(T) == 4 ? (T)__builtin_fminf((float)dist[j], (float)f_scale) : (T)__builtin_fmin((double)dist[j], (double)f_scale);
-            const T t = N::fma((T)2, dist[j], -c);
-            if (MASKED && !ok[j]) continue;
-            acc = N::fma(c, t, acc);
-        }
-    }
-    if constexpr (LOSS != ALP_LOSS_MEAN_DIST) acc *= (T)0.5;
-    return acc;
+    return group_loss_tail<T, LOSS, V, MASKED>(d2, ok, f_scale);
 }
 
 // ------------------------------------------------------------------ K3: residual vectors of B poses

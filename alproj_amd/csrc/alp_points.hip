@@ -15,6 +15,8 @@
 // element type T (float: 20 B/vertex streamed per projection pass; double: 40 B/vertex).
 // Planes are padded to a multiple of 1024 elements so that 16-byte vector accesses and
 // whole-workgroup tiles never leave the allocation.
+// The launch shapes (popeval_kernel's stripes x tiles, the residual / Jacobian chunks, streaming grids, RowDiv) are planned in
+// host/alp_plan.h, HIP-free and checked on the CPU; this unit allocates, records events and launches what it plans.
 #include "alp_internal.h"
 
 #include <algorithm>
@@ -41,48 +43,9 @@ int alloc_planes(void **slab, int k, int64_t n_pad, size_t es, void **planes[]) 
     return ALP_OK;
 }
 
-template <typename TIn, typename T, int C>
-int upload_columns(const TIn *host, int64_t n, const double o[3], T *p0, T *p1, T *p2) {
-    // points per staging chunk: 16 M (192 MB of float32 triples).  Measured on the MI355X box (tools/h2d_rate.hip):
-    // one pageable hipMemcpy sustains 56 GB/s at this size, 48 MB chunks with a host sync each 36 GB/s.
-    const int64_t CH = 16 << 20;
-    const int64_t ch = n < CH ? (n > 0 ? n : 1) : CH;
-    TIn *stage = nullptr;
-    ALP_HIP(hipMalloc((void **)&stage, (size_t)ch * C * sizeof(TIn)));
-    int rc = ALP_OK;
-    for (int64_t off = 0; off < n; off += ch) {
-        const int64_t cnt = (n - off < ch) ? (n - off) : ch;
-        hipError_t e = hipMemcpyAsync(stage, host + off * C, (size_t)cnt * C * sizeof(TIn),
-                                      hipMemcpyHostToDevice, ctx().stream);
-        if (e != hipSuccess) { rc = fail(ALP_EHIP, "H2D upload: %s", hipGetErrorString(e)); break; }
-        const int grid = (int)((cnt + 255) / 256 < 4096 ? (cnt + 255) / 256 : 4096);
-        hipLaunchKernelGGL((aos_to_planes_kernel<TIn, T, C>), dim3(grid), dim3(256), 0, ctx().stream,
-                           stage, cnt, off, o[0], o[1], o[2], p0, p1, p2);
-        e = hipGetLastError();                    // the staging buffer is reused in stream order: no host sync per chunk
-        if (e != hipSuccess) { rc = fail(ALP_EHIP, "upload kernel: %s", hipGetErrorString(e)); break; }
-    }
-    if (hipStreamSynchronize(ctx().stream) != hipSuccess && !rc) rc = fail(ALP_EHIP, "upload: stream failed");
-    hipFree(stage);
-    return rc;
-}
-
-template <int C>
-int upload_any(const void *host, int in_dtype, int64_t n, const double o[3], int precision, void *p0,
-               void *p1, void *p2) {
-    if (in_dtype == ALP_F64 && precision == ALP_F64)
-        return upload_columns<double, double, C>((const double *)host, n, o, (double *)p0, (double *)p1, (double *)p2);
-    if (in_dtype == ALP_F64 && precision == ALP_F32)
-        return upload_columns<double, float, C>((const double *)host, n, o, (float *)p0, (float *)p1, (float *)p2);
-    if (in_dtype == ALP_F32 && precision == ALP_F64)
-        return upload_columns<float, double, C>((const float *)host, n, o, (double *)p0, (double *)p1, (double *)p2);
-    if (in_dtype == ALP_F32 && precision == ALP_F32)
-        return upload_columns<float, float, C>((const float *)host, n, o, (float *)p0, (float *)p1, (float *)p2);
-    return fail(ALP_EINVAL, "in_dtype must be ALP_F32 or ALP_F64");
-}
-
 // One host COLUMN (n contiguous values of TIn) -> one device plane of T, minus its origin component in float64: the columns of a
 // table as they lie (a pandas block is columns x rows: a DataFrame's x, y, z are three contiguous runs), no host-side
-// interleaving.  Same chunking as upload_columns.
+// interleaving.
 template <typename TIn, typename T>
 __global__ __launch_bounds__(256) void column_to_plane_kernel(const TIn *__restrict__ src, int64_t count, int64_t dst_off, double o,
                                                               T *__restrict__ plane) {
@@ -91,21 +54,22 @@ __global__ __launch_bounds__(256) void column_to_plane_kernel(const TIn *__restr
         plane[dst_off + i] = (T)((double)src[i] - o);
 }
 
-template <typename TIn, typename T>
-int upload_planes_t(const void *const *cols, int ncols, int64_t n, const double *o, void *const *planes) {
-    const int64_t CH = 48 << 20;                      // values per staging chunk (192 MB of float32)
+// The staged upload: each of the `nsrc` host arrays of n items x `width` values crosses PCIe in chunks of at most CH items into
+// ONE device staging buffer, and launch(source, stage, count, offset, grid) spreads a chunk over the planes.
+template <typename TIn, typename Launch>
+int staged_upload(const void *const *srcs, int nsrc, int64_t n, int width, int64_t CH, Launch launch) {
     const int64_t ch = n < CH ? (n > 0 ? n : 1) : CH;
     TIn *stage = nullptr;
-    ALP_HIP(hipMalloc((void **)&stage, (size_t)ch * sizeof(TIn)));
+    ALP_HIP(hipMalloc((void **)&stage, (size_t)ch * width * sizeof(TIn)));
     int rc = ALP_OK;
-    for (int c = 0; c < ncols && !rc; ++c)
+    for (int c = 0; c < nsrc && !rc; ++c)
         for (int64_t off = 0; off < n; off += ch) {
             const int64_t cnt = (n - off < ch) ? (n - off) : ch;
-            hipError_t e = hipMemcpyAsync(stage, (const TIn *)cols[c] + off, (size_t)cnt * sizeof(TIn), hipMemcpyHostToDevice, ctx().stream);
+            hipError_t e = hipMemcpyAsync(stage, (const TIn *)srcs[c] + off * width, (size_t)cnt * width * sizeof(TIn),
+                                          hipMemcpyHostToDevice, ctx().stream);
             if (e != hipSuccess) { rc = fail(ALP_EHIP, "H2D upload: %s", hipGetErrorString(e)); break; }
-            const int grid = (int)((cnt + 255) / 256 < 4096 ? (cnt + 255) / 256 : 4096);
-            hipLaunchKernelGGL((column_to_plane_kernel<TIn, T>), dim3(grid), dim3(256), 0, ctx().stream, stage, cnt, off, o[c], (T *)planes[c]);
-            e = hipGetLastError();                    // the staging buffer is reused in stream order
+            launch(c, stage, cnt, off, (int)((cnt + 255) / 256 < 4096 ? (cnt + 255) / 256 : 4096));
+            e = hipGetLastError();                    // the staging buffer is reused in stream order: no host sync per chunk
             if (e != hipSuccess) { rc = fail(ALP_EHIP, "upload kernel: %s", hipGetErrorString(e)); break; }
         }
     if (hipStreamSynchronize(ctx().stream) != hipSuccess && !rc) rc = fail(ALP_EHIP, "upload: stream failed");
@@ -113,20 +77,31 @@ int upload_planes_t(const void *const *cols, int ncols, int64_t n, const double 
     return rc;
 }
 
-int upload_planes(const void *const *cols, int ncols, int in_dtype, int64_t n, const double *o, int precision, void *const *planes) {
-    if (in_dtype == ALP_F64 && precision == ALP_F64) return upload_planes_t<double, double>(cols, ncols, n, o, planes);
-    if (in_dtype == ALP_F64 && precision == ALP_F32) return upload_planes_t<double, float>(cols, ncols, n, o, planes);
-    if (in_dtype == ALP_F32 && precision == ALP_F64) return upload_planes_t<float, double>(cols, ncols, n, o, planes);
-    if (in_dtype == ALP_F32 && precision == ALP_F32) return upload_planes_t<float, float>(cols, ncols, n, o, planes);
+// C planes from the C columns cols[] as they lie, or (cols == NULL) from `rows`, n x C row-major; o[0..3) = the origin
+template <typename TIn, typename T, int C>
+int upload_t(const void *rows, const void *const *cols, int64_t n, const double *o, void *const *planes) {
+    if (cols)       // values per staging chunk: 48 M (192 MB of float32)
+        return staged_upload<TIn>(cols, C, n, 1, (int64_t)48 << 20, [&](int c, const TIn *stage, int64_t cnt, int64_t off, int grid) {
+            hipLaunchKernelGGL((column_to_plane_kernel<TIn, T>), dim3(grid), dim3(256), 0, ctx().stream, stage, cnt, off, o[c], (T *)planes[c]);
+        });
+    // points per staging chunk: 16 M (192 MB of float32 triples).  Measured on the MI355X box (tools/h2d_rate.hip):
+    // one pageable hipMemcpy sustains 56 GB/s at this size, 48 MB chunks with a host sync each 36 GB/s.
+    return staged_upload<TIn>(&rows, 1, n, C, (int64_t)16 << 20, [&](int, const TIn *stage, int64_t cnt, int64_t off, int grid) {
+        hipLaunchKernelGGL((aos_to_planes_kernel<TIn, T, C>), dim3(grid), dim3(256), 0, ctx().stream, stage, cnt, off, o[0], o[1], o[2],
+                           (T *)planes[0], (T *)planes[1], (T *)planes[2]);
+    });
+}
+
+template <int C>
+int upload(const void *rows, const void *const *cols, int in_dtype, int64_t n, const double *o, int precision, void *const *planes) {
+    if (in_dtype == ALP_F64 && precision == ALP_F64) return upload_t<double, double, C>(rows, cols, n, o, planes);
+    if (in_dtype == ALP_F64 && precision == ALP_F32) return upload_t<double, float, C>(rows, cols, n, o, planes);
+    if (in_dtype == ALP_F32 && precision == ALP_F64) return upload_t<float, double, C>(rows, cols, n, o, planes);
+    if (in_dtype == ALP_F32 && precision == ALP_F32) return upload_t<float, float, C>(rows, cols, n, o, planes);
     return fail(ALP_EINVAL, "in_dtype must be ALP_F32 or ALP_F64");
 }
 
-int stream_grid(int64_t items) {
-    // memory-bound streaming kernels: enough workgroups to fill 256 CUs x 8, grid-stride beyond
-    const int64_t want = (items + 255) / 256;
-    const int64_t cap = (int64_t)ctx().cu_count * 8;
-    return (int)(want < 1 ? 1 : (want < cap ? want : cap));
-}
+int stream_grid(int64_t items) { return host::stream_grid(items, ctx().cu_count); }
 
 // ------------------------------------------------------------------ grid recognition (K1's grid form)
 // A DSM's vertex list is its raster flattened row-major (meshgrid(x, y)): x depends on the column alone and y on the row alone,
@@ -171,16 +146,6 @@ __global__ __launch_bounds__(256) void grid_verify_kernel(const B *__restrict__ 
     if (!ok) atomicOr(flags + 1, 1u);
 }
 
-RowDiv row_div(uint32_t w) {
-    RowDiv rd;
-    uint32_t l = 0;
-    while ((1u << l) < w) ++l;                    // ceil(log2 w)
-    rd.w = w;
-    rd.shift = 31 + l;
-    rd.mul = (uint32_t)((((uint64_t)1 << rd.shift) + w - 1) / w);
-    return rd;
-}
-
 template <typename B>
 int grid_detect_t(alp_points *p, uint32_t *flags, RowDiv *out) {
     hipStream_t st = ctx().stream;
@@ -192,7 +157,7 @@ int grid_detect_t(alp_points *p, uint32_t *flags, RowDiv *out) {
     ALP_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st));
     ALP_HIP(hipStreamSynchronize(st));
     if (h[0] == GRID_NONE || h[0] > GRID_MAX_ROW) return ALP_OK;     // a single row, or too wide
-    const RowDiv rd = row_div(h[0]);
+    const RowDiv rd = host::row_div(h[0]);
     hipLaunchKernelGGL(grid_verify_kernel<B>, dim3(stream_grid(n)), dim3(256), 0, st, (const B *)p->x, (const B *)p->y, n, rd, flags);
     ALP_HIP(hipGetLastError());
     ALP_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -255,6 +220,20 @@ int ensure_pop_scratch(alp_points *p, int64_t P, int nblk) {
     return ALP_OK;
 }
 
+// the three timing events of a handle, all or none: a partial failure must not leave ev[1] / ev[2] NULL for good
+int ensure_pop_events(alp_points *p) {
+    if (p->ev[0]) return ALP_OK;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (auto &e : ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            for (auto &d : ev)
+                if (d) hipEventDestroy(d);
+            return fail(ALP_EHIP, "hipEventCreate failed");
+        }
+    for (int k = 0; k < 3; ++k) p->ev[k] = ev[k];
+    return ALP_OK;
+}
+
 // the launch half of enqueue_popeval (alp_points_internal.h: popeval_launch): the records lie in p->cand_dev
 template <typename T>
 int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false) {
@@ -267,91 +246,26 @@ int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bo
                                popeval_kernel<T, ALP_LOSS_HUBER, PopCfg<T>, false>,
                                popeval_kernel<T, ALP_LOSS_HUBER, PopCfg<T>, true>,
                                popeval_kernel<T, ALP_LOSS_HUBER, PopCfgLF<T>, false, T, true>};
-    // one workgroup per stripe of ~24 rows of 256 points (four groups of V = 6), between 4 and 64
-    // workgroups per CU: a stripe is re-read once per tile of 128 candidates and a short one stays
-    // in cache between those passes.  Measured, 100 M x 2048 float32: 4 workgroups per CU 244 ms,
-    // 8: 229, 16: 224, 32: 221, 64: 219, 128: 219; 10 M x 256: 8 per CU (stripes of 19 rows) 3.31
-    // ms, 16: 3.46, 32: 3.73.  float64 (three workgroups resident per CU): 24 per CU (round 5: 527 ms against 541 with 4).
-    int nblk = ctx().cu_count * (sizeof(T) == 8 ? 24 : 4);
-    int ytiles = 1;
-    const int64_t rows = (p->n + 255) / 256;
-    const int VV = lens_free ? PopCfgLF<T>::V : PopCfg<T>::V;       // rows of a full group
-    if (sizeof(T) == 4) {
-        const int64_t want = (rows + 4 * VV - 1) / (4 * VV);            // ~four full groups per stripe
-        const int64_t lo = (int64_t)ctx().cu_count * 4, hi = (int64_t)ctx().cu_count * 64;
-        // whole rounds of the 4 workgroups a CU holds at once while the grid is only a few rounds deep
-        const int64_t rounded = (want + lo - 1) / lo * lo;
-        nblk = (int)(want < lo ? lo : (want > hi ? hi : (want < 4 * lo ? rounded : want)));
-        // Two candidate tiles or more: the grid is stripes x tiles -- a workgroup runs ONE tile of 128 candidates over a stripe of
-        // whole groups of V rows.  Round 3 introduced it for populations of a few tiles whose one-column grid was only a few
-        // rounds deep (10 M x 256: 1954 stripes of 20 rows = 1.9 rounds of the 1024 resident workgroups, 2 rows of every 20 in
-        // the narrow groups; tools/sweep_popeval_grid.py, ms for P = 256 / 384 / 512 at 10 M points: one column of 2048 stripes
-        // 3.15 / 4.64 / 6.14; stripes of 18 rows x tiles 2.90 / 4.33 / 5.61).  Round 6 measured it at every other shape as well
-        // (profiles/r06_popeval_grid_sweep.txt, one column -> stripes x tiles, general | lens-free variant): 10 M x 1024 12.2 ->
-        // 11.0 | 5.81 -> 4.91 ms; 10 M x 2048 24.6 -> 21.7 | 11.5 -> 9.64; 30 M x 1024 34.9 -> 32.5 | 15.8 -> 14.4; 100 M x 2048
-        // 219.5 -> 215.2 | 95.7 -> 93.4 -- never slower, so it is the rule.  Stripes of k groups, k grown with the point count
-        // (about two stripes per resident slot and tile column for small sets, up to 16 groups = ~25 000 points for large ones:
-        // the timings are flat from 4 to 16 groups and the partial-sum buffer shrinks with the stripe count).
-        // The sums depend on the shape in the last bits only (up to ~3e-8 relative between shapes: other group boundaries).
-        const int tiles = (int)((P + POP_TC - 1) / POP_TC);
-        if (tiles >= 2) {
-            int64_t k = (int64_t)((double)rows / ((double)VV * 2.12 * (double)lo) + 0.5);      // groups of V rows per stripe
-            if (k < 1) k = 1;
-            if (k > 16) k = 16;
-            const int64_t stripes = (rows + VV * k - 1) / (VV * k);
-            if (stripes * tiles >= 4 * lo) {
-                nblk = (int)stripes;
-                ytiles = tiles;
-            }
-        }
-    }
-    if (sizeof(T) == 8) {
-        // the per-stripe partial sums (nblk x P doubles, read once per generation by reduce_partials_kernel) stay below 128 MB:
-        // 24 stripes per CU at P = 2048 are 100 MB (kept: 527 ms against 533 with 8 per CU); a population of 8192 gets 2048 stripes
-        const int64_t cap = ((int64_t)128 << 20) / (8 * P);
-        const int64_t lo = (int64_t)ctx().cu_count * 3;                  // one round of the three resident workgroups per CU
-        if (nblk > cap) nblk = (int)(cap > lo ? cap : lo);
-    }
-    // tuning hook: "stripes,ytiles".  The stripe count moves the last bits of the losses in either precision: it decides which rows
-    // go through the V-wide, the 2-wide and the masked single-row groups (float32: other group sums, up to ~3e-8 relative) and sets the
-    // ORDER of the float64 additions.  Same grid, same bits (tests/test_gpu_popeval_grid.py) -- a development switch, not a setting
-    if (const char *e = getenv("ALP_POP_GRID")) {
-        const int tiles = (int)((P + PopCfg<T>::TC - 1) / PopCfg<T>::TC);
-        int a = 0, b = 0;
-        if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 1 && b >= 1 && b <= tiles) { nblk = a; ytiles = b; }
-    }
-    if (rows < nblk) nblk = (int)(rows > 0 ? rows : 1);
-    if (batched) {
-        const int64_t cap = POP_BATCHED_PARTIALS_BYTES / (8 * P);
-        if (nblk > cap) nblk = (int)(cap > 1 ? cap : 1);
-        const int64_t tiles = (P + PopCfg<T>::TC - 1) / PopCfg<T>::TC, fill = (int64_t)ctx().cu_count * 4;
-        if (ytiles == 1 && tiles >= 2 && nblk < fill) {
-            const int64_t cols = (fill + nblk - 1) / nblk;
-            ytiles = (int)(cols < tiles ? cols : tiles);
-        }
-    }
-    if (int rc = ensure_pop_scratch(p, P, nblk)) return rc;
-    if (!p->ev[0]) {            // all three or none: a partial failure must not leave ev[1] / ev[2] NULL for good
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        for (auto &e : ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                for (auto &d : ev)
-                    if (d) hipEventDestroy(d);
-                return fail(ALP_EHIP, "hipEventCreate failed");
-            }
-        for (int k = 0; k < 3; ++k) p->ev[k] = ev[k];
-    }
+    static_assert(PopCfg<T>::TC == PopCfgLF<T>::TC, "one candidate tile size per precision: host::pop_grid takes one TC");
+    // the grid rule: host/alp_plan.h.  ALP_POP_GRID = "stripes,ytiles" (a development switch) overrides it where the pair is valid:
+    // one that does not parse leaves a 0, which pop_grid ignores
+    int ov[2] = {0, 0};
+    if (const char *e = getenv("ALP_POP_GRID")) sscanf(e, "%d,%d", &ov[0], &ov[1]);
+    const host::PopGrid g = host::pop_grid(p->n, P, sizeof(T) == 8, lens_free ? PopCfgLF<T>::V : PopCfg<T>::V, PopCfg<T>::TC,
+                                           ctx().cu_count, batched, ov[0], ov[1]);
+    if (int rc = ensure_pop_scratch(p, P, g.stripes)) return rc;
+    if (int rc = ensure_pop_events(p)) return rc;
     p->last_info[0] = lens_free ? ALP_POP_LENS_FREE : (shared_pose ? ALP_POP_SHARED_POSE : ALP_POP_GENERAL);
-    p->last_info[1] = nblk;
-    p->last_info[2] = ytiles;
+    p->last_info[1] = g.stripes;
+    p->last_info[2] = g.tile_cols;
     ALP_HIP(hipEventRecord(p->ev[0], ctx().stream));
     const PoseRec<T> *recs_general = (const PoseRec<T> *)p->cand_dev;
-    hipLaunchKernelGGL(kernels[which], dim3(nblk, ytiles), dim3(256), 0, ctx().stream, (const T *)p->x, (const T *)p->y,
+    hipLaunchKernelGGL(kernels[which], dim3(g.stripes, g.tile_cols), dim3(256), 0, ctx().stream, (const T *)p->x, (const T *)p->y,
                        (const T *)p->z, (const T *)p->uo, (const T *)p->vo, p->n, lens_free ? recs_general + p->cand_cap : recs_general,
                        (int)P, (T)f_scale, p->partials, recs_general);
     ALP_HIP(hipGetLastError());
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, ctx().stream,
-                       p->partials, nblk, (int)P, (double)p->n, p->sums_dev);
+                       p->partials, g.stripes, (int)P, (double)p->n, p->sums_dev);
     ALP_HIP(hipGetLastError());
     ALP_HIP(hipEventRecord(p->ev[1], ctx().stream));
     if (int rc = comm_allreduce_sum_f64(p->sums_dev, P + 1)) return rc;
@@ -413,9 +327,7 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
 // sums_out[0..K) = loss sums, sums_out[K] = vertex count.  Synchronous.
 int confirm_losses(alp_points *p, const double *cand, const int64_t *which, int K, int loss_kind, double f_scale,
                    double *sums_out) {
-    const int nblk_want = ctx().cu_count * 4;
-    const int64_t rows = (p->n + 255) / 256;
-    const int nblk = (int)(rows < nblk_want ? (rows > 0 ? rows : 1) : nblk_want);
+    const int nblk = host::confirm_grid(p->n, ctx().cu_count);
     const size_t rec_bytes = (size_t)CONFIRM_MAX * sizeof(PoseRec<double>);
     if (!p->conf_dev || p->conf_nblk < nblk) {
         if (p->conf_dev) hipFree(p->conf_dev);
@@ -448,17 +360,27 @@ int confirm_losses(alp_points *p, const double *cand, const int64_t *which, int 
     return ALP_OK;
 }
 
-// device staging of the residual entry points: at most RES_CHUNK_BYTES of output per launch
-constexpr size_t RES_CHUNK_BYTES = (size_t)256 << 20;
+// The chunk loop of alp_residuals* and alp_jacobian: launch(offset, count) fills the staging buffer with the output of `count`
+// points (host::stage_chunk_points of them: at most RES_CHUNK_BYTES per launch), copy(offset, count) sends it to the host.
+template <typename Launch, typename Copy>
+int staged_chunks(int64_t n, int64_t chunk, Launch launch, Copy copy) {
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t cnt = n - off < chunk ? n - off : chunk;
+        ktime_begin();
+        launch(off, cnt);
+        ktime_end();
+        ALP_HIP(hipGetLastError());
+        ALP_HIP(copy(off, cnt));
+        ALP_HIP(hipStreamSynchronize(ctx().stream));       // the staging buffer is reused; the records / the plan must outlive their copy
+    }
+    return ALP_OK;
+}
 
 template <typename T>
 int residuals_impl(alp_points *p, const double *cand, int64_t B, double *out) {
     // B pose records (kernel argument for B == 1 would save the copy; one path keeps it simple)
     const size_t rec_bytes = round_up((int64_t)(B * sizeof(PoseRec<T>)), 256);
-    int64_t chunk = (int64_t)(RES_CHUNK_BYTES / ((size_t)B * sizeof(double2)));
-    chunk = chunk / 1024 * 1024;
-    if (chunk < 1024) chunk = 1024;
-    if (chunk > p->n) chunk = p->n;
+    const int64_t chunk = host::stage_chunk_points(p->n, B);
     char *dev = nullptr;
     if (int rc = scratch_reserve(rec_bytes + (size_t)B * chunk * sizeof(double2), (void **)&dev)) return rc;
     PoseRec<T> *poses_dev = (PoseRec<T> *)dev;
@@ -467,53 +389,37 @@ int residuals_impl(alp_points *p, const double *cand, int64_t B, double *out) {
     for (int64_t b = 0; b < B; ++b) fold_pose_t<T>(cand + b * ALP_NPARAM, p->origin, &poses[b]);
     hipStream_t st = ctx().stream;
     ALP_HIP(hipMemcpyAsync(poses_dev, poses.data(), (size_t)B * sizeof(PoseRec<T>), hipMemcpyHostToDevice, st));
-    for (int64_t off = 0; off < p->n; off += chunk) {
-        const int64_t cnt = p->n - off < chunk ? p->n - off : chunk;
-        ktime_begin();
+    return staged_chunks(p->n, chunk, [&](int64_t off, int64_t cnt) {
         hipLaunchKernelGGL(residual_batch_kernel<T>, dim3(stream_grid(cnt)), dim3(256), 0, st, (const T *)p->x + off,
                            (const T *)p->y + off, (const T *)p->z + off, (const T *)p->uo + off, (const T *)p->vo + off,
                            res_dev, cnt, poses_dev, (int)B);
-        ktime_end();
-        ALP_HIP(hipGetLastError());
+    }, [&](int64_t off, int64_t cnt) {
         // row b of the chunk -> out[b][off .. off + cnt); a chunk that holds whole rows is one contiguous run (a pitched copy of
         // the same bytes took 2-3 x as long)
-        if (cnt == p->n)
-            ALP_HIP(hipMemcpyAsync(out, res_dev, (size_t)B * cnt * sizeof(double2), hipMemcpyDeviceToHost, st));
-        else
-            ALP_HIP(hipMemcpy2DAsync(out + 2 * off, (size_t)p->n * sizeof(double2), res_dev, (size_t)cnt * sizeof(double2),
-                                     (size_t)cnt * sizeof(double2), (size_t)B, hipMemcpyDeviceToHost, st));
-        ALP_HIP(hipStreamSynchronize(st));       // the staging buffer is reused; poses must outlive their copy
-    }
-    return ALP_OK;
+        if (cnt == p->n) return hipMemcpyAsync(out, res_dev, (size_t)B * cnt * sizeof(double2), hipMemcpyDeviceToHost, st);
+        return hipMemcpy2DAsync(out + 2 * off, (size_t)p->n * sizeof(double2), res_dev, (size_t)cnt * sizeof(double2),
+                                (size_t)cnt * sizeof(double2), (size_t)B, hipMemcpyDeviceToHost, st);
+    });
 }
 
-// alp_jacobian: chunks of whole points (a chunk's rows are one contiguous block of the output: one copy each), at most
-// RES_CHUNK_BYTES of output per launch as for the residuals
+// alp_jacobian: chunks of whole points (a chunk's rows are one contiguous block of the output: one copy each)
 template <typename TS>
 int jacobian_impl(alp_points *p, const JacPlan &plan, double *out) {
     const int64_t D = plan.D;
     const size_t plan_bytes = round_up((int64_t)sizeof(JacPlan), 256);
-    int64_t chunk = (int64_t)(RES_CHUNK_BYTES / ((size_t)D * sizeof(double2)));
-    chunk = chunk / 1024 * 1024;
-    if (chunk < 1024) chunk = 1024;
-    if (chunk > p->n) chunk = p->n;
+    const int64_t chunk = host::stage_chunk_points(p->n, D);
     char *dev = nullptr;
     if (int rc = scratch_reserve(plan_bytes + (size_t)chunk * D * sizeof(double2), (void **)&dev)) return rc;
     JacPlan *plan_dev = (JacPlan *)dev;
     double2 *jac_dev = (double2 *)(dev + plan_bytes);
     hipStream_t st = ctx().stream;
     ALP_HIP(hipMemcpyAsync(plan_dev, &plan, sizeof(JacPlan), hipMemcpyHostToDevice, st));
-    for (int64_t off = 0; off < p->n; off += chunk) {
-        const int64_t cnt = p->n - off < chunk ? p->n - off : chunk;
-        ktime_begin();
+    return staged_chunks(p->n, chunk, [&](int64_t off, int64_t cnt) {
         hipLaunchKernelGGL(jacobian_kernel<TS>, dim3(stream_grid(cnt)), dim3(256), 0, st, (const TS *)p->x + off,
                            (const TS *)p->y + off, (const TS *)p->z + off, jac_dev, cnt, (const JacPlan *)plan_dev);
-        ktime_end();
-        ALP_HIP(hipGetLastError());
-        ALP_HIP(hipMemcpyAsync(out + 2 * D * off, jac_dev, (size_t)cnt * D * sizeof(double2), hipMemcpyDeviceToHost, st));
-        ALP_HIP(hipStreamSynchronize(st));       // the staging buffer is reused; the plan must outlive its copy
-    }
-    return ALP_OK;
+    }, [&](int64_t off, int64_t cnt) {
+        return hipMemcpyAsync(out + 2 * D * off, jac_dev, (size_t)cnt * D * sizeof(double2), hipMemcpyDeviceToHost, st);
+    });
 }
 
 }  // namespace
@@ -634,8 +540,7 @@ static int points_create(const void *xyz, const void *const *cols, int in_dtype,
     int rc = alloc_planes(&p->slab_xyz, 3, p->n_pad, p->esize(), xyz_planes);
     if (!rc && n > 0) {
         void *const planes[3] = {p->x, p->y, p->z};
-        rc = cols ? upload_planes(cols, 3, in_dtype, n, origin, precision, planes)
-                  : upload_any<3>(xyz, in_dtype, n, origin, precision, p->x, p->y, p->z);
+        rc = upload<3>(xyz, cols, in_dtype, n, origin, precision, planes);
     }
     if (!rc) {
         hipError_t e = hipStreamSynchronize(ctx().stream);
@@ -689,38 +594,29 @@ int alp_points_layout(const alp_points_t *p, int64_t *row_length) {
     return ALP_OK;
 }
 
-int alp_points_set_observed(alp_points_t *p, const void *uv, int in_dtype) {
+// uv: n x 2 row-major (cols == NULL), or cols[0..1]: the u and v columns as they lie
+static int set_observed(alp_points_t *p, const void *uv, const void *const *cols, int in_dtype) {
     if (int rc = require_init()) return rc;
     ALP_REQUIRE(p, "points handle is NULL");
-    ALP_REQUIRE(p->n == 0 || uv, "uv is NULL");
+    ALP_REQUIRE(p->n == 0 || uv || (cols && cols[0] && cols[1]), "observed pixels are NULL");
     ALP_REQUIRE(in_dtype == ALP_F32 || in_dtype == ALP_F64, "in_dtype must be ALP_F32 or ALP_F64");
     if (!p->uo) {
         void **obs_planes[2] = {&p->uo, &p->vo};
         if (int rc = alloc_planes(&p->slab_obs, 2, p->n_pad, p->esize(), obs_planes)) return rc;
     }
     const double zero[3] = {0, 0, 0};
+    void *const planes[3] = {p->uo, p->vo, nullptr};
     if (p->n > 0)
-        if (int rc = upload_any<2>(uv, in_dtype, p->n, zero, p->precision, p->uo, p->vo, nullptr)) return rc;
+        if (int rc = upload<2>(uv, cols, in_dtype, p->n, zero, p->precision, planes)) return rc;
     ALP_HIP(hipStreamSynchronize(ctx().stream));
     return ALP_OK;
 }
 
+int alp_points_set_observed(alp_points_t *p, const void *uv, int in_dtype) { return set_observed(p, uv, nullptr, in_dtype); }
+
 int alp_points_set_observed_columns(alp_points_t *p, const void *u, const void *v, int in_dtype) {
-    if (int rc = require_init()) return rc;
-    ALP_REQUIRE(p, "points handle is NULL");
-    ALP_REQUIRE(p->n == 0 || (u && v), "u or v is NULL");
-    ALP_REQUIRE(in_dtype == ALP_F32 || in_dtype == ALP_F64, "in_dtype must be ALP_F32 or ALP_F64");
-    if (!p->uo) {
-        void **obs_planes[2] = {&p->uo, &p->vo};
-        if (int rc = alloc_planes(&p->slab_obs, 2, p->n_pad, p->esize(), obs_planes)) return rc;
-    }
-    const double zero[2] = {0, 0};
     const void *const cols[2] = {u, v};
-    void *const planes[2] = {p->uo, p->vo};
-    if (p->n > 0)
-        if (int rc = upload_planes(cols, 2, in_dtype, p->n, zero, p->precision, planes)) return rc;
-    ALP_HIP(hipStreamSynchronize(ctx().stream));
-    return ALP_OK;
+    return set_observed(p, nullptr, cols, in_dtype);
 }
 
 int alp_project(alp_points_t *p, const double params[ALP_NPARAM]) {

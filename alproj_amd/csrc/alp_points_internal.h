@@ -52,13 +52,12 @@ struct alp_points {
 namespace alp {
 
 // The population evaluation of P candidates whose pose records already lie in p->cand_dev (general records at [0, P), the
-// lens-free ones at [cand_cap, cand_cap + P) when `lens_free`): grid choice, popeval_kernel + reduce_partials_kernel into
+// lens-free ones at [cand_cap, cand_cap + P) when `lens_free`): grid choice (host/alp_plan.h: pop_grid), popeval_kernel + reduce_partials_kernel into
 // p->sums_dev (P + 1 sums, the last one the vertex count), the all-reduce of those sums when a communicator exists, and
 // last_info / the timing events.  Enqueue only.  The caller has reserved the scratch for P (points_pop_reserve).
 // `batched` (the device loop's multi-start launch, K starts x P candidates): the stripe count is capped so that the partial sums
-// (stripes x P doubles) stay within POP_BATCHED_PARTIALS_BYTES, and when the stripes alone do not fill the GPU (a GCP-sized set
+// (stripes x P doubles) stay within host::POP_BATCHED_PARTIALS_BYTES, and when the stripes alone do not fill the GPU (a GCP-sized set
 // has a handful of rows) the grid gets candidate-tile columns up to four workgroups per CU.  Every other launch keeps its grid.
-constexpr int64_t POP_BATCHED_PARTIALS_BYTES = (int64_t)128 << 20;
 int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false);
 // population scratch (records, sums) for P candidates
 int points_pop_reserve(alp_points *p, int64_t P);

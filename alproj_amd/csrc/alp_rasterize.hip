@@ -129,7 +129,7 @@ struct RzLook {
 static int rz_look_at(int agg, const double *values, long long n, int nb, bool planar, unsigned *flags_dev, RzLook *look) {
     hipStream_t st = ctx().stream;
     const long long count = n * nb;
-    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((count + 255) / 256, (long long)ctx().cu_count * 8));
+    const unsigned grid = (unsigned)host::stream_grid(count, ctx().cu_count);
     if (agg == AGG_MEDIAN) {
         ALP_HIP(hipMemsetAsync(flags_dev, 0, (size_t)nb * sizeof(unsigned), st));
         hipLaunchKernelGGL(rz_median_check_kernel, dim3(grid), dim3(256), 0, st, values, count, nb, planar ? n : 0ll, flags_dev);

@@ -1,7 +1,7 @@
 // Host-side code of libalproj_hip.so that needs no HIP: error reporting, the float64 folding of a camera pose, the
 // threaded helpers behind alp_host_hash64 / alp_host_minmax / alp_host_prefault, the threads that recognise a regular
-// grid in a host index array, the workers that widen / narrow a fetched plane, and the argmin / confirmation-band
-// selection of alp_eval_population_wait.
+// grid in a host index array, the workers that widen / narrow a fetched plane, the argmin / confirmation-band
+// selection of alp_eval_population_wait, and the launch planning of the point-set kernels (host/alp_plan.h).
 //
 // It is one header + host/alp_host.cpp so that the SAME code is compiled twice: by hipcc into the library, and -- by the
 // same clang++ and by g++ -- under -fsanitize=address,undefined and -fsanitize=thread into build/host_san/
@@ -67,6 +67,7 @@ struct alignas(16) PoseRec {
 
 }  // namespace alp
 #include "host/alp_fold.h"      // fold_pose_hd / lens_free_from_general_hd: the arithmetic, host and device
+#include "host/alp_plan.h"      // RowDiv, pop_grid, stage_chunk_points, stream_grid: the launch planning of alp_points.hip
 namespace alp {
 
 // params: the 25 ABI parameters; origin: local origin of the point set (absolute coords).

@@ -4,11 +4,13 @@
 // its thread thresholds (1, 70 001, one short of / exactly / one past a slice, two slices and a ragged rest), with
 // thread counts from 1 to 64, from several caller threads at once (independent handles may be used concurrently:
 // include/alproj_hip.h), and compared with a serial restatement written here.  Exit code 0 and "host selfcheck ok" =
-// every comparison held; the sanitizers add their own verdict on stderr.
+// every comparison held; the sanitizers add their own verdict on stderr.  --plan prints what host/alp_plan.h plans for the
+// queries it is given (tests/test_launch_plan.py holds the Python restatements of the launch rules to it).
 #include <cinttypes>
 #include <mutex>
 #include <random>
 #include <string>
+#include <utility>
 
 #include "host/alp_host.h"
 
@@ -318,6 +320,69 @@ void check_selection() {
     }
 }
 
+// ------------------------------------------------------------------ launch planning (host/alp_plan.h)
+// invariants of every plan over point counts around whole rows of 256, populations from one candidate to the ABI's limit, both
+// precisions with their two group heights, small and large GPUs; tests/test_launch_plan.py compares single plans (--plan)
+void check_plan() {
+    std::vector<int64_t> ns = {1, 2, 300, 1127, 67 * 256 - 37, 100000, 1000000, 10000000, 30000000, 100000000};
+    for (int64_t k : {1, 2, 5, 24, 1024, 4096, 39063, 390625})
+        for (int64_t d : {-1, 0, 1}) ns.push_back(k * 256 + d);
+    const int64_t Ps[] = {1, 2, 127, 128, 129, 250, 256, 384, 2048, 4096, 8192, 32768, 65536, (int64_t)1 << 20};
+    const int TC = 128;
+    for (int cu : {1, 64, 256, 304})
+        for (int64_t n : ns) {
+            const int64_t rows = (n + 255) / 256;
+            const int sg = host::stream_grid(n, cu), cg = host::confirm_grid(n, cu);
+            CHECK(sg >= 1 && sg <= 8 * cu && (sg == 8 * cu || sg == rows), "stream_grid(%" PRId64 ", %d) = %d", n, cu, sg);
+            CHECK(cg >= 1 && cg <= 4 * cu && cg <= rows, "confirm_grid(%" PRId64 ", %d) = %d", n, cu, cg);
+            for (int64_t P : Ps)
+                for (int f64 = 0; f64 < 2; ++f64)
+                    for (int V : {f64 ? 5 : 6, f64 ? 6 : 8})
+                        for (int batched = 0; batched < 2; ++batched) {
+                            const int64_t tiles = (P + TC - 1) / TC;
+                            const host::PopGrid g = host::pop_grid(n, P, f64, V, TC, cu, batched);
+                            CHECK(g.stripes >= 1 && g.stripes <= rows && g.tile_cols >= 1 && g.tile_cols <= tiles,
+                                  "pop_grid(%" PRId64 ", %" PRId64 ", f64=%d, V=%d, cu=%d, batched=%d) = %d x %d", n, P, f64, V, cu, batched,
+                                  g.stripes, g.tile_cols);
+                            CHECK(!batched || (int64_t)g.stripes * P * 8 <= host::POP_BATCHED_PARTIALS_BYTES,
+                                  "batched partial sums: %d stripes x %" PRId64, g.stripes, P);
+                            // ALP_POP_GRID: a valid pair is taken (stripes still clamped to the rows), any other one ignored
+                            const int64_t want_rows = std::min<int64_t>(rows, 7);
+                            const host::PopGrid o = host::pop_grid(n, P, f64, V, TC, cu, false, 7, (int)tiles);
+                            CHECK(o.stripes == want_rows && o.tile_cols == tiles, "override 7 x %" PRId64 " -> %d x %d", tiles, o.stripes, o.tile_cols);
+                            const host::PopGrid big = host::pop_grid(n, P, f64, V, TC, cu, batched, 1 << 30, 1);
+                            CHECK(big.stripes >= 1 && big.stripes <= rows && big.tile_cols >= 1 && big.tile_cols <= tiles, "override 2^30 x 1");
+                            const host::PopGrid none = host::pop_grid(n, P, f64, V, TC, cu, false);
+                            for (auto &bad : {std::pair<int, int>{0, 1}, {3, 0}, {3, (int)tiles + 1}, {-2, 1}}) {
+                                const host::PopGrid i = host::pop_grid(n, P, f64, V, TC, cu, false, bad.first, bad.second);
+                                CHECK(i.stripes == none.stripes && i.tile_cols == none.tile_cols, "override %d,%d not ignored", bad.first, bad.second);
+                            }
+                        }
+            for (int64_t pairs : {1, 2, 3, 11, 21, 22, 23, 4095, 4096}) {
+                const int64_t c = host::stage_chunk_points(n, pairs);
+                CHECK(c >= 1 && c <= n && (c % 1024 == 0 || c == n), "stage_chunk_points(%" PRId64 ", %" PRId64 ") = %" PRId64, n, pairs, c);
+                CHECK(c * pairs * 16 <= host::RES_CHUNK_BYTES, "chunk of %" PRId64 " points x %" PRId64 " pairs passes the staging limit", c, pairs);
+            }
+        }
+}
+
+// RowDiv::div(e) == e / w for every row length the grid form accepts (w <= 2^16) at the indices where a magic-number division
+// fails first: around the multiples of w, spread over [0, 2^31), and at the top of the range
+void check_row_div() {
+    for (uint32_t w = 2; w <= 65536; ++w) {
+        const RowDiv rd = host::row_div(w);
+        const uint64_t mul = (((uint64_t)1 << rd.shift) + w - 1) / w;
+        if (rd.w != w || mul > 0xffffffffull || rd.mul != (uint32_t)mul) CHECK(false, "row_div(%u): mul does not fit 32 bits", w);
+        const uint32_t top = 0x7fffffffu, kmax = top / w;
+        bool ok = true;
+        for (uint32_t e : {0u, 1u, w - 1, w, w + 1, top, top - w + 1, kmax * w, kmax * w - 1}) ok &= rd.div(e) == e / w;
+        for (uint32_t k = 1; k <= kmax; k += 1 + k / 3 + (w & 7)) {          // ~40 multiples, other ones for other w
+            ok &= rd.div(k * w) == k && rd.div(k * w - 1) == k - 1;
+        }
+        if (!ok) CHECK(false, "RowDiv::div is not e / %u somewhere below 2^31", w);
+    }
+}
+
 // ------------------------------------------------------------------ the error message is per thread
 void check_errors() {
     std::vector<std::thread> th;
@@ -363,11 +428,40 @@ int canary(const char *which) {
     return 2;
 }
 
+// --plan: one query per argument, or per line of stdin when there is none: n,P,f32|f64,V,TC,cu,batched,pairs[,stripes,tile_cols]
+// (the last two: an ALP_POP_GRID pair) -> "stripes tile_cols chunk_points stream_grid confirm_grid"
+int plan_query(const char *q) {
+    long long n = 0, P = 0, pairs = 0;
+    char prec[4] = "";
+    int V = 0, TC = 0, cu = 0, batched = 0, a = 0, b = 0;
+    const int got = sscanf(q, "%lld,%lld,%3[f0-9],%d,%d,%d,%d,%lld,%d,%d", &n, &P, prec, &V, &TC, &cu, &batched, &pairs, &a, &b);
+    const bool f64 = !strcmp(prec, "f64");
+    if ((got != 8 && got != 10) || (!f64 && strcmp(prec, "f32")) || n < 0 || P < 1 || V < 1 || TC < 1 || cu < 1 || pairs < 1) {
+        fprintf(stderr, "bad plan query: %s\n", q);
+        return 2;
+    }
+    const host::PopGrid g = host::pop_grid(n, P, f64, V, TC, cu, batched != 0, a, b);
+    printf("%d %d %lld %d %d\n", g.stripes, g.tile_cols, (long long)host::stage_chunk_points(n, pairs), host::stream_grid(n, cu),
+           host::confirm_grid(n, cu));
+    return 0;
+}
+
+int plan(int argc, char **argv) {
+    for (int i = 0; i < argc; ++i)
+        if (int rc = plan_query(argv[i])) return rc;
+    char line[256];
+    while (argc == 0 && fgets(line, sizeof(line), stdin))
+        if (int rc = line[0] == '\n' ? 0 : plan_query(line)) return rc;
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc > 2 && !strcmp(argv[1], "--canary")) return canary(argv[2]);
+    if (argc > 1 && !strcmp(argv[1], "--plan")) return plan(argc - 2, argv + 2);
     struct Group { const char *name; void (*fn)(); };
     const Group groups[] = {{"hash", check_hash},     {"minmax", check_minmax},   {"prefault", check_prefault}, {"fold_pose", check_fold_pose},
-                            {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors}};
+                            {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors},
+                            {"plan", check_plan},       {"row_div", check_row_div}};
     const bool concurrent = !(argc > 1 && !strcmp(argv[1], "--serial"));
     // every group on its own caller thread at once: the library promises that independent calls may overlap
     std::vector<std::thread> th;

@@ -1,0 +1,121 @@
+// Launch planning of the point-set kernels (alp_points.hip): the stripes x tile columns of a population evaluation, the points of
+// one staged residual / Jacobian launch, the grid of a streaming kernel, the magic-number division by a grid set's row length.
+// Integer arithmetic on (n, P, precision, V, cu_count) alone; the caller allocates and launches.  Included by host/alp_host.h
+// after host/alp_fold.h (ALP_HD); no HIP header.  host/alp_host_selfcheck.cpp sweeps it (check_plan) and prints it (--plan).
+#pragma once
+
+#include <cstdint>
+
+namespace alp {
+
+// Division by the row length W of a grid point set (alp_points.hip: points_grid_detect; K1's grid form: alp_point_kernels.h).
+// q = (e * mul) >> shift equals e / W for every e < 2^31 when 1 <= W <= 2^16, with shift = 31 + ceil(log2 W) and
+// mul = ceil(2^shift / W) < 2^32: mul exceeds 2^shift / W by less than 1, so e * mul / 2^shift exceeds e / W by less than
+// e / 2^shift < 2^31 / 2^shift <= 1 / W, which never reaches the next integer (the fraction of e / W is at most (W - 1) / W).
+struct RowDiv {
+    uint32_t w = 0, shift = 0, mul = 0;          // w = 0: not a grid (K1 reads the x and y planes)
+    ALP_HD uint32_t div(uint32_t e) const { return (uint32_t)(((uint64_t)e * mul) >> shift); }
+};
+
+namespace host {
+
+inline RowDiv row_div(uint32_t w) {
+    RowDiv rd;
+    uint32_t l = 0;
+    while ((1u << l) < w) ++l;                    // ceil(log2 w)
+    rd.w = w;
+    rd.shift = 31 + l;
+    rd.mul = (uint32_t)((((uint64_t)1 << rd.shift) + w - 1) / w);
+    return rd;
+}
+
+// memory-bound streaming kernels: enough workgroups of 256 lanes to fill 256 CUs x 8, grid-stride beyond
+inline int stream_grid(int64_t items, int cu_count) {
+    const int64_t want = (items + 255) / 256;
+    const int64_t cap = (int64_t)cu_count * 8;
+    return (int)(want < 1 ? 1 : (want < cap ? want : cap));
+}
+
+// device staging of the residual and Jacobian entry points: at most RES_CHUNK_BYTES of output per launch
+constexpr int64_t RES_CHUNK_BYTES = (int64_t)256 << 20;
+// points per launch when a point stages `pairs_per_point` double2 values (alp_residuals_batch: the B poses; alp_jacobian: the D
+// targets): whole multiples of 1024 points, at least 1024, at most n
+inline int64_t stage_chunk_points(int64_t n, int64_t pairs_per_point) {
+    int64_t chunk = RES_CHUNK_BYTES / (pairs_per_point * 16) / 1024 * 1024;
+    if (chunk < 1024) chunk = 1024;
+    return chunk > n ? n : chunk;
+}
+
+// stripes of the float64 confirmation pass over a float32 set (alp_points.hip: confirm_losses): one tile column
+inline int confirm_grid(int64_t n, int cu_count) {
+    const int64_t rows = (n + 255) / 256, want = (int64_t)cu_count * 4;
+    return (int)(rows < want ? (rows > 0 ? rows : 1) : want);
+}
+
+// the multi-start launch of the device loop (`batched`) keeps its partial sums (stripes x P doubles) within this
+constexpr int64_t POP_BATCHED_PARTIALS_BYTES = (int64_t)128 << 20;
+
+// The grid of popeval_kernel: `stripes` workgroups along x, each over a run of whole rows of 256 points, times `tile_cols`
+// columns of TC candidates each along y (1: a workgroup walks every tile of its stripe).
+struct PopGrid { int stripes, tile_cols; };
+
+// n points x P candidates; V = rows of a full group of the kernel variant (PopCfg<T>::V or PopCfgLF<T>::V), TC = candidates
+// per tile; (ov_stripes, ov_tile_cols) = the parsed ALP_POP_GRID pair, 0 when absent
+inline PopGrid pop_grid(int64_t n, int64_t P, bool is_f64, int V, int TC, int cu_count, bool batched, int ov_stripes = 0,
+                        int ov_tile_cols = 0) {
+    // one workgroup per stripe of ~24 rows of 256 points (four groups of V = 6), between 4 and 64
+    // workgroups per CU: a stripe is re-read once per tile of 128 candidates and a short one stays
+    // in cache between those passes.  Measured, 100 M x 2048 float32: 4 workgroups per CU 244 ms,
+    // 8: 229, 16: 224, 32: 221, 64: 219, 128: 219; 10 M x 256: 8 per CU (stripes of 19 rows) 3.31
+    // ms, 16: 3.46, 32: 3.73.  float64 (three workgroups resident per CU): 24 per CU (round 5: 527 ms against 541 with 4).
+    int nblk = cu_count * (is_f64 ? 24 : 4), ytiles = 1;
+    const int64_t rows = (n + 255) / 256, tiles = (P + TC - 1) / TC;
+    if (!is_f64) {
+        const int64_t want = (rows + 4 * V - 1) / (4 * V);            // ~four full groups per stripe
+        const int64_t lo = (int64_t)cu_count * 4, hi = (int64_t)cu_count * 64;
+        // whole rounds of the 4 workgroups a CU holds at once while the grid is only a few rounds deep
+        const int64_t rounded = (want + lo - 1) / lo * lo;
+        nblk = (int)(want < lo ? lo : (want > hi ? hi : (want < 4 * lo ? rounded : want)));
+        // Two candidate tiles or more: the grid is stripes x tiles -- a workgroup runs ONE tile of 128 candidates over a stripe of
+        // whole groups of V rows.  Round 3 introduced it for populations of a few tiles whose one-column grid was only a few
+        // rounds deep (10 M x 256: 1954 stripes of 20 rows = 1.9 rounds of the 1024 resident workgroups, 2 rows of every 20 in
+        // the narrow groups; tools/sweep_popeval_grid.py, ms for P = 256 / 384 / 512 at 10 M points: one column of 2048 stripes
+        // 3.15 / 4.64 / 6.14; stripes of 18 rows x tiles 2.90 / 4.33 / 5.61).  Round 6 measured it at every other shape as well
+        // (profiles/r06_popeval_grid_sweep.txt, one column -> stripes x tiles, general | lens-free variant): 10 M x 1024 12.2 ->
+        // 11.0 | 5.81 -> 4.91 ms; 10 M x 2048 24.6 -> 21.7 | 11.5 -> 9.64; 30 M x 1024 34.9 -> 32.5 | 15.8 -> 14.4; 100 M x 2048
+        // 219.5 -> 215.2 | 95.7 -> 93.4 -- never slower, so it is the rule.  Stripes of k groups, k grown with the point count
+        // (about two stripes per resident slot and tile column for small sets, up to 16 groups = ~25 000 points for large ones:
+        // the timings are flat from 4 to 16 groups and the partial-sum buffer shrinks with the stripe count).
+        // The sums depend on the shape in the last bits only (up to ~3e-8 relative between shapes: other group boundaries).
+        if (tiles >= 2) {
+            int64_t k = (int64_t)((double)rows / ((double)V * 2.12 * (double)lo) + 0.5);      // groups of V rows per stripe
+            k = k < 1 ? 1 : (k > 16 ? 16 : k);
+            const int64_t stripes = (rows + V * k - 1) / (V * k);
+            if (stripes * tiles >= 4 * lo) { nblk = (int)stripes; ytiles = (int)tiles; }
+        }
+    } else {
+        // the per-stripe partial sums (nblk x P doubles, read once per generation by reduce_partials_kernel) stay below 128 MB:
+        // 24 stripes per CU at P = 2048 are 100 MB (kept: 527 ms against 533 with 8 per CU); a population of 8192 gets 2048 stripes
+        const int64_t cap = ((int64_t)128 << 20) / (8 * P);
+        const int64_t lo = (int64_t)cu_count * 3;                  // one round of the three resident workgroups per CU
+        if (nblk > cap) nblk = (int)(cap > lo ? cap : lo);
+    }
+    // tuning hook ALP_POP_GRID="stripes,ytiles".  The stripe count moves the last bits of the losses in either precision: it decides which
+    // rows go through the V-wide, the 2-wide and the masked single-row groups (float32: other group sums, up to ~3e-8 relative) and sets the
+    // ORDER of the float64 additions.  Same grid, same bits (tests/test_gpu_popeval_grid.py) -- a development switch, not a setting
+    if (ov_stripes >= 1 && ov_tile_cols >= 1 && ov_tile_cols <= tiles) { nblk = ov_stripes; ytiles = ov_tile_cols; }
+    if (rows < nblk) nblk = (int)(rows > 0 ? rows : 1);
+    if (batched) {
+        const int64_t cap = POP_BATCHED_PARTIALS_BYTES / (8 * P);
+        if (nblk > cap) nblk = (int)(cap > 1 ? cap : 1);
+        const int64_t fill = (int64_t)cu_count * 4;
+        if (ytiles == 1 && tiles >= 2 && nblk < fill) {
+            const int64_t cols = (fill + nblk - 1) / nblk;
+            ytiles = (int)(cols < tiles ? cols : tiles);
+        }
+    }
+    return {nblk, ytiles};
+}
+
+}  // namespace host
+}  // namespace alp

@@ -1,6 +1,6 @@
 """An independent restatement of the CMA-ES candidate draw (alproj_amd/csrc/alp_sampler.h) in numpy, shared by
-tests/test_cma_sampler_reference.py and tests/test_gpu_cma_limits.py, and the grid rule of the batched population launch
-(alproj_amd/csrc/alp_points.hip: popeval_launch_t with batched = true).
+tests/test_cma_sampler_reference.py and tests/test_gpu_cma_limits.py, and the grid rule of the population launch
+(alproj_amd/csrc/host/alp_plan.h: pop_grid; tests/test_launch_plan.py holds the two to each other on the CPU).
 
 The draw: philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011) with the counter
 (j >> 1, try, candidate, generation as uint32) and the key (seed low, seed high); 53-bit uniforms and Box-Muller (z[j] from cos,
@@ -116,8 +116,9 @@ BATCHED_PARTIALS_BYTES = 128 << 20
 GROUP_V = {("f32", False): 6, ("f32", True): 8, ("f64", False): 5, ("f64", True): 6}
 
 
-def batched_grid(n, R, prec, lens_free, cu):
-    """(stripes, tile columns) that popeval_launch_t picks for R candidates on n points with batched = true (no ALP_POP_GRID)"""
+def batched_grid(n, R, prec, lens_free, cu, batched=True):
+    """(stripes, tile columns) that host::pop_grid picks for R candidates on n points with batched = true (no ALP_POP_GRID);
+    batched=False: the grid of every other population launch (the rule without its last two steps)"""
     rows = -(-n // 256)
     V = GROUP_V[(prec, lens_free)]
     tiles = -(-R // POP_TC)
@@ -138,6 +139,8 @@ def batched_grid(n, R, prec, lens_free, cu):
         if nblk > cap:
             nblk = max(cap, cu * 3)
     nblk = min(nblk, max(rows, 1))
+    if not batched:
+        return nblk, ytiles
     cap = BATCHED_PARTIALS_BYTES // (8 * R)
     if nblk > cap:
         nblk = max(cap, 1)

@@ -1,5 +1,6 @@
 """Shared by tests/test_gpu_residuals.py and tests/test_gpu_jacobian.py: the launch rules of the batched residual and Jacobian
-entry points restated (alproj_amd/csrc/alp_points.hip: residuals_impl, jacobian_impl, stream_grid; alp_point_kernels.h: RES_V),
+entry points restated (alproj_amd/csrc/host/alp_plan.h: stage_chunk_points, stream_grid; alp_point_kernels.h: RES_V;
+tests/test_launch_plan.py holds the restatement and the header to each other on the CPU),
 scipy's 2-point finite-difference poses around a lens pose, seeded point sets, the bench-shaped 10 M DSM, and the float64 /
 float32 references of the residual vectors with the float32 filters and their cap."""
 import os
@@ -27,7 +28,7 @@ F32_DROP_CAP = 0.02
 
 # ------------------------------------------------------------------ launch rules
 def chunk_points(n, pairs_per_point):
-    """points per launch: residuals_impl stages B residual pairs per point, jacobian_impl D; 16 bytes each"""
+    """points per launch (stage_chunk_points): residuals_impl stages B residual pairs per point, jacobian_impl D; 16 bytes each"""
     c = max(1024, (RES_CHUNK_BYTES // (16 * pairs_per_point)) // 1024 * 1024)
     return min(c, n)
 

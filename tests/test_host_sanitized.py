@@ -1,6 +1,7 @@
 """The HIP-free host side of libalproj_hip.so (alproj_amd/csrc/host/: error state, fold_pose, the threads behind
 alp_host_hash64 / alp_host_minmax / alp_host_prefault, the grid-recognition threads of alp_mesh_create, the conversion
-workers of alp_projected_fetch, the argmin / confirmation-band selection of alp_eval_population_wait) compiled WITHOUT HIP
+workers of alp_projected_fetch, the argmin / confirmation-band selection of alp_eval_population_wait, the launch planning of
+the point-set kernels) compiled WITHOUT HIP
 and run under AddressSanitizer + UndefinedBehaviorSanitizer and under ThreadSanitizer, each in a child process.
 
 The driver (csrc/host/alp_host_selfcheck.cpp) calls every helper with sizes that straddle its thread thresholds, with 1 to
@@ -69,12 +70,13 @@ def test_library_and_sanitized_build_share_their_sources():
     """what runs under the sanitizers is what ships: the library's source list names host/alp_host.cpp, and neither it nor
     the header it shares with the .hip units includes a HIP header"""
     assert "host/alp_host.cpp" in _build.SOURCES
-    for name in ("alp_host.h", "alp_host.cpp"):
+    for name in ("alp_host.h", "alp_host.cpp", "alp_fold.h", "alp_plan.h"):
         text = open(os.path.join(_build.HOST_DIR, name)).read()
         assert "hip_runtime" not in text and "#include <hip" not in text, name
     # the moved code is gone from the HIP units: one definition each
     for unit, words in (("alp_core.hip", ("hash_slice", "MADV_POPULATE_WRITE", "void fold_pose(")),
-                        ("alp_points.hip", ("void convert_slice(", "std::thread")),
+                        ("alp_points.hip", ("void convert_slice(", "std::thread", "2.12", "RES_CHUNK_BYTES =", "RowDiv row_div(")),
+                        ("alp_internal.h", ("struct RowDiv",)),
                         ("alp_raster.hip", ("struct HostGridCheck", "void grid_rows_check("))):
         text = open(os.path.join(_build.CSRC, unit)).read()
         for w in words:
