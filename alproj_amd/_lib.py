@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("ALPROJ_HIP_LIB", os.path.join(_HERE, "libalproj_hip.s
 
 ALP_F32, ALP_F64, ALP_I32, ALP_I64, ALP_U8, ALP_U16 = 0, 1, 2, 3, 4, 5
 LOSS_MEAN_DIST, LOSS_HUBER = 0, 1
+# alp_normal_equations: scipy.optimize.least_squares' losses of one scalar residual (enum alp_normal_loss)
+NORMAL_LOSSES = {"linear": 0, "soft_l1": 1, "huber": 2, "cauchy": 3}
 NPARAM = 25
 UNIQUE_ID_BYTES = 128
 
@@ -201,6 +203,7 @@ _SIGNATURES = {
     "alp_residuals": [_c_void_p, _c_dp, _c_dp],
     "alp_residuals_batch": [_c_void_p, _c_dp, _c_i64, _c_dp],
     "alp_jacobian": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_int, _c_dp],
+    "alp_normal_equations": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_int, _c_double, _c_dp],
     "alp_eval_population": [_c_void_p, _c_dp, _c_i64, _c_int, _c_double, _c_dp, ctypes.POINTER(_c_i64)],
     "alp_eval_population_enqueue": [_c_void_p, _c_dp, _c_i64, _c_int, _c_double],
     "alp_eval_population_wait": [_c_void_p, _c_dp, ctypes.POINTER(_c_i64)],
@@ -390,6 +393,32 @@ def _same_float_columns(cols, k):
     return [np.ascontiguousarray(c, dtype=dt) for c in cols]
 
 
+def normal_loss_check(loss, f_scale):
+    """(loss code, f_scale) of alp_normal_equations; ValueError for an unknown loss or an f_scale that is not a positive finite
+    number"""
+    if loss not in NORMAL_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(NORMAL_LOSSES)}, not {loss!r}")
+    fs = float(f_scale)
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError("f_scale must be a positive finite number")
+    return NORMAL_LOSSES[loss], fs
+
+
+def normal_targets_check(target_idx):
+    """the int32 target indices of alp_normal_equations / an exact Jacobian; ValueError for none or more than 23, one out of
+    range, w / h or a repeated one (the one statement of the rule on the Python side: optimize._jacobian_targets calls it)"""
+    idx = np.ascontiguousarray(np.asarray(target_idx).reshape(-1), dtype=np.int32)
+    if not 1 <= len(idx) <= NPARAM - 2:
+        raise ValueError("1 to 23 targets are needed")
+    if ((idx < 0) | (idx >= NPARAM)).any():
+        raise ValueError("a target index lies outside the 25 parameters")
+    if np.isin(idx, [PARAM_KEYS.index("w"), PARAM_KEYS.index("h")]).any():
+        raise ValueError("w and h cannot be targets (they are image sizes, not fitted)")
+    if len(set(idx.tolist())) != len(idx):
+        raise ValueError("the targets must be distinct")
+    return idx
+
+
 class Points:
     """Device-resident point set (RAII wrapper of alp_points_t)."""
 
@@ -512,6 +541,28 @@ class Points:
         check(self._lib.alp_jacobian(self._h, as_dp(pvec), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx),
                                      int(bool(of_residuals)), as_dp(out)))
         return out
+
+    def normal_equations(self, pvec, target_idx, loss="linear", f_scale=1.0):
+        """-> (G (D, D) symmetric, g (D,), cost, n): the normal equations of the least-squares problem at ``pvec``, formed on
+        the device (alp_normal_equations).  G = J^T J and g = J^T r with J, r the Jacobian and the residual vector
+        observed - projected, scaled row by row for the robust ``loss`` ("linear", "soft_l1", "huber", "cauchy" with scipy's
+        meaning and ``f_scale``); cost = scipy's 0.5 f_scale^2 sum rho; n = the point count.  With a communicator all four are
+        the sums over the ranks.  ValueError, before the library is called, for an unknown loss, f_scale <= 0 or not finite,
+        w / h, an index out of range or a repeated target."""
+        idx = normal_targets_check(target_idx)
+        kind, fs = normal_loss_check(loss, f_scale)
+        pvec = np.ascontiguousarray(pvec, dtype=np.float64)
+        if pvec.shape != (NPARAM,):
+            raise ValueError("pvec must have shape (25,)")
+        d = len(idx)
+        tri = d * (d + 1) // 2
+        out = np.empty(tri + d + 2, dtype=np.float64)
+        check(self._lib.alp_normal_equations(self._h, as_dp(pvec), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), d, kind, fs,
+                                             as_dp(out)))
+        G = np.zeros((d, d), dtype=np.float64)
+        G[np.triu_indices(d)] = out[:tri]
+        G = G + np.triu(G, 1).T
+        return G, out[tri:tri + d].copy(), 0.5 * fs * fs * float(out[tri + d]), int(out[tri + d + 1])
 
     def eval_population(self, cand, loss_kind, f_scale=10.0, want_argmin=True):
         """-> (losses (P,), argmin).  ``want_argmin=False``: losses only -- the library then skips the float64 confirmation

@@ -691,6 +691,150 @@ __global__ __launch_bounds__(256) void jacobian_kernel(const TS *__restrict__ x,
     }
 }
 
+// ------------------------------------------------------------------ K3n: the normal equations J^T J, J^T r, sum rho
+// K3j's rows contracted where they are made instead of stored: a lane takes a point, forms the point's two augmented rows
+// [s J_row | r_scaled] (M = D + 1 <= 24 values each; s and the scaling of r: scipy's scale_for_robust_loss_function) and the
+// wave accumulates the Gram matrix of its rows with v_mfma_f64_16x16x4_f64.  Nothing of size O(n) is written anywhere.
+//
+// The tile.  A wave owns NRM_ROWS = 64 rows of LDS at a time, stored column-major: value c of row k at tile[c * NRM_RS + k],
+// so that the 64 lanes' writes of one column are one contiguous run.  The MFMA wants, in lane l, A[i = l & 15][k = l >> 4]
+// and B[k = l >> 4][j = l & 15] (the f32 16x16x4 operand map, one f64 per lane) -- for a Gram matrix both are
+// R[k0 + (l >> 4)][16 b + (l & 15)] of column block b, ONE ds_read_b64 per block and k-step: the diagonal blocks 00 and 11
+// take the same register as A and B, block 01 takes block 0's as A and block 1's as B.  NRM_RS = 66 doubles = 132 dwords = 4
+// mod 64: a ds_read_b64 is served in the lane groups 0..31 and 32..63 over 64 dword banks, and the lanes of a group (16 columns
+// x 2 consecutive rows) start at bank 4 c + 2 (k & 1) + const -- 32 distinct pairs of banks, no conflict (a stride of 68
+// doubles = 8 mod 64 dwords put columns c and c + 8 on the same banks).  M <= 16: block 00 alone.  Columns at or past M: the
+// lane reads column M - 1 again; what that yields lands in rows / columns of the result nobody reads (an element of D depends
+// on its own row of A and column of B alone).  The u rows of the wave's 64 points go through the tile first, then their v rows: 2 x 16 k-steps.
+// C / D of the f64 form: lane l, register e holds D[(l >> 4) + 4 e][l & 15] (NOT the f32 row map).
+//
+// Order of the additions, fixed by the launch shape alone: a wave walks the groups of its workgroup's stripe in index order,
+// inside a group the u rows then the v rows of its 64 points, k ascending; the four waves of a workgroup are added in wave
+// order; every workgroup writes one row of partials -- in the layout of alp_normal_equations' `out` less its last value --
+// and reduce_partials_kernel adds the rows.  No atomics.  A masked lane (past the end of the set) contributes exact zeros.
+constexpr int NRM_ROWS = 64;
+constexpr int NRM_RS = 66;
+constexpr int NRM_MAXM = JAC_MAX + 1;
+constexpr int NRM_TILE = NRM_MAXM * NRM_RS;         // doubles per wave: 12 672 bytes, 50 KB per workgroup
+static_assert(NRM_TILE >= 32 * 32, "a wave's 32 x 32 result is parked in its tile");
+typedef double nrm_v4d __attribute__((ext_vector_type(4)));
+
+// scipy's rho(z) and the two row scalings: *s = sqrt(max(rho' + 2 z rho'', 1e-10)), *w = rho' / *s
+template <int LOSS>
+__device__ __forceinline__ double normal_rho(double z, double &s, double &w) {
+    double rho, d1, d2;
+    if constexpr (LOSS == ALP_NORMAL_LINEAR) {
+        s = 1.0; w = 1.0;
+        return z;
+    } else if constexpr (LOSS == ALP_NORMAL_SOFT_L1) {
+        const double t = 1.0 + z, q = __builtin_sqrt(t);
+        rho = 2.0 * (q - 1.0); d1 = 1.0 / q; d2 = -0.5 / (t * q);
+    } else if constexpr (LOSS == ALP_NORMAL_HUBER) {
+        const double q = __builtin_sqrt(z);
+        const bool in = z <= 1.0;
+        rho = in ? z : 2.0 * q - 1.0;
+        d1 = in ? 1.0 : 1.0 / q;
+        d2 = in ? 0.0 : -0.5 / (z * q);
+    } else {
+        const double t = 1.0 + z;
+        rho = log1p(z); d1 = 1.0 / t; d2 = -1.0 / (t * t);
+    }
+    const double a = d1 + 2.0 * z * d2;
+    s = __builtin_sqrt(a > 1e-10 ? a : (a == a ? 1e-10 : a));       // max(a, 1e-10); NaN stays NaN
+    w = d1 / s;
+    return rho;
+}
+
+template <typename TS, int LOSS>
+__global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+                                                     const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
+                                                     int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plan,
+                                                     double *__restrict__ partials) {
+    __shared__ double s_tile[4][NRM_TILE];
+    __shared__ double s_cost[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int D = plan->D, M = D + 1;
+    const bool two = M > 16;                          // wave-uniform: a second column block
+    double *tile = s_tile[wave];
+    const int kq = lane >> 4;
+    const int c0 = (lane & 15) < M ? (lane & 15) : M - 1;
+    const int c1 = 16 + (lane & 15) < M ? 16 + (lane & 15) : M - 1;
+    const double *rd0 = tile + c0 * NRM_RS + kq, *rd1 = tile + c1 * NRM_RS + kq;
+    nrm_v4d a00 = {0, 0, 0, 0}, a01 = {0, 0, 0, 0}, a11 = {0, 0, 0, 0};
+    double cost = 0.0;
+
+    const int64_t beg = (int64_t)blockIdx.x * groups_per * 256;
+    const int64_t end = (beg + groups_per * 256 < n) ? beg + groups_per * 256 : n;
+    for (int64_t base = beg; base < end; base += 256) {
+        const int64_t i = base + tid;
+        const bool ok = i < end;
+        const int64_t k = ok ? i : base;              // a group's first point always exists
+        const double qx = (double)x[k], qy = (double)y[k], qz = (double)z[k];
+        // the residuals: K3's float64 arithmetic (project_norm / to_pixels on the plan's record = fold_pose's)
+        double xd, yd, pu, pv;
+        project_norm<double>(plan->rec, qx, qy, qz, xd, yd);
+        to_pixels<double>(plan->rec, xd, yd, pu, pv);
+        const double r[2] = {(double)uo[k] - pu, (double)vo[k] - pv};
+        JacPoint P;
+        jac_point(plan, qx, qy, qz, P);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {                 // the u rows of the wave's 64 points, then their v rows
+            const double t = r[h] * inv_f_scale;
+            double s, w;
+            const double rho = normal_rho<LOSS>(t * t, s, w);
+            cost += ok ? rho : 0.0;
+            for (int m = 0; m < D; ++m) tile[m * NRM_RS + lane] = ok ? s * jac_value(plan, P, h * D + m) : 0.0;
+            tile[D * NRM_RS + lane] = ok ? w * r[h] : 0.0;
+            __builtin_amdgcn_wave_barrier();          // the tile is the wave's own; LDS serves a wave in order
+            if (two) {
+#pragma unroll 4
+                for (int k0 = 0; k0 < NRM_ROWS; k0 += 4) {
+                    const double f0 = rd0[k0], f1 = rd1[k0];
+                    a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, f0, a00, 0, 0, 0);
+                    a01 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, f1, a01, 0, 0, 0);
+                    a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(f1, f1, a11, 0, 0, 0);
+                }
+            } else {
+#pragma unroll 4
+                for (int k0 = 0; k0 < NRM_ROWS; k0 += 4) {
+                    const double f0 = rd0[k0];
+                    a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, f0, a00, 0, 0, 0);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    // park the wave's result as a 32 x 32 row-major matrix in its tile (blocks 00, 01, 11; the rest is never read)
+    cost = wave_sum_to_lane63(cost);
+    if (lane == 63) s_cost[wave] = cost;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int row = kq + 4 * e, col = lane & 15;
+        tile[row * 32 + col] = a00[e];
+        tile[row * 32 + 16 + col] = a01[e];
+        tile[(16 + row) * 32 + 16 + col] = a11[e];
+    }
+    __syncthreads();
+    const int tri = D * (D + 1) / 2, T = tri + D + 1;
+    for (int t = tid; t < T; t += 256) {
+        double v;
+        if (t == T - 1) {
+            v = ((s_cost[0] + s_cost[1]) + s_cost[2]) + s_cost[3];
+        } else {
+            int row = 0, col = t;
+            if (t < tri) {
+                while (col >= D - row) { col -= D - row; ++row; }      // row-major upper triangle: row `row` holds D - row values
+                col += row;
+            } else {
+                row = t - tri; col = D;                                 // J^T r: column D of the augmented Gram matrix
+            }
+            const int o = row * 32 + col;
+            v = ((s_tile[0][o] + s_tile[1][o]) + s_tile[2][o]) + s_tile[3][o];
+        }
+        partials[(int64_t)blockIdx.x * T + t] = v;
+    }
+}
+
 // TS = element type of the planes in HBM, T = arithmetic type (TS = float with T = double is the
 // float64 re-evaluation of a float32 point set: alp_eval_population's argmin confirmation)
 template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, typename TS = T, bool EXACT_POLES = false, bool LENS_FREE = false>

@@ -4,6 +4,7 @@
 //                    (VALU-bound; candidates staged in LDS, wave64 DPP reductions)
 //   residual_batch_kernel  observed - projected for B poses, interleaved (least-squares path)
 //   jacobian_kernel  d projected / d parameters for one pose, exact (least-squares path)
+//   normal_kernel    the same rows contracted to J^T J, J^T r and the cost where they are made (f64 MFMA; least-squares path)
 //
 // Reference arithmetic: src/alproj/optimize.py  project :122-155, _distort :98-120,
 // rmse :157-178, huber_loss :181-212, compute_residuals :215-237, and the generation loop
@@ -15,7 +16,7 @@
 // element type T (float: 20 B/vertex streamed per projection pass; double: 40 B/vertex).
 // Planes are padded to a multiple of 1024 elements so that 16-byte vector accesses and
 // whole-workgroup tiles never leave the allocation.
-// The launch shapes (popeval_kernel's stripes x tiles, the residual / Jacobian chunks, streaming grids, RowDiv) are planned in
+// The launch shapes (popeval_kernel's stripes x tiles, the residual / Jacobian chunks, normal_kernel's stripes, streaming grids, RowDiv) are planned in
 // host/alp_plan.h, HIP-free and checked on the CPU; this unit allocates, records events and launches what it plans.
 #include "alp_internal.h"
 
@@ -422,6 +423,38 @@ int jacobian_impl(alp_points *p, const JacPlan &plan, double *out) {
     });
 }
 
+// alp_normal_equations: normal_kernel over host::normal_grid's stripes, reduce_partials_kernel over its rows, one all-reduce.
+// The scratch holds the plan, the partial rows and the T + 1 sums; T + 1 doubles cross PCIe.
+template <typename TS>
+int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, double *out) {
+    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, double *);
+    static const Kernel kernels[4] = {normal_kernel<TS, ALP_NORMAL_LINEAR>, normal_kernel<TS, ALP_NORMAL_SOFT_L1>,
+                                      normal_kernel<TS, ALP_NORMAL_HUBER>, normal_kernel<TS, ALP_NORMAL_CAUCHY>};
+    const int D = plan.D, T = D * (D + 1) / 2 + D + 1;
+    const host::NormalGrid g = host::normal_grid(p->n, ctx().cu_count);
+    const size_t plan_bytes = round_up((int64_t)sizeof(JacPlan), 256);
+    char *dev = nullptr;
+    if (int rc = scratch_reserve(plan_bytes + ((size_t)g.blocks * T + T + 1) * sizeof(double), (void **)&dev)) return rc;
+    JacPlan *plan_dev = (JacPlan *)dev;
+    double *partials = (double *)(dev + plan_bytes), *sums = partials + (size_t)g.blocks * T;
+    hipStream_t st = ctx().stream;
+    if (g.blocks > 0) {
+        ALP_HIP(hipMemcpyAsync(plan_dev, &plan, sizeof(JacPlan), hipMemcpyHostToDevice, st));
+        ktime_begin();
+        hipLaunchKernelGGL(kernels[loss], dim3(g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z,
+                           (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plan_dev, partials);
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((T + 31) / 32)), dim3(256), 0, st, partials, g.blocks, T, (double)p->n, sums);
+        ktime_end();
+        ALP_HIP(hipGetLastError());
+    } else {
+        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)(T + 1) * sizeof(double), st));      // an empty shard still joins the all-reduce
+    }
+    if (int rc = comm_allreduce_sum_f64(sums, T + 1)) return rc;
+    ALP_HIP(hipMemcpyAsync(out, sums, (size_t)(T + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    ALP_HIP(hipStreamSynchronize(st));           // the plan (stack) must outlive its copy too
+    return ALP_OK;
+}
+
 }  // namespace
 
 namespace alp {
@@ -701,6 +734,18 @@ int alp_jacobian(alp_points_t *p, const double params[ALP_NPARAM], const int32_t
     if (p->n == 0) return ALP_OK;
     ALP_REQUIRE(out, "out is NULL");
     return p->precision == ALP_F64 ? jacobian_impl<double>(p, plan, out) : jacobian_impl<float>(p, plan, out);
+}
+
+int alp_normal_equations(alp_points_t *p, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int loss, double f_scale,
+                         double *out) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p && params && out, "NULL argument");
+    ALP_REQUIRE(loss >= ALP_NORMAL_LINEAR && loss <= ALP_NORMAL_CAUCHY, "unknown loss");
+    ALP_REQUIRE(f_scale > 0 && std::isfinite(f_scale), "f_scale must be a positive finite number");
+    JacPlan plan;
+    if (int rc = jacobian_plan(params, p->origin, target_idx, D, 1, &plan)) return rc;
+    if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations: observed uv not set");
+    return p->precision == ALP_F64 ? normal_impl<double>(p, plan, loss, f_scale, out) : normal_impl<float>(p, plan, loss, f_scale, out);
 }
 
 // obs_b / prj_b NULL: that array is interleaved (n x 2 row-major); else a = the u column, b = the v column

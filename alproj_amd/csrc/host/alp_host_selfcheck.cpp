@@ -363,7 +363,22 @@ void check_plan() {
                 CHECK(c >= 1 && c <= n && (c % 1024 == 0 || c == n), "stage_chunk_points(%" PRId64 ", %" PRId64 ") = %" PRId64, n, pairs, c);
                 CHECK(c * pairs * 16 <= host::RES_CHUNK_BYTES, "chunk of %" PRId64 " points x %" PRId64 " pairs passes the staging limit", c, pairs);
             }
+            // normal_grid: the stripes cover every group exactly once, no workgroup is empty, the partial rows stay within the cap
+            const host::NormalGrid ng = host::normal_grid(n, cu);
+            CHECK(ng.blocks >= 1 && ng.blocks <= host::NORMAL_MAX_BLOCKS && ng.blocks <= (int64_t)cu * host::NORMAL_WG_PER_CU && ng.groups_per >= 1,
+                  "normal_grid(%" PRId64 ", %d) = %d x %" PRId64, n, cu, ng.blocks, ng.groups_per);
+            CHECK((int64_t)ng.blocks * ng.groups_per >= rows && (int64_t)(ng.blocks - 1) * ng.groups_per < rows,
+                  "normal_grid(%" PRId64 ", %d) = %d x %" PRId64 " does not tile %" PRId64 " groups", n, cu, ng.blocks, ng.groups_per, rows);
+            int64_t covered = 0;
+            for (int b = 0; b < ng.blocks; ++b) {            // the kernel's own stripe arithmetic
+                const int64_t beg = (int64_t)b * ng.groups_per * 256, end = std::min<int64_t>(beg + ng.groups_per * 256, n);
+                CHECK(beg == covered && end > beg, "normal_grid(%" PRId64 ", %d): stripe %d is [%" PRId64 ", %" PRId64 ")", n, cu, b, beg, end);
+                covered = end;
+            }
+            CHECK(covered == n, "normal_grid(%" PRId64 ", %d) covers %" PRId64 " points", n, cu, covered);
         }
+    const host::NormalGrid none = host::normal_grid(0, 256);
+    CHECK(none.blocks == 0 && none.groups_per == 0, "normal_grid(0) launches %d workgroups", none.blocks);
 }
 
 // RowDiv::div(e) == e / w for every row length the grid form accepts (w <= 2^16) at the indices where a magic-number division
@@ -429,8 +444,20 @@ int canary(const char *which) {
 }
 
 // --plan: one query per argument, or per line of stdin when there is none: n,P,f32|f64,V,TC,cu,batched,pairs[,stripes,tile_cols]
-// (the last two: an ALP_POP_GRID pair) -> "stripes tile_cols chunk_points stream_grid confirm_grid"
+// (the last two: an ALP_POP_GRID pair) -> "stripes tile_cols chunk_points stream_grid confirm_grid";
+// normal,n,cu -> "blocks groups_per" of normal_grid
 int plan_query(const char *q) {
+    if (!strncmp(q, "normal,", 7)) {
+        long long nn = -1;
+        int ncu = 0;
+        if (sscanf(q + 7, "%lld,%d", &nn, &ncu) != 2 || nn < 0 || ncu < 1) {
+            fprintf(stderr, "bad plan query: %s\n", q);
+            return 2;
+        }
+        const host::NormalGrid g = host::normal_grid(nn, ncu);
+        printf("%d %lld\n", g.blocks, (long long)g.groups_per);
+        return 0;
+    }
     long long n = 0, P = 0, pairs = 0;
     char prec[4] = "";
     int V = 0, TC = 0, cu = 0, batched = 0, a = 0, b = 0;

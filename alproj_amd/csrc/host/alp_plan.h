@@ -1,5 +1,6 @@
 // Launch planning of the point-set kernels (alp_points.hip): the stripes x tile columns of a population evaluation, the points of
-// one staged residual / Jacobian launch, the grid of a streaming kernel, the magic-number division by a grid set's row length.
+// one staged residual / Jacobian launch, the stripes of the normal-equations kernel, the grid of a streaming kernel, the
+// magic-number division by a grid set's row length.
 // Integer arithmetic on (n, P, precision, V, cu_count) alone; the caller allocates and launches.  Included by host/alp_host.h
 // after host/alp_fold.h (ALP_HD); no HIP header.  host/alp_host_selfcheck.cpp sweeps it (check_plan) and prints it (--plan).
 #pragma once
@@ -115,6 +116,25 @@ inline PopGrid pop_grid(int64_t n, int64_t P, bool is_f64, int V, int TC, int cu
         }
     }
     return {nblk, ytiles};
+}
+
+// The grid of normal_kernel (alp_normal_equations): `blocks` workgroups, each over a stripe of `groups_per` whole groups of 256
+// points (the last stripe may be shorter and its last group ragged); every workgroup writes ONE row of partial sums.
+// Workgroups: NORMAL_WG_PER_CU per CU -- two rounds of the three a CU holds at once (50 KB of LDS each) -- and never more than
+// NORMAL_MAX_BLOCKS, which keeps the partial rows (at most 300 doubles each) below 5 MB whatever the device.  The stripes are
+// then made as long as they must be and the workgroups that would be left without a group are not launched.  n = 0: no launch.
+constexpr int NORMAL_WG_PER_CU = 6;
+constexpr int NORMAL_MAX_BLOCKS = 2048;
+struct NormalGrid { int blocks; int64_t groups_per; };
+
+inline NormalGrid normal_grid(int64_t n, int cu_count) {
+    const int64_t groups = (n + 255) / 256;
+    if (groups <= 0) return {0, 0};
+    int64_t want = (int64_t)cu_count * NORMAL_WG_PER_CU;
+    if (want > NORMAL_MAX_BLOCKS) want = NORMAL_MAX_BLOCKS;
+    if (want > groups) want = groups;
+    const int64_t per = (groups + want - 1) / want;
+    return {(int)((groups + per - 1) / per), per};
 }
 
 }  // namespace host

@@ -11,8 +11,8 @@ here                          reference                                device en
 ``compute_residuals``         optimize.py:215-237                      alp_residuals
 ``bounds_to_array``           optimize.py:249-276                      (host, D <= 21 scalars)
 ``CMAOptimizer.optimize``     optimize.py:359-439                      alp_eval_population, alp_cma_*
-``LsqOptimizer.optimize``     optimize.py:467-539                      alp_residuals
-``parameter_covariance``      (none: standard errors of a fit)         alp_jacobian, alp_residuals
+``LsqOptimizer.optimize``     optimize.py:467-539                      alp_residuals; method="normal": alp_normal_equations
+``parameter_covariance``      (none: standard errors of a fit)         alp_jacobian, alp_residuals; "normal": alp_normal_equations
 ``intrinsic_mat`` etc.        optimize.py:8-96                         (host, 3x3 / 4x4)
 ============================  =======================================  ======================
 
@@ -38,7 +38,7 @@ from .cma import CMA
 
 __all__ = ["intrinsic_mat", "extrinsic_mat", "project", "rmse", "huber_loss",
            "compute_residuals", "DEFAULT_BOUND_WIDTHS", "bounds_to_array", "BaseOptimizer",
-           "CMAOptimizer", "LsqOptimizer", "start_seeds", "best_start"]
+           "CMAOptimizer", "LsqOptimizer", "start_seeds", "best_start", "normal_lm"]
 
 
 # ------------------------------------------------------------------------------------------
@@ -221,25 +221,45 @@ def _jacobian_targets(target_params):
     an unknown key or a repeated one"""
     targets = list(target_params)
     for t in targets:
-        if t in ("w", "h"):
-            raise ValueError(f"{t!r} cannot be a target of the exact Jacobian (w and h are image sizes, not fitted)")
         if t not in _lib.PARAM_KEYS:
             raise ValueError(f"unknown parameter {t!r}")
-    if len(set(targets)) != len(targets):
-        raise ValueError("the targets of the exact Jacobian must be distinct")
-    if not 1 <= len(targets) <= _lib.NPARAM - 2:
-        raise ValueError("the exact Jacobian needs 1 to 23 targets")
-    return np.array([_lib.PARAM_KEYS.index(t) for t in targets], dtype=np.int32)
+    return _lib.normal_targets_check([_lib.PARAM_KEYS.index(t) for t in targets])
 
 
-def parameter_covariance(obj_points, img_points, params, target_params):
+def _covariance_from_normal_equations(G, rtr, m):
+    """s^2 G^-1 from the eigendecomposition of the Jacobi-scaled G (unit diagonal), s^2 = rtr / (m - D); inf when the scaled
+    matrix is rank-deficient by numpy's matrix_rank rule (its smallest eigenvalue <= D eps times its largest) or a column of
+    J is zero"""
+    d = G.shape[0]
+    dg = np.sqrt(np.diag(G))
+    if not (dg > 0).all():
+        return np.full((d, d), np.inf)
+    lam, V = np.linalg.eigh(G / np.outer(dg, dg))
+    if lam[0] <= d * np.finfo(np.float64).eps * lam[-1]:
+        return np.full((d, d), np.inf)
+    return (V / lam) @ V.T * (rtr / (m - d)) / np.outer(dg, dg)
+
+
+def parameter_covariance(obj_points, img_points, params, target_params, method="svd"):
     """Covariance and standard errors of the camera parameters ``target_params`` fitted to the GCPs, at ``params``:
     ``cov`` = s^2 (J^T J)^-1 with s^2 = r^T r / (2N - D), J the exact (2N, D) Jacobian of the residual vector r (one
     ``alp_jacobian`` and one ``alp_residuals`` call on a float64 point set), formed from the SVD of J.  Returns
     ``(cov, std)`` with ``std = {target: sqrt(cov[j, j])}``.  When J is rank-deficient to working precision (a singular
     value <= max(2N, D) eps sigma_max, numpy's matrix_rank rule) the targets cannot all be determined from these GCPs:
     ``cov`` and ``std`` are inf.  With several ranks J and r are gathered first: every rank returns the same numbers.
-    ValueError for w / h or repeated targets, or for 2N <= D."""
+    ValueError for w / h or repeated targets, or for 2N <= D.
+
+    ``method="normal"`` (opt-in) never forms J: one ``alp_normal_equations`` call with the linear loss returns J^T J, r^T r
+    and the point count, summed over the ranks on the device -- (D + 1)(D + 2) / 2 + 1 doubles cross PCIe instead of the
+    (2N, D) matrix, and nothing is gathered.  ``cov`` then comes from the eigendecomposition of J^T J scaled to a unit
+    diagonal, and rank deficiency is numpy's matrix_rank rule applied to THAT D x D matrix: lambda_min <= D eps lambda_max.
+    This rule sees the SQUARED condition number of the column-scaled J -- the eigenvalues of J^T J are the squares of J's
+    singular values -- so it declares deficiency earlier than the SVD of J does (at a condition number of about
+    1 / sqrt(D eps) ~ 1e7 instead of 1 / (2N eps)), and the entries of ``cov`` carry a relative error of about the squared
+    condition number times eps instead of the condition number times eps.  That is why ``"svd"`` stays the default: choose
+    ``"normal"`` for point sets whose Jacobian is too large to move, with targets that are well determined."""
+    if method not in ("svd", "normal"):
+        raise ValueError("method must be 'svd' or 'normal'")
     targets = list(target_params)
     cols = _jacobian_targets(targets)
     xyz = _xyz_array(obj_points)
@@ -249,8 +269,19 @@ def parameter_covariance(obj_points, img_points, params, target_params):
     pvec = _lib.params_vector(params)
     with _points(xyz, _camera_origin(params), "f64") as pts:
         _set_observed(pts, _uv_array(img_points))
-        J = pts.jacobian(pvec, cols, of_residuals=True)
-        r = pts.residuals(pvec)
+        if method == "normal":
+            G, _, cost, n_total = pts.normal_equations(pvec, cols, "linear", 1.0)
+        else:
+            J = pts.jacobian(pvec, cols, of_residuals=True)
+            r = pts.residuals(pvec)
+    if method == "normal":
+        m, d = 2 * n_total, len(targets)
+        if m <= d:
+            raise ValueError(f"{m} residuals: not more than the {d} targets")
+        if not (np.isfinite(G).all() and np.isfinite(cost)):
+            raise ValueError("the residuals or their Jacobian are not finite at these parameters")
+        cov = _covariance_from_normal_equations(G, 2.0 * cost, m)
+        return cov, {t: float(np.sqrt(cov[j, j])) for j, t in enumerate(targets)}
     if world > 1:
         J, r = _lib.comm_allgather(J), _lib.comm_allgather(r)
     m, d = J.shape
@@ -490,10 +521,106 @@ class CMAOptimizer(BaseOptimizer):
     F64_FINAL_MAX_POINTS = F64_MAX_POINTS
 
 
+def normal_lm(fun, x0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None):
+    """Bounded Levenberg-Marquardt on the normal equations.  ``fun(x) -> (G, g, cost)``: G = J^T J (D, D), g = J^T r (D,),
+    cost = the objective (0.5 r^T r for the linear loss), all at x -- ``Points.normal_equations`` on the device, or any
+    oracle.  Minimises cost over lower <= x <= upper (either may be infinite).
+
+    Damping (Nielsen): mu_0 = 1e-3 max diag G; an accepted step with gain ratio rho = actual / predicted reduction gives
+    mu *= max(1/3, 1 - (2 rho - 1)^3), nu = 2; a failed one mu *= nu, nu *= 2.  The damping matrix is
+    mu diag(scale^2) / max(scale^2) with scale the running maximum of sqrt(diag G) (Marquardt's scaling, kept monotone).
+    Solve: Cholesky of the damped matrix scaled to a unit diagonal; a factorisation that fails is a failed step.
+    Bounds: a variable on a bound whose gradient pushes outward is left out of the solve for that iteration; the trial point
+    is clipped into the box and the predicted reduction is that of the clipped step.
+    A step is accepted only when the new cost is finite and smaller.
+    Stopping, with scipy.optimize.least_squares' names and status codes: 1 ``gtol`` (the infinity norm of g over the free
+    variables), 2 ``ftol`` (actual reduction < ftol * cost on a step with rho > 0.25), 3 ``xtol`` (|step| < xtol (xtol + |x|)),
+    4 both, 0 ``max_nfev`` evaluations (default 100 D), -1 the cost at x0 is not finite.
+
+    Returns a dict: x, cost, grad_norm, iterations (accepted steps), evaluations, status."""
+    x = np.clip(np.asarray(x0, dtype=np.float64), lower, upper)
+    lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    d = len(x)
+    max_nfev = 100 * d if max_nfev is None else int(max_nfev)
+    G, g, cost = fun(x)
+    nfev, iterations, status = 1, 0, None
+
+    def free_of(x, g):
+        return ~(((x <= lower) & (g > 0)) | ((x >= upper) & (g < 0)))
+
+    if not (np.isfinite(cost) and np.isfinite(G).all() and np.isfinite(g).all()):
+        return dict(x=x, cost=float(cost), grad_norm=float("nan"), iterations=0, evaluations=1, status=-1)
+    scale = np.sqrt(np.diag(G))
+    mu, nu = 1e-3 * float(np.max(np.diag(G))), 2.0
+    if not mu > 0:
+        mu = 1e-3
+    while True:
+        free = free_of(x, g)
+        g_norm = float(np.max(np.abs(g[free]))) if free.any() else 0.0
+        if g_norm < gtol:
+            status = 1
+            break
+        if nfev >= max_nfev:
+            status = 0
+            break
+        scale = np.maximum(scale, np.sqrt(np.diag(G)))
+        s2 = scale[free] ** 2
+        top = float(np.max(scale ** 2))
+        A = G[np.ix_(free, free)] + np.diag(mu * (s2 / top if top > 0 else np.ones_like(s2)))
+        step = np.zeros(d)
+        ok = False
+        dA = np.diag(A)
+        if (dA > 0).all():
+            j = 1.0 / np.sqrt(dA)
+            try:
+                L = np.linalg.cholesky(A * np.outer(j, j))
+                delta = -j * np.linalg.solve(L.T, np.linalg.solve(L, j * g[free]))
+                ok = bool(np.isfinite(delta).all())
+            except np.linalg.LinAlgError:
+                ok = False
+        predicted = -1.0
+        if ok:
+            step[free] = delta
+            x_new = np.clip(x + step, lower, upper)
+            step = x_new - x
+            predicted = -(float(g @ step) + 0.5 * float(step @ G @ step))
+        if not ok or not predicted > 0:
+            # no usable step at this damping.  Once mu dwarfs G, the step is -g / mu scaled: when even that is below xtol, stop
+            if ok and np.linalg.norm(step) < xtol * (xtol + np.linalg.norm(x)):
+                status = 3
+                break
+            mu, nu = mu * nu, nu * 2.0
+            if not np.isfinite(mu):
+                status = 3
+                break
+            continue
+        G_new, g_new, cost_new = fun(x_new)
+        nfev += 1
+        actual = cost - cost_new
+        step_norm, x_norm = float(np.linalg.norm(step)), float(np.linalg.norm(x))
+        accepted = bool(np.isfinite(cost_new) and np.isfinite(G_new).all() and np.isfinite(g_new).all() and cost_new < cost)
+        ratio = actual / predicted if accepted else -1.0
+        f_stop = accepted and actual < ftol * cost and ratio > 0.25
+        x_stop = step_norm < xtol * (xtol + x_norm)
+        if accepted:
+            x, G, g, cost = x_new, G_new, g_new, float(cost_new)
+            iterations += 1
+            mu, nu = mu * max(1.0 / 3.0, 1.0 - (2.0 * ratio - 1.0) ** 3), 2.0
+        else:
+            mu, nu = mu * nu, nu * 2.0
+        if f_stop or x_stop:
+            status = 4 if (f_stop and x_stop) else (2 if f_stop else 3)
+            break
+    free = free_of(x, g)
+    return dict(x=x, cost=float(cost), grad_norm=float(np.max(np.abs(g[free]))) if free.any() else 0.0,
+                iterations=iterations, evaluations=nfev, status=status)
+
+
 class LsqOptimizer(BaseOptimizer):
     """scipy.optimize.least_squares driver (reference optimize.py:442-539); the residual
     vector of every trial point comes from ``alp_residuals`` on a float64 point set, and with
-    ``jac="analytic"`` its exact Jacobian from ``alp_jacobian``.
+    ``jac="analytic"`` its exact Jacobian from ``alp_jacobian``.  ``method="normal"`` solves on the normal equations the
+    device forms (``alp_normal_equations``) instead, for point sets whose residual vector and Jacobian are too large to move.
 
     Several ranks (points sharded, one process per GPU): the reference solves ONE problem over all points
     (optimize.py:510-528), so every rank all-gathers the residual vector -- and the rows of the batched Jacobian -- of
@@ -551,10 +678,49 @@ class LsqOptimizer(BaseOptimizer):
 
         return _jac
 
+    def _optimize_normal(self, bound_widths, loss, f_scale, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None, precision=None,
+                         **kwargs):
+        """optimize(method="normal"); every refusal comes before the device is touched"""
+        if "jac" in kwargs:
+            raise ValueError("method='normal' takes no jac=: it solves on J^T J and J^T r, no Jacobian exists in it")
+        if kwargs:
+            raise TypeError(f"method='normal' got unexpected keyword arguments {sorted(kwargs)}")
+        cols = _jacobian_targets(self.target_params)
+        _lib.normal_loss_check(loss, f_scale)
+        bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
+        pts = self._device_points(precision)
+        try:
+            def sums(values):
+                return pts.normal_equations(self._candidate_matrix(values)[0], cols, loss, f_scale)[:3]
+
+            res = normal_lm(sums, self.target_params_init, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol,
+                            max_nfev=max_nfev)
+            # every rank has run the same iteration on the same all-reduced sums; rank 0's solution is broadcast before the
+            # final error, a collective over the shards, as for the other methods
+            best = np.ascontiguousarray(res["x"], dtype=np.float64)
+            _, world = _lib.comm_info()
+            if world > 1:
+                _lib.comm_bcast(best, root=0)
+            err, _ = pts.eval_population(self._candidate_matrix(best), _lib.LOSS_MEAN_DIST, 0.0)
+        finally:
+            pts.close()
+        self.result_ = {k: res[k] for k in ("cost", "iterations", "evaluations", "status", "grad_norm")}
+        return self._result_params(best), float(err[0])
+
     def optimize(self, method="trf", bound_widths=None, loss="linear", f_scale=1.0, **kwargs):
         """scipy.optimize.least_squares on the device residuals.  ``jac``: "batched" (the default for trf and dogbox: 2-point
         differences, D + 1 trial points per launch), "analytic" (the exact Jacobian, alp_jacobian; targets w / h refused),
-        anything scipy accepts (for lm the default stays MINPACK's own differences)."""
+        anything scipy accepts (for lm the default stays MINPACK's own differences).
+
+        ``method="normal"``: a bounded Levenberg-Marquardt (``normal_lm``) on J^T J, J^T r and the cost, which the device forms
+        in one kernel per trial point (alp_normal_equations): no residual vector and no Jacobian reaches the host, and with
+        several ranks the sums arrive all-reduced -- nothing is gathered.  ``loss`` / ``f_scale`` as for scipy (linear,
+        soft_l1, huber, cauchy); bounds as for trf (``bound_widths=None``: the default widths; a width of inf leaves a target
+        unbounded); ``ftol``, ``xtol``, ``gtol`` (1e-10 each) and ``max_nfev`` with scipy's meaning; ``precision`` as for
+        CMAOptimizer (None: float64 up to F64_MAX_POINTS points, float32 above).  ``jac=`` is refused (there is no Jacobian in
+        this method), and so are targets w / h.  ``self.result_``: cost, iterations, evaluations, status, grad_norm."""
+        if method == "normal":
+            return self._optimize_normal(bound_widths, loss, f_scale, **kwargs)
         analytic = kwargs.get("jac") == "analytic"
         cols = _jacobian_targets(self.target_params) if analytic else None
         if method == "lm" and bound_widths is not None:

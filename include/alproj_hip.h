@@ -63,6 +63,15 @@ enum alp_loss {
     ALP_LOSS_HUBER = 1      /* src/alproj/optimize.py:205-212 */
 };
 
+/* Loss kinds of the least-squares normal equations (alp_normal_equations): scipy.optimize.least_squares' rho(z) of ONE
+ * scalar residual r, z = (r / f_scale)^2 -- not of a point's distance: ALP_NORMAL_HUBER is not ALP_LOSS_HUBER. */
+enum alp_normal_loss {
+    ALP_NORMAL_LINEAR = 0,  /* rho = z */
+    ALP_NORMAL_SOFT_L1 = 1, /* rho = 2 (sqrt(1 + z) - 1) */
+    ALP_NORMAL_HUBER = 2,   /* rho = z for z <= 1, else 2 sqrt(z) - 1 */
+    ALP_NORMAL_CAUCHY = 3   /* rho = ln(1 + z) */
+};
+
 /* ---------------------------------------------------------------- library / device --- */
 
 int alp_abi_version(void);
@@ -207,6 +216,20 @@ int alp_residuals_batch(alp_points_t *pts, const double *cand, int64_t B, double
  * ALP_EINVAL for NULL, a bad D, a bad or repeated target.  n = 0: nothing happens. */
 int alp_jacobian(alp_points_t *pts, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int of_residuals,
                  double *out);
+/* The normal equations of the least-squares problem at one parameter vector, formed on the device: what a Gauss-Newton /
+ * Levenberg-Marquardt step and the covariance s^2 (J^T J)^-1 need of the residual vector of src/alproj/optimize.py:215-237
+ * and of the solve of :442-539, without the (2n, D) Jacobian ever leaving the registers.  J = the Jacobian of the residual
+ * vector observed - projected (alp_jacobian with of_residuals), r = that vector (a float64 set: alp_residuals' values bit
+ * for bit); float64 arithmetic on either set.  loss (enum alp_normal_loss) and f_scale have scipy's meaning: with
+ * z = (r_i / f_scale)^2, row i of J is scaled by s_i = sqrt(max(rho'(z) + 2 z rho''(z), 1e-10)) and r_i by rho'(z) / s_i
+ * (linear: s = 1).  Targets as for alp_jacobian.  out, D (D + 1) / 2 + D + 2 doubles:
+ *   the upper triangle of J^T J, row-major | J^T r (D values) | sum of rho(z) (cost = f_scale^2 / 2 times it) | point count.
+ * With a communicator, every value is the sum over the ranks (one all-reduce of at most 301 doubles).  No atomics: the
+ * order of every addition is set by the launch shape, so the same call gives the same bits.  Non-finite values propagate
+ * into the sums they touch.  n = 0 gives zeros.  Needs observed uv (else the error alp_residuals gives).
+ * ALP_EINVAL for NULL, a bad D, a bad or repeated target, an unknown loss, f_scale <= 0 or not finite. */
+int alp_normal_equations(alp_points_t *pts, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int loss,
+                         double f_scale, double *out);
 
 /* Population-wide reprojection error: replaces the inner loop of CMAOptimizer.optimize,
  * src/alproj/optimize.py:420-423, i.e. P calls of _proj_error (:347-356) = project +
