@@ -37,6 +37,19 @@
 //   4. resolve_kernel: one thread per OUTPUT pixel: distortion source map (float64), fetch the
 //      winning triangle, perspective-correct interpolation by ray/triangle intersection in view
 //      space, min_distance mask, write h x w x 3 float32 (row 0 = top)
+// On the host a frame is render_impl: clear, ensure_grid_plan (once per grid mesh: parked queues, tile boxes), draw_grid_mesh
+// or draw_indexed_mesh (step 2 and 3), resolve_frame.  Every grid size and queue capacity, and the verdict of finish_frame on
+// a finished frame's queue counters, is integer arithmetic in host/alp_plan.h (frame_plan, initial_park_caps, frame_verdict),
+// HIP-free and swept on the CPU; this file allocates and launches.  The development builds' reports hang on three hooks
+// (raster_dev.h), empty in a release build.
+//
+// Preprocessor switches of this translation unit; a build with any of them set needs -DALP_DEV (the guards at the head of
+// raster_dev.h stop it otherwise) and says so through alp_build_flags().  tests/test_abi_symbols.py holds this list and the
+// guards to every #if of the unit.
+//   development switches: ALP_WG_TIMING ALP_RASTER_STATS VIS_PLAIN_STORE VIS_NEVER PARK_NOATOMIC PARKED_SKIP_CELLS
+//                         PARKED_SKIP_COOP PARKED_SKIP_COOP4 GRID_STOP_AFTER GRID_NO_XCD_SWIZZLE
+//   tunables:             INLINE_LOG2 FAST_MAX COOP_MIN_W COOP_MIN_PIX GT_W_LOG2 GT_H_LOG2 HIZ_SPAN GRID_WAVES_PER_EU
+//                         PATCH_MIN_FAST PATCH_WORDS_NEAR PATCH_WORDS_FAR RASTER_BLOCKS_PER_CU RESOLVE_BLOCKS_PER_CU
 // The arithmetic that decides coverage and visibility is specified step by step in DESIGN.md
 // section 5 and compiled with -ffp-contract=off so that it is reproducible bit for bit.
 //
@@ -56,92 +69,11 @@
 #include <type_traits>
 #include <vector>
 
-// ---- development switches ---------------------------------------------------------------------------------
-// Timing / census / stage-skipping builds used while the kernels were tuned (tools/build_variant.sh; DESIGN.md
-// section 5 quotes their results).  Several produce WRONG IMAGES by design, so none of them can get into a
-// library by accident: each needs -DALP_DEV next to it, the library reports what it was built with through
-// alp_build_flags(), and tests/test_abi_symbols.py requires the shipped one to report nothing.  The development
-// environment overrides (ALP_NEAR_PX, ALP_GRID_LANES, ALP_PATCH_NEAR / _FAR) are read by ALP_DEV builds only.
-// ALP_NO_GRID_DETECT, ALP_QUEUE_CAP, ALP_NO_VIS_CACHE, ALP_NO_TILE_CULL and ALP_NO_OCCLUSION stay: they select
-// between paths that produce the same image and are how the tests reach the index kernels, the queue growth,
-// the full-frame path and the exact path without its culling.
-#if defined(ALP_WG_TIMING) || defined(ALP_RASTER_STATS) || defined(VIS_PLAIN_STORE) || defined(VIS_NEVER) || defined(PARK_NOATOMIC) || \
-    defined(PARKED_SKIP_CELLS) || defined(PARKED_SKIP_COOP) || defined(PARKED_SKIP_COOP4) || defined(GRID_STOP_AFTER) ||               \
-    defined(GRID_NO_XCD_SWIZZLE) || defined(PT_SKIP_CELLS) || defined(PT_SKIP_SMALL) || defined(PT_SKIP_LARGE) || defined(PARKED_TILES_LAB) || \
-    defined(INDEX_LDS_LAB)
-#define ALP_DEV_SWITCHES 1
-#ifndef ALP_DEV
-#error "development switch given without -DALP_DEV: this would build a library that renders wrong images"
-#endif
-#endif
-#if defined(INLINE_LOG2) || defined(FAST_MAX) || defined(COOP_MIN_W) || defined(COOP_MIN_PIX) || defined(GT_W_LOG2) || defined(GT_H_LOG2) || \
-    defined(HIZ_SPAN) || defined(GRID_WAVES_PER_EU) || defined(PATCH_MIN_FAST) || defined(PATCH_WORDS_NEAR) || defined(PATCH_WORDS_FAR) ||    \
-    defined(RASTER_BLOCKS_PER_CU) || defined(RESOLVE_BLOCKS_PER_CU) || defined(PARKED_TILES_WGS_PER_CU) || defined(PARKED_BY_TILES_DEFAULT)
-#define ALP_DEV_TUNABLES 1
-#ifndef ALP_DEV
-#error "tuning parameter overridden without -DALP_DEV"
-#endif
-#endif
-
 namespace alp {
 
-const char *raster_dev_flags() {
-    return ""
-#ifdef ALP_DEV
-           "ALP_DEV,"
-#endif
-#ifdef ALP_DEV_TUNABLES
-           "tunables-overridden,"
-#endif
-#ifdef ALP_WG_TIMING
-           "ALP_WG_TIMING,"
-#endif
-#ifdef ALP_RASTER_STATS
-           "ALP_RASTER_STATS,"
-#endif
-#ifdef VIS_PLAIN_STORE
-           "VIS_PLAIN_STORE(wrong image),"
-#endif
-#ifdef VIS_NEVER
-           "VIS_NEVER(wrong image),"
-#endif
-#ifdef PARK_NOATOMIC
-           "PARK_NOATOMIC(wrong image),"
-#endif
-#if defined(PARKED_SKIP_CELLS) || defined(PARKED_SKIP_COOP) || defined(PARKED_SKIP_COOP4)
-           "PARKED_SKIP_*(wrong image),"
-#endif
-#ifdef PARKED_TILES_LAB
-           "PARKED_TILES_LAB,"
-#endif
-#ifdef INDEX_LDS_LAB
-           "INDEX_LDS_LAB,"
-#endif
-#if defined(PT_SKIP_CELLS) || defined(PT_SKIP_SMALL) || defined(PT_SKIP_LARGE)
-           "PT_SKIP_*(wrong image),"
-#endif
-#ifdef GRID_STOP_AFTER
-           "GRID_STOP_AFTER(wrong image),"
-#endif
-#ifdef GRID_NO_XCD_SWIZZLE
-           "GRID_NO_XCD_SWIZZLE,"
-#endif
-        ;
-}
-
-#ifdef ALP_DEV
-static const char *dev_getenv(const char *name) { return getenv(name); }
-#else
-static const char *dev_getenv(const char *) { return nullptr; }
-#endif
-
-#ifndef PARKED_BY_TILES_DEFAULT
-#define PARKED_BY_TILES_DEFAULT 0       // 1: raster_parked_tiles_kernel draws the first round's parked work (ALP_PARKED=tiles / waves overrides)
-#endif
-#ifndef PARKED_TILES_WGS_PER_CU
-#define PARKED_TILES_WGS_PER_CU 4       // persistent grid: 32 KB of LDS per workgroup
-#endif
-
+// the development switches' guards, alp_build_flags() and report hooks (before the kernels: the guards must see which
+// tunables the command line set)
+#include "raster_dev.h"
 // The stages, in dependency order (one translation unit: the kernels inline each other's device functions):
 #include "raster_common.h"
 #include "raster_parked.h"
@@ -168,6 +100,21 @@ int upload_chunked(void *dst, const void *src, size_t bytes) {
     return ALP_OK;
 }
 
+// A host array of `total` elements of `esize` bytes through the staging buffer `stage` in chunks of `chunk` elements, one
+// kernel per chunk: launch(off, cnt).  Nothing waits in between (tools/h2d_rate.hip: large chunks, no sync) -- the stream
+// orders a chunk's kernel before the next chunk's copy.  Ends at the first HIP error; the caller synchronises.
+template <typename Launch>
+static hipError_t staged_upload(const void *src, size_t esize, int64_t total, int64_t chunk, void *stage, Launch launch) {
+    for (int64_t off = 0; off < total; off += chunk) {
+        const int64_t cnt = total - off < chunk ? total - off : chunk;
+        hipError_t e = hipMemcpyAsync(stage, (const char *)src + (size_t)off * esize, (size_t)cnt * esize, hipMemcpyHostToDevice, ctx().stream);
+        if (e != hipSuccess) return e;
+        launch(off, cnt);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 int ensure_queue(alp_mesh *m, unsigned cap) {
     if (m->queue && m->qcap >= cap) return ALP_OK;
     if (m->queue) hipFree(m->queue);
@@ -179,32 +126,22 @@ int ensure_queue(alp_mesh *m, unsigned cap) {
 
 // both device queues start at 2^20 entries and grow on demand (finish_frame); ALP_QUEUE_CAP
 // lowers the start so that tests can exercise the growth path
-unsigned initial_queue_cap() {
-    if (const char *e = getenv("ALP_QUEUE_CAP")) {
-        const long v = atol(e);
-        if (v >= 1 && v < (1l << 30)) return (unsigned)v;
-    }
-    return 1u << 20;
-}
+unsigned initial_queue_cap() { return host::initial_queue_cap(getenv("ALP_QUEUE_CAP")); }
 
-// Queues of parked work: [first round | second round] per kind.  The second round (far tiles: hardly
-// anything to park) gets an eighth of the first round's capacity; finish_frame grows either on overflow.
-int ensure_park(alp_mesh *m, unsigned cap_small, unsigned cap_large, unsigned cap_cell) {
-    if (m->park_small && m->park_cap[0] >= cap_small && m->park_cap[1] >= cap_large && m->park_cap[2] >= cap_cell) return ALP_OK;
+// Queues of parked work: [first round | second round] per kind (small triangles, large triangles, cells), `cap` and `cap_b`
+// entries; the capacities are host::initial_park_caps' at the first grid frame and host::frame_verdict's after an overflow.
+static int alloc_park(alp_mesh *m, const unsigned cap[3], const unsigned cap_b[3]) {
     if (m->park_small) hipFree(m->park_small);
     if (m->park_cell) hipFree(m->park_cell);
     m->park_small = nullptr;
     m->park_large = nullptr;
     m->park_cell = nullptr;
-    const unsigned caps[3] = {cap_small, cap_large, cap_cell};
-    unsigned b[3];
-    for (int k = 0; k < 3; ++k) b[k] = std::max(m->park_cap_b[k], caps[k] / 8 + 64);
-    ALP_HIP(hipMalloc((void **)&m->park_small, ((size_t)cap_small + b[0] + cap_large + b[1]) * sizeof(Deferred)));
-    ALP_HIP(hipMalloc((void **)&m->park_cell, ((size_t)cap_cell + b[2]) * sizeof(ParkedCell)));
-    m->park_large = (Deferred *)m->park_small + cap_small + b[0];
+    ALP_HIP(hipMalloc((void **)&m->park_small, ((size_t)cap[0] + cap_b[0] + cap[1] + cap_b[1]) * sizeof(Deferred)));
+    ALP_HIP(hipMalloc((void **)&m->park_cell, ((size_t)cap[2] + cap_b[2]) * sizeof(ParkedCell)));
+    m->park_large = (Deferred *)m->park_small + cap[0] + cap_b[0];
     for (int k = 0; k < 3; ++k) {
-        m->park_cap[k] = caps[k];
-        m->park_cap_b[k] = b[k];
+        m->park_cap[k] = cap[k];
+        m->park_cap_b[k] = cap_b[k];
     }
     return ALP_OK;
 }
@@ -373,298 +310,171 @@ int ensure_frame(alp_mesh *m, int w, int h) {
     return ALP_OK;
 }
 
-// development: ALP_PATCH_NEAR / ALP_PATCH_FAR override the patch sizes (words; 0 switches the patches off)
-static int patch_words_env(const char *name, int dflt) {
-    if (const char *e = dev_getenv(name)) {
-        const long w = atol(e);
-        if (w >= 0 && w <= 5632) return (int)w;
+// ---- one frame, step by step.  Every grid size comes from host::frame_plan (host/alp_plan.h); the steps allocate and launch.
+// The frame's counters live right behind the visibility buffer (one fill clears both).  Queue counters, QC_STRIDE per round:
+// [0] work items, [1] general entries, [2] small parked, [3] large parked, [4] parked cells; then (+ 2 * QC_STRIDE) the
+// lengths of the three tile lists and the FAR tiles' screen region.
+unsigned *frame_counters(const alp_mesh *m, const View &v) { return (unsigned *)(m->vis + (size_t)v.w * v.h); }
+
+host::FramePlan frame_plan_of(const alp_mesh *m, const View &v) {
+    return host::frame_plan(m->implicit, m->grid_h, m->grid_w, m->n_tri, v.w, v.h, ctx().cu_count, GT_W, GT_H, RASTER_BLOCKS_PER_CU,
+                            RESOLVE_BLOCKS_PER_CU);
+}
+
+// the rare cases of one round (near-plane crossings, 64 px and more): general entries into work items, then the work items
+template <bool IMPLICIT>
+int drain_rare(alp_mesh *m, const View &v, const host::FramePlan &p, int round) {
+    hipStream_t st = ctx().stream;
+    unsigned *items = frame_counters(m, v) + QC_STRIDE * round, *general = items + 1;
+    hipLaunchKernelGGL((raster_general_kernel<IMPLICIT>), dim3(p.general_wgs), dim3(256), 0, st, m->vert, m->ind,
+                       (long long)m->grid_w, v, m->vis, m->gqueue, general, m->gcap, m->queue, items, m->qcap);
+    ALP_HIP(hipGetLastError());
+    hipLaunchKernelGGL((raster_large_kernel<IMPLICIT>), dim3(p.large_wgs), dim3(256), 0, st, m->vert, m->ind,
+                       (long long)m->grid_w, v, m->vis, m->queue, items, m->qcap);
+    ALP_HIP(hipGetLastError());
+    return ALP_OK;
+}
+
+// what raster_grid_kernel parked in one round; the second round's entries follow the first round's in the queues
+int drain_parked(alp_mesh *m, const View &v, const host::FramePlan &p, int round) {
+    const unsigned *cap = round ? m->park_cap_b : m->park_cap;
+    hipLaunchKernelGGL(raster_parked_kernel, dim3(p.parked_wgs[round]), dim3(256), 0, ctx().stream, v, m->vis,
+                       m->park_small + (round ? m->park_cap[0] : 0), m->park_large + (round ? m->park_cap[1] : 0),
+                       m->park_cell + (round ? m->park_cap[2] : 0), frame_counters(m, v) + QC_STRIDE * round + 2, cap[0], cap[1], cap[2]);
+    ALP_HIP(hipGetLastError());
+    return ALP_OK;
+}
+
+// Once per grid mesh, at its first frame: the parked queues and the tile plan (the vertices never change).
+int ensure_grid_plan(alp_mesh *m, const host::FramePlan &p) {
+    if (!m->park_small) {
+        host::FrameQueues q;
+        for (int k = 0; k < 3; ++k) q.park_b[k] = m->park_cap_b[k];
+        host::initial_park_caps(initial_queue_cap(), &q);
+        if (int e = alloc_park(m, q.park, q.park_b)) return e;
     }
-    return dflt;
+    if (m->tile_bounds) return ALP_OK;
+    // published only when both allocations and the launch succeeded: a half-made plan must not
+    // make the next frame skip this block and read uninitialised boxes
+    float *tb = nullptr;
+    unsigned *tl = nullptr;
+    hipError_t e = hipMalloc((void **)&tb, (size_t)p.tile_bounds_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&tl, (size_t)p.tile_lists_bytes);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(tile_bounds_kernel, dim3((unsigned)p.tiles), dim3(256), 0, ctx().stream, m->vert, (int)m->grid_h,
+                           (int)m->grid_w, p.tiles_x, tb);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        if (tb) hipFree(tb);
+        if (tl) hipFree(tl);
+        return fail(ALP_EHIP, "frame plan of the mesh: %s", hipGetErrorString(e));
+    }
+    m->tile_bounds = tb;
+    m->tile_lists = tl;
+    return ALP_OK;
+}
+
+// one round of raster_grid_kernel over a tile list: one workgroup per possible list entry, the ones beyond the list's length
+// leave at once.  patch_words: the LDS depth patch (words of 8 bytes; 0 = none) -- the kernel's static LDS is 19 KB, 64 KB per
+// workgroup in all.
+int grid_round(alp_mesh *m, const View &v, const host::FramePlan &p, int round, int along_rows, const unsigned *list,
+               const unsigned *list_count, int patch_words) {
+    unsigned *fcount = frame_counters(m, v);
+    const unsigned *cap = round ? m->park_cap_b : m->park_cap;
+    hipLaunchKernelGGL(raster_grid_kernel, dim3(p.grid_wgs), dim3(256), (size_t)patch_words * 8, ctx().stream, m->vert, m->valid,
+                       (int)m->grid_h, (int)m->grid_w, v, m->vis, m->gqueue, fcount + 1, m->gcap, along_rows, list, list_count,
+                       m->park_small + (round ? m->park_cap[0] : 0), m->park_large + (round ? m->park_cap[1] : 0),
+                       m->park_cell + (round ? m->park_cap[2] : 0), fcount + QC_STRIDE * round + 2, cap[0], cap[1], cap[2], patch_words);
+    ALP_HIP(hipGetLastError());
+    return ALP_OK;
+}
+
+// Coverage of a regular-grid mesh: tile plan, first round (the NEAR tiles: the occluders), depth pyramid and occlusion test of
+// the FAR tiles, second round (the survivors), and the consumers of what the rounds set aside.
+int draw_grid_mesh(alp_mesh *m, const View &v, const host::FramePlan &p) {
+    hipStream_t st = ctx().stream;
+    unsigned *near_list = m->tile_lists, *far_list = near_list + p.tiles, *second_list = far_list + p.tiles,
+             *counts = frame_counters(m, v) + 2 * QC_STRIDE;   // [0] near, [1] far, [2] far survivors (cleared with the queue counters)
+    TileCull cull;
+    make_tile_cull(v, &cull);
+    if (getenv("ALP_NO_TILE_CULL")) cull.enabled = 0;     // development: measure / cross-check the exact path alone
+    if (getenv("ALP_NO_OCCLUSION")) cull.occlusion = 0;   // development: frustum culling only, one round
+    // vertices are X, Z, Y: columns step X (R[0][0] on screen x), rows step Y (R[0][2])
+    int along_rows = std::fabs(v.R[0][2]) > std::fabs(v.R[0][0]);
+    if (const char *e = dev_getenv("ALP_GRID_LANES")) along_rows = e[0] == 'r';   // development override
+    hipLaunchKernelGGL(tile_plan_kernel, dim3(p.plan_grid), dim3(256), 0, st, m->tile_bounds, (unsigned)p.tiles, cull, near_list,
+                       far_list, counts, counts + 4);
+    ALP_HIP(hipGetLastError());
+    static const int patch_near = patch_words_env("ALP_PATCH_NEAR", PATCH_WORDS_NEAR),
+                     patch_far = patch_words_env("ALP_PATCH_FAR", PATCH_WORDS_FAR);
+    if (int e = grid_round(m, v, p, 0, along_rows, near_list, counts + 0, patch_near)) return e;
+    if (int e = dev_report_first_round(st, counts)) return e;
+    // The rare cases (near-plane crossings, triangles of 64 px and more) of BOTH rounds are drawn once, after
+    // the second round's grid kernel: its general entries follow the first round's in the same queue.  The
+    // pyramid then lacks those few triangles as occluders -- it stays conservative -- and a frame has two
+    // launches fewer.
+    const bool two_rounds = cull.enabled && cull.occlusion;
+    if (!two_rounds)
+        if (int e = drain_rare<true>(m, v, p, 0)) return e;
+    if (int e = drain_parked(m, v, p, 0)) return e;
+    if (two_rounds) {
+        // depth pyramid of everything the first round drew, occlusion test of the far tiles, second round.
+        // (Measured and not kept: building the pyramid BEFORE the first round's parked cells / triangles
+        // are drawn and running the second round on a second stream next to them -- the parked geometry
+        // is the main occluder, three times as many far tiles survive, 1.23 instead of 1.06 ms.)
+        const HizDims dm = hiz_dims(v.w, v.h);
+        hipLaunchKernelGGL(hiz_build_kernel, dim3((unsigned)dm.w[3], (unsigned)dm.h[3]), dim3(256), 0, st, m->vis, v.w, v.h, dm,
+                           m->hiz, counts + 4);
+        ALP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(tile_occlusion_kernel, dim3(p.plan_grid), dim3(256), 0, st, m->tile_bounds, cull, far_list, counts, dm,
+                           m->hiz, second_list, counts + 2);
+        ALP_HIP(hipGetLastError());
+        if (int e = grid_round(m, v, p, 1, along_rows, second_list, counts + 2, patch_far)) return e;
+        if (int e = drain_rare<true>(m, v, p, 0)) return e;      // round 0's counters: both rounds' entries
+        if (int e = drain_parked(m, v, p, 1)) return e;
+    }
+    return dev_report_tiles(m, v, cull, p.tiles, p.plan_grid, two_rounds, counts);
+}
+
+// coverage of any other index array: one thread per triangle, then the rare cases
+int draw_indexed_mesh(alp_mesh *m, const View &v, const host::FramePlan &p) {
+    hipLaunchKernelGGL((raster_kernel<false>), dim3(p.index_grid), dim3(256), 0, ctx().stream, m->vert, m->ind, m->valid,
+                       (long long)m->n_tri, (long long)m->grid_w, v, m->vis, m->gqueue, frame_counters(m, v) + 1, m->gcap);
+    ALP_HIP(hipGetLastError());
+    return drain_rare<false>(m, v, p, 0);
+}
+
+template <bool IMPLICIT>
+int resolve_frame(alp_mesh *m, const View &v, const RemapCoef &rc, double min_distance, const host::FramePlan &p) {
+    const int identity = rc.a1 == 1 && rc.a2 == 1 && rc.k1 == 0 && rc.k2 == 0 && rc.k3 == 0 && rc.k4 == 0 && rc.k5 == 0 &&
+                         rc.k6 == 0 && rc.p1 == 0 && rc.p2 == 0 && rc.s1 == 0 && rc.s2 == 0 && rc.s3 == 0 && rc.s4 == 0 &&
+                         rc.c0 > 0 && rc.c1 > 0;
+    hipLaunchKernelGGL((resolve_kernel<IMPLICIT>), dim3(p.resolve_grid), dim3(256), 0, ctx().stream, m->vert,
+                       m->coords_as_value ? nullptr : m->value, m->ind, (long long)m->grid_w, v, rc, identity, min_distance, m->vis,
+                       m->image, frame_counters(m, v), m->n_tri > 0 ? m->qcount_host : nullptr);
+    ALP_HIP(hipGetLastError());
+    return ALP_OK;
 }
 
 // Enqueue one whole frame on the library stream, no host round trip: clear, raster passes (the
-// queue lengths stay on the device), resolve.  The two queue counters are copied to pinned host
-// memory at the end; finish_frame() checks them before anything reads the frame.
+// queue lengths stay on the device), resolve.  The queue counters are copied to pinned host
+// memory at the end (by the resolve); finish_frame() checks them before anything reads the frame.
 // `resolve_only`: the visibility buffer (and the frame's counters behind it) already hold this view's finished
 // raster passes -- only the resolve runs (the visibility cache, see alp_mesh::vis_current).
-template <bool IMPLICIT>
 int render_impl(alp_mesh *m, const View &v, const RemapCoef &rc, double min_distance, bool resolve_only = false) {
     hipStream_t st = ctx().stream;
-    const int cu = ctx().cu_count;
-    unsigned *const fcount = (unsigned *)(m->vis + (size_t)v.w * v.h);
+    const host::FramePlan p = frame_plan_of(m, v);
     m->vis_current = false;          // until every launch below has been accepted
     // one fill clears the visibility buffer AND the frame's queue / list counters, which live right behind it
     if (!resolve_only)
         ALP_HIP(hipMemsetAsync(m->vis, 0, (size_t)v.w * v.h * sizeof(unsigned long long) + QC_TOTAL * sizeof(unsigned), st));
     if (m->n_tri > 0 && !resolve_only) {
-        // queue counters, four per round: [0] work items, [1] general entries, [2] small parked, [3] large parked
-        // the consumers of one round: (a) the rare cases (near-plane crossings, 64 px and more), (b) what
-        // raster_grid_kernel parked; the second round's parked entries follow the first round's in the queues
-        auto drain_rare = [&](int round) -> int {
-            unsigned *items = fcount + QC_STRIDE * round, *general = items + 1;
-            hipLaunchKernelGGL((raster_general_kernel<IMPLICIT>), dim3(cu * 2), dim3(256), 0, st, m->vert, m->ind,
-                               (long long)m->grid_w, v, m->vis, m->gqueue, general, m->gcap, m->queue, items, m->qcap);
-            ALP_HIP(hipGetLastError());
-            hipLaunchKernelGGL((raster_large_kernel<IMPLICIT>), dim3(cu * 8), dim3(256), 0, st, m->vert, m->ind,
-                               (long long)m->grid_w, v, m->vis, m->queue, items, m->qcap);
-            ALP_HIP(hipGetLastError());
-            return ALP_OK;
-        };
-        // how the first round's parked work is drawn: by queue entry (raster_parked_kernel) or by tile through LDS depth
-        // patches (raster_parked_tiles_kernel); the same image either way
-        bool by_tiles = false;
-#ifdef PARKED_TILES_LAB
-        if constexpr (IMPLICIT) {
-            const char *e = dev_getenv("ALP_PARKED");
-            by_tiles = e ? e[0] == 't' : PARKED_BY_TILES_DEFAULT != 0;
-        }
-#endif
-        auto drain_parked = [&](int round) -> int {
-            unsigned *items = fcount + QC_STRIDE * round;
-            const unsigned *cap = round ? m->park_cap_b : m->park_cap;
-            const int wgs = round ? cu * 2 : cu * 8;
-#ifdef PARKED_TILES_LAB
-            if (round == 0 && by_tiles) {
-                hipLaunchKernelGGL(raster_parked_tiles_kernel, dim3(cu * PARKED_TILES_WGS_PER_CU), dim3(256), 0, st, v, m->vis, m->park_small,
-                                   m->park_large, m->park_cell, items + 2, cap[0], cap[1], cap[2], m->park_tiles, m->park_units,
-                                   m->park_units_cap);
-                ALP_HIP(hipGetLastError());
-                return ALP_OK;
-            }
-#endif
-            hipLaunchKernelGGL(raster_parked_kernel, dim3(wgs), dim3(256), 0, st, v, m->vis,
-                               m->park_small + (round ? m->park_cap[0] : 0), m->park_large + (round ? m->park_cap[1] : 0),
-                               m->park_cell + (round ? m->park_cap[2] : 0), items + 2, cap[0], cap[1], cap[2]);
-            ALP_HIP(hipGetLastError());
-            return ALP_OK;
-        };
-        if constexpr (IMPLICIT) {
-            if (!m->park_small) {
-                // ~0.7 M parked cells and a few 100 k parked triangles per 5616 x 3744 frame of the 100 M-vertex DSM
-                const unsigned cap = initial_queue_cap();
-                const bool dflt = cap == (1u << 20);
-                if (int e = ensure_park(m, cap, cap, dflt ? 2u << 20 : cap)) return e;
-            }
-            const int tiles_x = (int)((m->grid_w - 1 + GT_W - 1) / GT_W);
-            const long long tiles = (long long)tiles_x * ((m->grid_h - 1 + GT_H - 1) / GT_H);
-            if (by_tiles && !m->park_tiles) {
-                // one record per tile at most; units: a frame of the 100 M-vertex DSM makes ~45 k (grown on overflow, finish_frame)
-                const unsigned ucap = std::max(m->park_units_cap, (unsigned)std::min<long long>(std::max<long long>(tiles, 1 << 16), 1 << 22));
-                ParkedTile *pt = nullptr;
-                ParkedUnit *pu = nullptr;
-                if (hipMalloc((void **)&pt, (size_t)tiles * sizeof(ParkedTile)) != hipSuccess ||
-                    hipMalloc((void **)&pu, (size_t)ucap * sizeof(ParkedUnit)) != hipSuccess) {
-                    if (pt) hipFree(pt);
-                    return fail(ALP_EHIP, "allocation of the parked-tile records failed");
-                }
-                m->park_tiles = pt;
-                m->park_units = pu;
-                m->park_tiles_cap = (unsigned)tiles;
-                m->park_units_cap = ucap;
-            }
-            if (!m->tile_bounds) {      // once per mesh: the vertices never change
-                // published only when both allocations and the launch succeeded: a half-made plan must not
-                // make the next frame skip this block and read uninitialised boxes
-                float *tb = nullptr;
-                unsigned *tl = nullptr;
-                hipError_t e = hipMalloc((void **)&tb, (size_t)tiles * 6 * sizeof(float));
-                // three tile lists (near, far, far survivors) + their three counters
-                if (e == hipSuccess) e = hipMalloc((void **)&tl, (size_t)(3 * tiles) * sizeof(unsigned));
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(tile_bounds_kernel, dim3((unsigned)tiles), dim3(256), 0, st, m->vert, (int)m->grid_h,
-                                       (int)m->grid_w, tiles_x, tb);
-                    e = hipGetLastError();
-                }
-                if (e != hipSuccess) {
-                    if (tb) hipFree(tb);
-                    if (tl) hipFree(tl);
-                    return fail(ALP_EHIP, "frame plan of the mesh: %s", hipGetErrorString(e));
-                }
-                m->tile_bounds = tb;
-                m->tile_lists = tl;
-            }
-            unsigned *near_list = m->tile_lists, *far_list = near_list + tiles, *second_list = far_list + tiles,
-                     *counts = fcount + 2 * QC_STRIDE;   // [0] near, [1] far, [2] far survivors (cleared with the queue counters)
-            TileCull cull;
-            make_tile_cull(v, &cull);
-            if (getenv("ALP_NO_TILE_CULL")) cull.enabled = 0;     // development: measure / cross-check the exact path alone
-            if (getenv("ALP_NO_OCCLUSION")) cull.occlusion = 0;   // development: frustum culling only, one round
-            // vertices are X, Z, Y: columns step X (R[0][0] on screen x), rows step Y (R[0][2])
-            int along_rows = std::fabs(v.R[0][2]) > std::fabs(v.R[0][0]);
-            if (const char *e = dev_getenv("ALP_GRID_LANES")) along_rows = e[0] == 'r';   // development override
-            const unsigned plan_grid = (unsigned)((tiles + 255) / 256);
-            const unsigned grid_wgs = (unsigned)((tiles + 7) / 8 * 8);     // whole turns of the 8 XCDs (see the kernel's phase 0)
-            hipLaunchKernelGGL(tile_plan_kernel, dim3(plan_grid), dim3(256), 0, st, m->tile_bounds, (unsigned)tiles, cull,
-                               near_list, far_list, counts, counts + 4);
-            ALP_HIP(hipGetLastError());
-            // first round: the near tiles (the occluders).  One workgroup per possible list entry; the
-            // ones beyond the list's length leave at once.
-            // LDS depth patches (words of 8 bytes; 0 = none).  Static LDS of the kernel is 19 KB: 64 KB per workgroup in all.
-            static const int patch_near = patch_words_env("ALP_PATCH_NEAR", PATCH_WORDS_NEAR),
-                             patch_far = patch_words_env("ALP_PATCH_FAR", PATCH_WORDS_FAR);
-            hipLaunchKernelGGL(raster_grid_kernel, dim3(grid_wgs), dim3(256), (size_t)patch_near * 8, st, m->vert, m->valid,
-                               (int)m->grid_h, (int)m->grid_w, v, m->vis, m->gqueue, fcount + 1, m->gcap,
-                               along_rows, near_list, counts + 0, m->park_small, m->park_large, m->park_cell,
-                               fcount + 2, m->park_cap[0], m->park_cap[1], m->park_cap[2], patch_near,
-                               by_tiles ? m->park_tiles : nullptr, m->park_units, m->park_units_cap);
-            ALP_HIP(hipGetLastError());
-#ifdef ALP_WG_TIMING
-            {   // duration of every workgroup of the first round
-                ALP_HIP(hipStreamSynchronize(st));
-                unsigned hc[4];
-                ALP_HIP(hipMemcpy(hc, counts, sizeof(hc), hipMemcpyDeviceToHost));
-                std::vector<unsigned long long> tt(8 * (size_t)hc[0]);
-                ALP_HIP(hipMemcpyFromSymbol(tt.data(), HIP_SYMBOL(g_wgtime), tt.size() * 8));
-                unsigned long long t0 = ~0ull, t1 = 0;
-                std::vector<double> dur;
-                double phase[4] = {0, 0, 0, 0};
-                for (unsigned i = 0; i < hc[0] && i < 131072; ++i) {
-                    t0 = std::min(t0, tt[8 * i]);
-                    t1 = std::max(t1, tt[8 * i + 4]);
-                    dur.push_back((tt[8 * i + 4] - tt[8 * i]) / 100.0);
-                    for (int k = 0; k < 4; ++k) phase[k] += (tt[8 * i + k + 1] - tt[8 * i + k]) / 100.0;
-                }
-                std::vector<double> sorted = dur;
-                std::sort(sorted.begin(), sorted.end());
-                double sum = 0;
-                for (double d : dur) sum += d;
-                fprintf(stderr, "[wg timing] first round: %u workgroups, span %.1f us, sum of durations %.0f us (vertices %.0f, classify %.0f, fast %.0f, slow %.0f), "
-                                "median %.1f, p90 %.1f, p99 %.1f, max %.1f us\n", hc[0], (t1 - t0) / 100.0, sum, phase[0], phase[1], phase[2], phase[3],
-                        sorted[sorted.size() / 2], sorted[sorted.size() * 9 / 10], sorted[sorted.size() * 99 / 100], sorted.back());
-                std::vector<unsigned> idx(dur.size());
-                for (unsigned i = 0; i < idx.size(); ++i) idx[i] = i;
-                std::partial_sort(idx.begin(), idx.begin() + std::min<size_t>(8, idx.size()), idx.end(), [&](unsigned a, unsigned b) { return dur[a] > dur[b]; });
-                for (size_t k = 0; k < std::min<size_t>(8, idx.size()); ++k) {
-                    const unsigned i = idx[k];
-                    fprintf(stderr, "   wg %u: start +%.1f us, duration %.1f us = vertices %.1f + classify %.1f + fast %.1f + slow %.1f\n", i,
-                            (tt[8 * i] - t0) / 100.0, dur[i], (tt[8 * i + 1] - tt[8 * i]) / 100.0, (tt[8 * i + 2] - tt[8 * i + 1]) / 100.0,
-                            (tt[8 * i + 3] - tt[8 * i + 2]) / 100.0, (tt[8 * i + 4] - tt[8 * i + 3]) / 100.0);
-                }
-            }
-#endif
-            // The rare cases (near-plane crossings, triangles of 64 px and more) of BOTH rounds are drawn once, after
-            // the second round's grid kernel: its general entries follow the first round's in the same queue.  The
-            // pyramid then lacks those few triangles as occluders -- it stays conservative -- and a frame has two
-            // launches fewer.
-            const bool two_rounds = cull.enabled && cull.occlusion;
-            if (!two_rounds)
-                if (int e = drain_rare(0)) return e;
-            if (int e = drain_parked(0)) return e;
-            if (two_rounds) {
-                // depth pyramid of everything the first round drew, occlusion test of the far tiles, second round.
-                // (Measured and not kept: building the pyramid BEFORE the first round's parked cells / triangles
-                // are drawn and running the second round on a second stream next to them -- the parked geometry
-                // is the main occluder, three times as many far tiles survive, 1.23 instead of 1.06 ms.)
-                const HizDims dm = hiz_dims(v.w, v.h);
-                hipLaunchKernelGGL(hiz_build_kernel, dim3((unsigned)dm.w[3], (unsigned)dm.h[3]), dim3(256), 0, st, m->vis, v.w,
-                                   v.h, dm, m->hiz, counts + 4);
-                ALP_HIP(hipGetLastError());
-                hipLaunchKernelGGL(tile_occlusion_kernel, dim3(plan_grid), dim3(256), 0, st, m->tile_bounds, cull, far_list,
-                                   counts, dm, m->hiz, second_list, counts + 2);
-                ALP_HIP(hipGetLastError());
-                hipLaunchKernelGGL(raster_grid_kernel, dim3(grid_wgs), dim3(256), (size_t)patch_far * 8, st, m->vert, m->valid,
-                                   (int)m->grid_h, (int)m->grid_w, v, m->vis, m->gqueue, fcount + 1, m->gcap,
-                                   along_rows, second_list, counts + 2, m->park_small + m->park_cap[0],
-                                   m->park_large + m->park_cap[1], m->park_cell + m->park_cap[2], fcount + QC_STRIDE + 2,
-                                   m->park_cap_b[0], m->park_cap_b[1], m->park_cap_b[2], patch_far, (ParkedTile *)nullptr,
-                                   (ParkedUnit *)nullptr, 0u);
-                ALP_HIP(hipGetLastError());
-                if (int e = drain_rare(0)) return e;
-                if (int e = drain_parked(1)) return e;
-            }
-#ifdef ALP_RASTER_STATS
-            if (by_tiles) {      // census of the parked-tile records: how many bin passes, how full
-                unsigned pc[8];
-                ALP_HIP(hipStreamSynchronize(st));
-                ALP_HIP(hipMemcpy(pc, fcount, sizeof(pc), hipMemcpyDeviceToHost));
-                std::vector<ParkedTile> rr(pc[7]);
-                if (pc[7]) ALP_HIP(hipMemcpy(rr.data(), m->park_tiles, rr.size() * sizeof(ParkedTile), hipMemcpyDeviceToHost));
-                long long bins = 0, area = 0, ent[3] = {0, 0, 0}, hist[8] = {0, 0, 0, 0, 0, 0, 0, 0}, scan = 0;
-                for (const ParkedTile &r : rr) {
-                    const int nb = (((r.i1 - (r.i0 & ~7)) >> 6) + 1) * (((r.j1 - r.j0) >> 6) + 1);
-                    bins += nb;
-                    area += (long long)(r.i1 - r.i0 + 1) * (r.j1 - r.j0 + 1);
-                    for (int k = 0; k < 3; ++k) ent[k] += r.n[k];
-                    scan += (long long)nb * (r.n[0] + r.n[1] + r.n[2]);
-                    ++hist[nb <= 1 ? 0 : nb <= 2 ? 1 : nb <= 4 ? 2 : nb <= 8 ? 3 : nb <= 16 ? 4 : nb <= 32 ? 5 : nb <= 128 ? 6 : 7];
-                }
-                fprintf(stderr, "[parked tiles] records %u units %u | bins %lld (box area %lld px) | entries small %lld large %lld cells %lld | "
-                                "entry scans over all passes %lld | records by bins <=1 %lld, 2 %lld, <=4 %lld, <=8 %lld, <=16 %lld, <=32 %lld, <=128 %lld, more %lld\n",
-                        pc[7], pc[6], bins, area, ent[0], ent[1], ent[2], scan, hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7]);
-            }
-            {
-                unsigned hc[4];
-                ALP_HIP(hipMemcpyAsync(hc, counts, sizeof(hc), hipMemcpyDeviceToHost, st));
-                ALP_HIP(hipStreamSynchronize(st));
-                fprintf(stderr, "[frame plan] tiles %lld: near %u, far %u of which %u survive the occlusion test\n", tiles, hc[0],
-                        hc[1], hc[2]);
-                if (two_rounds) {
-                    // how many NEAR tiles would an occlusion test against the FINISHED frame drop (an upper bound for
-                    // what more rounds could gain)?  Full-frame pyramid, the NEAR list through tile_occlusion_kernel.
-                    const HizDims dm = hiz_dims(v.w, v.h);
-                    const unsigned full[4] = {65535u, (unsigned)v.w, 65535u, (unsigned)v.h}, zero = 0;
-                    ALP_HIP(hipMemcpy(counts + 4, full, sizeof(full), hipMemcpyHostToDevice));
-                    ALP_HIP(hipMemcpy(counts + 3, &zero, sizeof(zero), hipMemcpyHostToDevice));
-                    hipLaunchKernelGGL(hiz_build_kernel, dim3((unsigned)dm.w[3], (unsigned)dm.h[3]), dim3(256), 0, st, m->vis, v.w, v.h, dm,
-                                       m->hiz, counts + 4);
-                    hipLaunchKernelGGL(tile_occlusion_kernel, dim3(plan_grid), dim3(256), 0, st, m->tile_bounds, cull, near_list,
-                                       counts - 1, dm, m->hiz, second_list, counts + 3);      // counts[-1 + 1] = the NEAR count
-                    unsigned left = 0;
-                    ALP_HIP(hipStreamSynchronize(st));
-                    ALP_HIP(hipMemcpy(&left, counts + 3, sizeof(left), hipMemcpyDeviceToHost));
-                    fprintf(stderr, "[frame plan] of the %u NEAR tiles %u survive a test against the finished frame\n", hc[0], left);
-                }
-            }
-#endif
-        } else {
-            const long long want = (m->n_tri + 255) / 256;
-#ifndef RASTER_BLOCKS_PER_CU
-#define RASTER_BLOCKS_PER_CU 64        // 16: 2.12 ms, 64: 2.01 (explicit int32 indices, 100 M vertices)
-#endif
-            const int grid = (int)(want < (long long)cu * RASTER_BLOCKS_PER_CU ? want : (long long)cu * RASTER_BLOCKS_PER_CU);
-            bool through_lds = false;
-#ifdef INDEX_LDS_LAB        // round 5: a block's vertices transformed once through an LDS hash set -- bit-exact, slower, not kept (raster_index.h)
-            if constexpr (!IMPLICIT) {
-                if (m->ind_sharing < 0.0f) {       // once per mesh: how many distinct vertices do 256 consecutive triangles name?
-                    unsigned long long *sums = nullptr, host[2] = {0, 0};
-                    if (int e = scratch_reserve(sizeof(host), (void **)&sums)) return e;
-                    ALP_HIP(hipMemsetAsync(sums, 0, sizeof(host), st));
-                    const long long blocks = want, step = blocks > 4096 ? blocks / 4096 : 1;
-                    hipLaunchKernelGGL(index_sharing_kernel, dim3((unsigned)std::min<long long>((blocks + step - 1) / step, 4096)), dim3(256), 0, st,
-                                       m->ind, (long long)m->n_tri, step, sums);
-                    ALP_HIP(hipMemcpyAsync(host, sums, sizeof(host), hipMemcpyDeviceToHost, st));
-                    ALP_HIP(hipStreamSynchronize(st));
-                    m->ind_sharing = host[1] ? (float)((double)host[0] / (double)host[1]) : 1.0f;
-                }
-                const char *force = getenv("ALP_INDEX_LDS");     // "0" / "1": either kernel whatever the array
-                through_lds = force ? atoi(force) != 0 : m->ind_sharing <= INDEX_SHARING_MAX;
-                if (through_lds)
-                    hipLaunchKernelGGL(raster_index_lds_kernel, dim3(grid), dim3(256), 0, st, m->vert, m->ind, m->valid, (long long)m->n_tri, v,
-                                       m->vis, m->gqueue, fcount + 1, m->gcap);
-            }
-#endif
-            if (!through_lds)
-                hipLaunchKernelGGL((raster_kernel<IMPLICIT>), dim3(grid), dim3(256), 0, st, m->vert, m->ind, m->valid,
-                                   (long long)m->n_tri, (long long)m->grid_w, v, m->vis, m->gqueue, fcount + 1,
-                                   m->gcap);
-            ALP_HIP(hipGetLastError());
-            if (int e = drain_rare(0)) return e;
-        }
+        if (m->implicit)
+            if (int e = ensure_grid_plan(m, p)) return e;
+        if (int e = m->implicit ? draw_grid_mesh(m, v, p) : draw_indexed_mesh(m, v, p)) return e;
     }
-    const long long npix = (long long)v.w * v.h;
-    const long long want = (npix + 255) / 256;
-#ifndef RESOLVE_BLOCKS_PER_CU
-#define RESOLVE_BLOCKS_PER_CU 64       // 16: 0.200 ms, 64: 0.176, one block per 256 pixels: 0.176 (100 M-vertex frame)
-#endif
-    const int grid = (int)(want < (long long)cu * RESOLVE_BLOCKS_PER_CU ? want : (long long)cu * RESOLVE_BLOCKS_PER_CU);
-    const int identity = rc.a1 == 1 && rc.a2 == 1 && rc.k1 == 0 && rc.k2 == 0 && rc.k3 == 0 && rc.k4 == 0 && rc.k5 == 0 &&
-                         rc.k6 == 0 && rc.p1 == 0 && rc.p2 == 0 && rc.s1 == 0 && rc.s2 == 0 && rc.s3 == 0 && rc.s4 == 0 &&
-                         rc.c0 > 0 && rc.c1 > 0;
-    hipLaunchKernelGGL((resolve_kernel<IMPLICIT>), dim3(grid), dim3(256), 0, st, m->vert,
-                       m->coords_as_value ? nullptr : m->value, m->ind,
-                       (long long)m->grid_w, v, rc, identity, min_distance, m->vis, m->image, fcount,
-                       m->n_tri > 0 ? m->qcount_host : nullptr);
-    ALP_HIP(hipGetLastError());
+    if (int e = m->implicit ? resolve_frame<true>(m, v, rc, min_distance, p) : resolve_frame<false>(m, v, rc, min_distance, p)) return e;
     m->last_v = v;
     m->last_rc = rc;
     m->last_min_distance = min_distance;
@@ -672,25 +482,7 @@ int render_impl(alp_mesh *m, const View &v, const RemapCoef &rc, double min_dist
     m->vis_current = true;
     m->rz_n = -1;                    // a rasterisation plan belongs to the frame it was made for
     ++(resolve_only ? m->frames_resolve_only : m->frames_full);
-#ifdef ALP_RASTER_STATS
-    {
-        unsigned long long hs[24 + 64], zero[24 + 64] = {0};
-        ALP_HIP(hipStreamSynchronize(st));
-        ALP_HIP(hipMemcpyFromSymbol(hs, HIP_SYMBOL(g_rstat), sizeof(hs)));
-        ALP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_rstat), zero, sizeof(zero)));
-        fprintf(stderr, "[raster stats] inline tris %llu | inline fragments by bbox width: 1px %llu, 2-3 %llu, 4-7 %llu, "
-                        ">=8 %llu | coop tris %llu fragments %llu\n", hs[2], hs[3], hs[4], hs[5], hs[6], hs[8], hs[7]);
-        static const char *bn[8] = {"<=512", "<=1K", "<=2K", "<=4K", "<=8K", "<=16K", "<=64K", ">64K"};
-        for (int b = 0; b < 8; ++b)
-            fprintf(stderr, "[footprint %6s px] tiles %7llu  area %10llu  cells FAST %9llu SLOW %9llu PARKED %8llu | box centres FAST %10llu "
-                            "SLOW %10llu PARKED %10llu\n", bn[b], hs[24 + 8 * b], hs[25 + 8 * b], hs[26 + 8 * b], hs[27 + 8 * b], hs[28 + 8 * b],
-                    hs[29 + 8 * b], hs[30 + 8 * b], hs[31 + 8 * b]);
-        fprintf(stderr, "[parked cells] %llu: box height <= 2: %llu, <= 4: %llu; width <= 4: %llu; centres in boxes %llu\n", hs[23], hs[19], hs[20],
-                hs[21], hs[22]);
-        fprintf(stderr, "[grid stats] (unused %llu) tiles drawn %llu | FAST cells %llu (wave rounds %llu) SLOW cells %llu (wave "
-                        "rounds %llu)\n", hs[9], hs[10], hs[11], hs[13], hs[12], hs[14]);
-    }
-#endif
+    if (int e = dev_report_frame(st)) return e;
     m->rendered = true;
     return ALP_OK;
 }
@@ -702,44 +494,30 @@ static bool same_view(const View &a, const View &b) {
            !memcmp(a.Rd, b.Rd, sizeof(a.Rd)) && !memcmp(a.camd, b.camd, sizeof(a.camd));
 }
 
-// Before anything reads the last frame: wait for it and make sure neither queue overflowed.  A
+// Before anything reads the last frame: wait for it and make sure no queue overflowed (host::frame_verdict).  A
 // queue that was too small is grown and the frame rendered again (max is idempotent, but the
-// dropped entries were never drawn).
+// dropped entries were never drawn); the verdict on the grown queues with the same counters is "none", so a frame is
+// redone only for entries that the redone frame itself newly asks for.
 int finish_frame(alp_mesh *m) {
     while (m->unchecked) {
         ALP_HIP(hipStreamSynchronize(ctx().stream));
         m->unchecked = false;
-        const unsigned *h = m->qcount_host;
-        const unsigned items = std::max(h[0], h[QC_STRIDE]), general = std::max(h[1], h[QC_STRIDE + 1]);
-        bool park_ok = true;
-        unsigned want_a[3], want_b[3];
+        host::FrameQueues have;
+        have.items = m->qcap;
+        have.general = m->gcap;
         for (int k = 0; k < 3; ++k) {
-            want_a[k] = m->park_cap[k];
-            want_b[k] = m->park_cap_b[k];
-            if (m->park_small && h[2 + k] > m->park_cap[k]) { park_ok = false; want_a[k] = h[2 + k] + h[2 + k] / 4 + 1024; }
-            if (m->park_small && h[QC_STRIDE + 2 + k] > m->park_cap_b[k]) { park_ok = false; want_b[k] = h[QC_STRIDE + 2 + k] + h[QC_STRIDE + 2 + k] / 4 + 1024; }
+            have.park[k] = m->park_cap[k];
+            have.park_b[k] = m->park_cap_b[k];
         }
-        const bool units_ok = !m->park_units || h[6] <= m->park_units_cap;      // [6]: units the first round's tiles asked for
-        if (items <= m->qcap && general <= m->gcap && park_ok && units_ok) break;
-        if (!units_ok) {
-            hipFree(m->park_tiles);
-            hipFree(m->park_units);
-            m->park_tiles = nullptr;
-            m->park_units = nullptr;
-            m->park_units_cap = h[6] + h[6] / 4 + 1024;      // reallocated by the frame below
-        }
-        if (!park_ok) {
-            for (int k = 0; k < 3; ++k) m->park_cap_b[k] = want_b[k];
-            m->park_cap[0] = 0;           // force the reallocation
-            if (int e = ensure_park(m, want_a[0], want_a[1], want_a[2])) return e;
-        }
-        if (items > m->qcap)
-            if (int e = ensure_queue(m, items + items / 4 + 1024)) return e;
-        if (general > m->gcap)
-            if (int e = ensure_gqueue(m, general + general / 4 + 1024)) return e;
-        if (int e = m->implicit ? render_impl<true>(m, m->last_v, m->last_rc, m->last_min_distance)
-                                : render_impl<false>(m, m->last_v, m->last_rc, m->last_min_distance))
-            return e;
+        const host::QueueVerdict want = host::frame_verdict(m->qcount_host, QC_STRIDE, m->park_small != nullptr, have);
+        if (want.none()) break;
+        if (want.park)
+            if (int e = alloc_park(m, want.caps.park, want.caps.park_b)) return e;
+        if (want.items)
+            if (int e = ensure_queue(m, want.caps.items)) return e;
+        if (want.general)
+            if (int e = ensure_gqueue(m, want.caps.general)) return e;
+        if (int e = render_impl(m, m->last_v, m->last_rc, m->last_min_distance)) return e;
     }
     return ALP_OK;
 }
@@ -753,19 +531,80 @@ int alp::finish_frame_of(alp_mesh *m) { return finish_frame(m); }
 int alp::upload_f32(float *dst, const void *src, int dtype, int64_t n_vert) {
     const size_t count = (size_t)n_vert * 3;
     if (dtype == ALP_F32) return upload_chunked(dst, src, count * 4);
-    const size_t CH = (size_t)24 << 20;                 // doubles per chunk: 192 MB (tools/h2d_rate.hip: large chunks, no sync in between)
+    const size_t CH = (size_t)24 << 20;                 // doubles per chunk: 192 MB
     const size_t ch = count < CH ? count : CH;
     double *stage = nullptr;
     if (int rc = scratch_reserve(ch * 8, (void **)&stage)) return rc;
     hipStream_t st = ctx().stream;
-    for (size_t off = 0; off < count; off += ch) {
-        const size_t cnt = count - off < ch ? count - off : ch;
-        ALP_HIP(hipMemcpyAsync(stage, (const double *)src + off, cnt * 8, hipMemcpyHostToDevice, st));
+    const hipError_t e = staged_upload(src, 8, (int64_t)count, (int64_t)ch, stage, [&](int64_t off, int64_t cnt) {
         hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(4096), dim3(256), 0, st, stage, (long long)cnt, (long long)off, dst);
-        ALP_HIP(hipGetLastError());
-    }
+    });
+    if (e != hipSuccess) return fail(ALP_EHIP, "float64 upload: %s", hipGetErrorString(e));
     ALP_HIP(hipStreamSynchronize(st));
     return ALP_OK;
+}
+
+// alp_mesh_create: is the host index array the full regular grid of row length gw?  Checked WHILE IT STREAMS through the
+// staging buffer, chunks of whole triangles; nothing is stored.
+static int streamed_grid_check(alp_mesh *m, const void *ind, int ind_dtype, int64_t n_tri, long long gw, bool *is_grid) {
+    hipStream_t st = ctx().stream;
+    const size_t esize = ind_dtype == ALP_I32 ? 4 : 8;
+    const int64_t total = n_tri * 3;
+    const int64_t CH = (int64_t)(((size_t)192 << 20) / esize) / 3 * 3;      // whole triangles per chunk
+    const int64_t ch = total < CH ? total : CH;
+    void *stage = nullptr;
+    if (int rc = scratch_reserve((size_t)ch * esize, &stage)) return rc;
+    hipError_t e = hipMemsetAsync(m->qcount_dev, 0, sizeof(unsigned), st);
+    if (e == hipSuccess)
+        e = staged_upload(ind, esize, total, ch, stage, [&](int64_t off, int64_t cnt) {
+            if (ind_dtype == ALP_I32)
+                hipLaunchKernelGGL(check_grid_chunk_kernel<int>, dim3(4096), dim3(256), 0, st, (const int *)stage, cnt / 3, off / 3, gw, m->qcount_dev);
+            else
+                hipLaunchKernelGGL(check_grid_chunk_kernel<long long>, dim3(4096), dim3(256), 0, st, (const long long *)stage, cnt / 3, off / 3, gw,
+                                   m->qcount_dev);
+        });
+    if (e == hipSuccess) e = hipMemcpyAsync(m->qcount_host, m->qcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(ALP_EHIP, "grid check: %s", hipGetErrorString(e));
+    *is_grid = *m->qcount_host == 0;
+    return ALP_OK;
+}
+
+// alp_mesh_create: the index array of m->n_tri triangles as int32 on the device, every index checked against the vertex count
+static int upload_indices(alp_mesh *m, const void *ind, int ind_dtype) {
+    hipStream_t st = ctx().stream;
+    const long long n_vert = m->n_vert;
+    if (hipMalloc((void **)&m->ind, (size_t)m->n_tri * 12) != hipSuccess) return fail(ALP_EHIP, "hipMalloc ind");
+    if (hipMemsetAsync(m->qcount_dev, 0, sizeof(unsigned), st) != hipSuccess) return fail(ALP_EHIP, "index check: memset");
+    const int64_t total = m->n_tri * 3;
+    hipError_t e = hipSuccess;
+    if (ind_dtype == ALP_I32) {
+        if (int rc = upload_chunked(m->ind, ind, (size_t)total * 4)) return rc;
+        hipLaunchKernelGGL(check_index_range_kernel, dim3(4096), dim3(256), 0, st, m->ind, (long long)total, n_vert, m->qcount_dev);
+    } else {
+        // int64 (what numpy builds, surface.py:194-201; project.py:215 casts with astype("i4")): narrowed on the
+        // device, staged through the library scratch in chunks of 192 MB
+        const int64_t CH = 24 << 20;
+        const int64_t ch = total < CH ? total : CH;
+        long long *stage = nullptr;
+        if (int rc = scratch_reserve((size_t)ch * 8, (void **)&stage)) return rc;
+        e = staged_upload(ind, 8, total, ch, stage, [&](int64_t off, int64_t cnt) {
+            hipLaunchKernelGGL(narrow_indices_kernel, dim3(4096), dim3(256), 0, st, stage, (long long)cnt, (long long)off, m->ind, n_vert,
+                               m->qcount_dev);
+        });
+    }
+    // range check (an out-of-range index would fault in the kernels): counted by the kernels above
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(m->qcount_host, m->qcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(ALP_EHIP, "index upload: %s", hipGetErrorString(e));
+    if (*m->qcount_host == 0) return ALP_OK;
+    // name the first offender like the host check did (cold path: a scan of the caller's array)
+    for (int64_t i = 0; i < total; ++i) {
+        const long long v = ind_dtype == ALP_I32 ? (long long)((const int *)ind)[i] : ((const long long *)ind)[i];
+        if (v < 0 || v >= n_vert) return fail(ALP_EINVAL, "index %lld out of range at %lld", v, (long long)i);
+    }
+    return fail(ALP_EINVAL, "%u indices out of range", *m->qcount_host);
 }
 
 // Regular-grid recognition in a host index array (HostGridCheck, host_check_threads, grid_candidate): host/alp_host.h --
@@ -828,33 +667,8 @@ int alp_mesh_create(const void *vert, int vert_dtype, const void *value, int val
     bool streamed_grid = false;
     if (cand_gw) {
         const long long gh = cand_gh, gw = cand_gw;
-        if (host_check.started) {
-            streamed_grid = host_check.is_grid();
-        } else {
-            hipStream_t st = ctx().stream;
-            const size_t esize = ind_dtype == ALP_I32 ? 4 : 8;
-            const int64_t total = n_tri * 3;
-            const int64_t CH = (int64_t)(((size_t)192 << 20) / esize) / 3 * 3;      // whole triangles per chunk
-            const int64_t ch = total < CH ? total : CH;
-            void *stage = nullptr;
-            if ((rc = scratch_reserve((size_t)ch * esize, &stage))) return bail(rc);
-            hipError_t e = hipMemsetAsync(m->qcount_dev, 0, sizeof(unsigned), st);
-            for (int64_t off = 0; off < total && e == hipSuccess; off += ch) {
-                const int64_t cnt = total - off < ch ? total - off : ch;
-                e = hipMemcpyAsync(stage, (const char *)ind + (size_t)off * esize, (size_t)cnt * esize, hipMemcpyHostToDevice, st);
-                if (e != hipSuccess) break;
-                if (ind_dtype == ALP_I32)
-                    hipLaunchKernelGGL(check_grid_chunk_kernel<int>, dim3(4096), dim3(256), 0, st, (const int *)stage, cnt / 3, off / 3, gw, m->qcount_dev);
-                else
-                    hipLaunchKernelGGL(check_grid_chunk_kernel<long long>, dim3(4096), dim3(256), 0, st, (const long long *)stage, cnt / 3, off / 3, gw,
-                                       m->qcount_dev);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(m->qcount_host, m->qcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return bail(fail(ALP_EHIP, "grid check: %s", hipGetErrorString(e)));
-            streamed_grid = *m->qcount_host == 0;
-        }
+        if (host_check.started) streamed_grid = host_check.is_grid();
+        else if ((rc = streamed_grid_check(m, ind, ind_dtype, n_tri, gw, &streamed_grid))) return bail(rc);
         if (streamed_grid) {
             m->implicit = true;
             m->grid_h = gh;
@@ -862,44 +676,8 @@ int alp_mesh_create(const void *vert, int vert_dtype, const void *value, int val
         }
     }
     const bool want_ind = !implicit && n_tri > 0 && !streamed_grid;
-    if (want_ind) {
-        hipStream_t st = ctx().stream;
-        if (hipMalloc((void **)&m->ind, (size_t)n_tri * 12) != hipSuccess) return bail(fail(ALP_EHIP, "hipMalloc ind"));
-        if (hipMemsetAsync(m->qcount_dev, 0, sizeof(unsigned), st) != hipSuccess) return bail(fail(ALP_EHIP, "index check: memset"));
-        const int64_t total = n_tri * 3;
-        if (ind_dtype == ALP_I32) {
-            if ((rc = upload_chunked(m->ind, ind, (size_t)total * 4))) return bail(rc);
-            hipLaunchKernelGGL(check_index_range_kernel, dim3(4096), dim3(256), 0, st, m->ind, (long long)total, (long long)n_vert,
-                               m->qcount_dev);
-        } else {
-            // int64 (what numpy builds, surface.py:194-201; project.py:215 casts with astype("i4")): narrowed on the
-            // device, staged through the library scratch in chunks of 192 MB
-            const int64_t CH = 24 << 20;
-            const int64_t ch = total < CH ? total : CH;
-            long long *stage = nullptr;
-            if ((rc = scratch_reserve((size_t)ch * 8, (void **)&stage))) return bail(rc);
-            for (int64_t off = 0; off < total; off += ch) {
-                const int64_t cnt = total - off < ch ? total - off : ch;
-                if (hipMemcpyAsync(stage, (const long long *)ind + off, (size_t)cnt * 8, hipMemcpyHostToDevice, st) != hipSuccess)
-                    return bail(fail(ALP_EHIP, "index upload"));
-                hipLaunchKernelGGL(narrow_indices_kernel, dim3(4096), dim3(256), 0, st, stage, (long long)cnt, (long long)off, m->ind,
-                                   (long long)n_vert, m->qcount_dev);
-            }
-        }
-        // range check (an out-of-range index would fault in the kernels): counted by the kernels above
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(m->qcount_host, m->qcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return bail(fail(ALP_EHIP, "index upload: %s", hipGetErrorString(e)));
-        if (*m->qcount_host != 0) {
-            // name the first offender like the host check did (cold path: a scan of the caller's array)
-            for (int64_t i = 0; i < total; ++i) {
-                const long long v = ind_dtype == ALP_I32 ? (long long)((const int *)ind)[i] : ((const long long *)ind)[i];
-                if (v < 0 || v >= n_vert) return bail(fail(ALP_EINVAL, "index %lld out of range at %lld", v, (long long)i));
-            }
-            return bail(fail(ALP_EINVAL, "%u indices out of range", *m->qcount_host));
-        }
-    }
+    if (want_ind)
+        if ((rc = upload_indices(m, ind, ind_dtype))) return bail(rc);
     if ((rc = ensure_queue(m, initial_queue_cap()))) return bail(rc);
     if ((rc = ensure_gqueue(m, initial_queue_cap()))) return bail(rc);
     // ... and when they were (surface.py:203-205), the grid with a vertex mask
@@ -929,7 +707,7 @@ int alp_mesh_destroy(alp_mesh_t *m) {
                     (void *)m->tri_present, (void *)m->tri_rank, (void *)m->vis, (void *)m->image,
                     (void *)m->queue, (void *)m->gqueue, (void *)m->qcount_dev, (void *)m->compact_counts, (void *)m->compact_offsets,
                     (void *)m->tile_bounds, (void *)m->tile_lists, (void *)m->hiz, (void *)m->park_small, (void *)m->park_cell,
-                    (void *)m->rz_points, (void *)m->rz_work, (void *)m->park_tiles, (void *)m->park_units})
+                    (void *)m->rz_points, (void *)m->rz_work})
         if (p) hipFree(p);
     if (m->qcount_host) hipHostFree(m->qcount_host);
     for (auto &e : m->ev_frame)
@@ -960,7 +738,7 @@ int alp_render_enqueue(alp_mesh_t *m, const double params[ALP_NPARAM], const dou
         m->ev_frame[1] = b;
     }
     ALP_HIP(hipEventRecord(m->ev_frame[0], ctx().stream));
-    const int e = m->implicit ? render_impl<true>(m, v, rc, min_distance, cached) : render_impl<false>(m, v, rc, min_distance, cached);
+    const int e = render_impl(m, v, rc, min_distance, cached);
     if (e) return e;
     ALP_HIP(hipEventRecord(m->ev_frame[1], ctx().stream));
     return ALP_OK;
@@ -1098,12 +876,19 @@ int alp_render_valid_count(alp_mesh_t *m, int64_t *count) {
     return frame_valid_count(m, count);
 }
 
-int alp_render_fetch_valid(alp_mesh_t *m, const double *offsets, uint32_t *idx_out, double *xyz_out) {
+// prologue of the three alp_render_fetch_valid*: the count alp_render_valid_count left, taken (it serves one fetch)
+static int take_valid_total(alp_mesh_t *m, const char *who, int64_t *M) {
     if (int rc = require_init()) return rc;
-    ALP_REQUIRE(m, "mesh handle is NULL");
-    if (m->valid_total < 0) return fail(ALP_ESTATE, "alp_render_fetch_valid: call alp_render_valid_count first");
-    const int64_t M = m->valid_total;
+    if (!m) return fail(ALP_EINVAL, "%s: mesh handle is NULL", who);
+    if (m->valid_total < 0) return fail(ALP_ESTATE, "%s: call alp_render_valid_count first", who);
+    *M = m->valid_total;
     m->valid_total = -1;
+    return ALP_OK;
+}
+
+int alp_render_fetch_valid(alp_mesh_t *m, const double *offsets, uint32_t *idx_out, double *xyz_out) {
+    int64_t M = 0;
+    if (int rc = take_valid_total(m, __func__, &M)) return rc;
     if (M == 0) return ALP_OK;
     ALP_REQUIRE(idx_out && xyz_out, "output is NULL");
     char *dev = nullptr;
@@ -1121,11 +906,8 @@ int alp_render_fetch_valid(alp_mesh_t *m, const double *offsets, uint32_t *idx_o
 }
 
 int alp_render_fetch_valid_planes(alp_mesh_t *m, const double *offsets, uint32_t *idx_out, double *x_out, double *y_out, double *z_out) {
-    if (int rc = require_init()) return rc;
-    ALP_REQUIRE(m, "mesh handle is NULL");
-    if (m->valid_total < 0) return fail(ALP_ESTATE, "alp_render_fetch_valid_planes: call alp_render_valid_count first");
-    const int64_t M = m->valid_total;
-    m->valid_total = -1;
+    int64_t M = 0;
+    if (int rc = take_valid_total(m, __func__, &M)) return rc;
     if (M == 0) return ALP_OK;
     ALP_REQUIRE(idx_out && x_out && y_out && z_out, "output is NULL");
     char *dev = nullptr;
@@ -1147,11 +929,8 @@ int alp_render_fetch_valid_planes(alp_mesh_t *m, const double *offsets, uint32_t
 
 int alp_render_fetch_valid_table(alp_mesh_t *m, const double *offsets, const void *array, int array_dtype, int64_t channels,
                                  int64_t *index_out, int16_t *u_out, int16_t *v_out, double *block_out) {
-    if (int rc = require_init()) return rc;
-    ALP_REQUIRE(m, "mesh handle is NULL");
-    if (m->valid_total < 0) return fail(ALP_ESTATE, "alp_render_fetch_valid_table: call alp_render_valid_count first");
-    const int64_t M = m->valid_total;
-    m->valid_total = -1;
+    int64_t M = 0;
+    if (int rc = take_valid_total(m, __func__, &M)) return rc;
     if (M == 0) return ALP_OK;
     ALP_REQUIRE(index_out && u_out && v_out && block_out, "output is NULL");
     ALP_REQUIRE(channels >= 0 && channels <= 64, "channel count out of range");
@@ -1202,23 +981,30 @@ int alp_render(alp_mesh_t *m, const double params[ALP_NPARAM], const double *off
     return alp_render_fetch(m, out);
 }
 
-int alp_distort_image(const float *img, int64_t h, int64_t w, int64_t c, const double coeffs[14], float *out) {
-    if (int rc = require_init()) return rc;
-    ALP_REQUIRE(img && out && coeffs, "NULL argument");
-    ALP_REQUIRE(h >= 1 && w >= 1 && c >= 1 && h <= 32768 && w <= 32768, "bad image shape");
+// stand-alone distort(): the inverted coefficients of an h x w image (only they and the size matter of the view) and the
+// grid of its kernels
+static void distort_setup(int64_t h, int64_t w, const double coeffs[14], RemapCoef *rc, int *grid) {
     double p[ALP_NPARAM] = {0};
     for (int i = 0; i < 14; ++i) p[7 + i] = coeffs[i];
     p[3] = 60; p[21] = (double)w; p[22] = (double)h;
     View v;
+    make_view(p, nullptr, &v, rc);
+    const long long want = ((long long)h * w + 255) / 256;
+    *grid = (int)(want < 4096 ? want : 4096);
+}
+
+int alp_distort_image(const float *img, int64_t h, int64_t w, int64_t c, const double coeffs[14], float *out) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(img && out && coeffs, "NULL argument");
+    ALP_REQUIRE(h >= 1 && w >= 1 && c >= 1 && h <= 32768 && w <= 32768, "bad image shape");
     RemapCoef rc;
-    make_view(p, nullptr, &v, &rc);
+    int grid = 0;
+    distort_setup(h, w, coeffs, &rc, &grid);
     const size_t bytes = (size_t)h * w * c * sizeof(float);
     float *dev = nullptr;
     if (int e2 = scratch_reserve(2 * bytes, (void **)&dev)) return e2;
     hipError_t e = hipMemcpyAsync(dev, img, bytes, hipMemcpyHostToDevice, ctx().stream);
     if (e == hipSuccess) {
-        const long long want = ((long long)h * w + 255) / 256;
-        const int grid = (int)(want < 4096 ? want : 4096);
         hipLaunchKernelGGL(distort_image_kernel, dim3(grid), dim3(256), 0, ctx().stream, dev, (int)w, (int)h, (int)c, rc,
                            (float *)((char *)dev + bytes));
         e = hipMemcpyAsync(out, (char *)dev + bytes, bytes, hipMemcpyDeviceToHost, ctx().stream);
@@ -1232,17 +1018,12 @@ int alp_distort_map(int64_t h, int64_t w, const double coeffs[14], float *map_x,
     if (int rc = require_init()) return rc;
     ALP_REQUIRE(coeffs && map_x && map_y, "NULL argument");
     ALP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768, "bad image shape");
-    double p[ALP_NPARAM] = {0};
-    for (int i = 0; i < 14; ++i) p[7 + i] = coeffs[i];
-    p[3] = 60; p[21] = (double)w; p[22] = (double)h;
-    View v;
     RemapCoef rc;
-    make_view(p, nullptr, &v, &rc);
+    int grid = 0;
+    distort_setup(h, w, coeffs, &rc, &grid);
     const size_t bytes = (size_t)h * w * sizeof(float);
     float *dev = nullptr;
     if (int e2 = scratch_reserve(2 * bytes, (void **)&dev)) return e2;
-    const long long want = ((long long)h * w + 255) / 256;
-    const int grid = (int)(want < 4096 ? want : 4096);
     hipLaunchKernelGGL(distort_map_kernel, dim3(grid), dim3(256), 0, ctx().stream, (int)w, (int)h, rc, dev, dev + (size_t)h * w);
     ALP_HIP(hipGetLastError());
     ALP_HIP(hipMemcpyAsync(map_x, dev, bytes, hipMemcpyDeviceToHost, ctx().stream));

@@ -39,22 +39,6 @@ struct alignas(16) ParkedCell {
     unsigned pad[3];
 };
 
-// What ONE tile (workgroup) of raster_grid_kernel parked, for raster_parked_tiles_kernel: its contiguous ranges in the
-// three queues and the pixel box (clamped to the viewport) of everything in them.  The consumer covers that box with
-// PT_BIN x PT_BIN-pixel LDS depth patches; a unit = (tile record, slot): the bins slot, slot + nslots, ... of the tile.
-struct ParkedTile {
-    unsigned base[3];          // first entry: small triangles, large triangles, cells
-    unsigned n[3];
-    int i0, j0, i1, j1;
-    unsigned pad[2];
-};
-struct ParkedUnit {
-    unsigned rec;
-    unsigned short slot, nslots;
-};
-constexpr int PT_BIN = 64;            // 4096 words of 8 bytes = 32 KB of LDS per workgroup
-constexpr int PT_MAX_UNITS = 32;      // a tile's bins are dealt to at most this many units (the nearest tiles cover 100+ bins)
-
 }  // namespace alp
 
 struct alp_mesh {
@@ -63,7 +47,6 @@ struct alp_mesh {
     float *vert = nullptr, *value = nullptr;
     int *ind = nullptr;
     unsigned char *valid = nullptr;    // optional, per vertex: 0 = nodata, its triangles are not drawn
-    float ind_sharing = -1.0f;         // INDEX_LDS_LAB builds only: distinct vertices / references per block of 256 triangles
     // A filtered index array of the regular grid (surface.py:203-205: the triangles of nodata vertices removed)
     // recognised at creation: rendered as the implicit grid with the vertex mask it implies; these map the
     // grid's triangle ids back to positions in the caller's array (alp_render_fetch_visibility)
@@ -86,9 +69,6 @@ struct alp_mesh {
     alp::ParkedCell *park_cell = nullptr;                         // implicit grid: parked cells
     unsigned park_cap[3] = {0, 0, 0};                             // small, large, cells: first round
     unsigned park_cap_b[3] = {0, 0, 0};                           // second round (its entries follow the first round's)
-    alp::ParkedTile *park_tiles = nullptr;                        // first round: one record per tile that parked something
-    alp::ParkedUnit *park_units = nullptr;
-    unsigned park_tiles_cap = 0, park_units_cap = 0;
     // per round (2 rounds x QC_STRIDE) [0] work items, [1] general entries, [2] small parked, [3] large parked,
     // [4] parked cells; then the three tile-list lengths of the frame plan
     unsigned *qcount_dev = nullptr;
@@ -130,8 +110,9 @@ int upload_chunked(void *dst, const void *src, size_t bytes);
 int upload_f32(float *dst, const void *src, int dtype, int64_t n_vert);   // n x 3 float32 / float64 host -> float32 device
 int ensure_queue(alp_mesh *m, unsigned cap);
 int ensure_gqueue(alp_mesh *m, unsigned cap);
-int ensure_park(alp_mesh *m, unsigned cap_small, unsigned cap_large, unsigned cap_cell);
-constexpr int QC_STRIDE = 8;           // counters per round
+// counters per round: [0] .. [4] in use; slots [6] and [7] of round 0, once a lab's, are now unused like the other spare ones.
+// The kernels and the single clearing fill depend on this layout.
+constexpr int QC_STRIDE = 8;
 constexpr int QC_TOTAL = 2 * QC_STRIDE + 8;   // two rounds of queue counters, three tile-list counters (+1), the FAR tiles' screen region (4)
 unsigned initial_queue_cap();
 int frame_valid_count(alp_mesh *m, int64_t *count);

@@ -5,7 +5,8 @@
 // thread counts from 1 to 64, from several caller threads at once (independent handles may be used concurrently:
 // include/alproj_hip.h), and compared with a serial restatement written here.  Exit code 0 and "host selfcheck ok" =
 // every comparison held; the sanitizers add their own verdict on stderr.  --plan prints what host/alp_plan.h plans for the
-// queries it is given (tests/test_launch_plan.py holds the Python restatements of the launch rules to it).
+// queries it is given (tests/test_launch_plan.py holds the Python restatements of the launch rules to it, and reads the render
+// frame's plans and overflow verdicts off it).
 #include <cinttypes>
 #include <mutex>
 #include <random>
@@ -381,6 +382,105 @@ void check_plan() {
     CHECK(none.blocks == 0 && none.groups_per == 0, "normal_grid(0) launches %d workgroups", none.blocks);
 }
 
+// ------------------------------------------------------------------ the render frame's plan (host/alp_plan.h)
+// launch shapes over grids from one cell to 20000 x 20000 (sides around the 2^16-th vertex for the tile edge), frames from one
+// pixel to the ABI's 32768 x 32768, small and large GPUs; then the overflow verdict: what grows exceeds what was asked for, what
+// did not overflow keeps its capacity, and the verdict on the grown queues is "none" -- the reason finish_frame's loop ends
+void check_frame_plan() {
+    const int TW = 64, TH = 16;               // GT_W x GT_H of raster_plan.h
+    const int64_t sides[] = {2, 3, 16, 17, 18, 64, 65, 66, 129, 1000, 3163, 10000, 20000, 65536, 65537, 65538};
+    const int frames[][2] = {{1, 1}, {1, 255}, {16, 16}, {17, 15}, {320, 200}, {640, 427}, {5616, 3744}, {32768, 1}, {32768, 32768}};
+    for (int cu : {1, 64, 256, 304})
+        for (int64_t gh : sides)
+            for (int64_t gw : sides) {
+                if (gh * gw >= ((int64_t)1 << 31)) continue;                    // alp_mesh_create: fewer than 2^31 vertices
+                for (auto &f : frames) {
+                    const host::FramePlan p = host::frame_plan(true, gh, gw, 2 * (gh - 1) * (gw - 1), f[0], f[1], cu, TW, TH);
+                    const int64_t tiles_y = p.tiles_x ? p.tiles / p.tiles_x : 0;
+                    CHECK(p.tiles_x >= 1 && tiles_y >= 1 && p.tiles == p.tiles_x * tiles_y, "tiles of %" PRId64 " x %" PRId64, gh, gw);
+                    CHECK((int64_t)p.tiles_x * TW >= gw - 1 && (int64_t)(p.tiles_x - 1) * TW < gw - 1 && tiles_y * TH >= gh - 1 &&
+                              (tiles_y - 1) * TH < gh - 1, "the tiles of %" PRId64 " x %" PRId64 " do not cover its cells exactly", gh, gw);
+                    CHECK(p.grid_wgs % 8 == 0 && p.grid_wgs >= p.tiles && p.grid_wgs < p.tiles + 8, "grid kernel: %u workgroups for %" PRId64 " tiles",
+                          p.grid_wgs, p.tiles);
+                    CHECK((int64_t)p.plan_grid * 256 >= p.tiles && ((int64_t)p.plan_grid - 1) * 256 < p.tiles, "plan grid %u for %" PRId64 " tiles",
+                          p.plan_grid, p.tiles);
+                    CHECK(p.tile_bounds_bytes == p.tiles * 24 && p.tile_lists_bytes == p.tiles * 12, "tile plan sizes");
+                    CHECK(p.parked_wgs[0] == 8 * cu && p.parked_wgs[1] == 2 * cu && p.general_wgs == 2 * cu && p.large_wgs == 8 * cu && p.index_grid == 0,
+                          "persistent grids at %d CUs", cu);
+                    const int64_t blocks = ((int64_t)f[0] * f[1] + 255) / 256;
+                    CHECK(p.resolve_grid >= 1 && p.resolve_grid <= 64 * cu && p.resolve_grid == std::min<int64_t>(blocks, 64 * cu),
+                          "resolve grid %d for %d x %d at %d CUs", p.resolve_grid, f[0], f[1], cu);
+                }
+            }
+    for (int cu : {1, 64, 256, 304})
+        for (int64_t n_tri : {(int64_t)1, (int64_t)255, (int64_t)256, (int64_t)257, (int64_t)64 * 256 * cu - 1, (int64_t)64 * 256 * cu,
+                              (int64_t)64 * 256 * cu + 1, (int64_t)199960002, ((int64_t)1 << 32) - 2}) {
+            const host::FramePlan p = host::frame_plan(false, 0, 0, n_tri, 1, 1, cu, TW, TH);
+            CHECK(p.index_grid >= 1 && p.index_grid <= 64 * cu && p.index_grid == std::min<int64_t>((n_tri + 255) / 256, 64 * cu) && p.tiles == 0 &&
+                      p.grid_wgs == 0 && p.resolve_grid == 1, "index grid %d for %" PRId64 " triangles at %d CUs", p.index_grid, n_tri, cu);
+            // the tunables: other caps for the two capped grids only
+            const host::FramePlan q = host::frame_plan(false, 0, 0, n_tri, 5616, 3744, cu, TW, TH, 16, 8);
+            CHECK(q.index_grid == std::min<int64_t>((n_tri + 255) / 256, 16 * cu) && q.resolve_grid == std::min<int64_t>(82134, 8 * cu), "tunable caps");
+        }
+    // the start capacities
+    CHECK(host::initial_queue_cap(nullptr) == (1u << 20) && host::initial_queue_cap("8") == 8 && host::initial_queue_cap("0") == (1u << 20) &&
+              host::initial_queue_cap("-3") == (1u << 20) && host::initial_queue_cap("1073741824") == (1u << 20) &&
+              host::initial_queue_cap("1073741823") == 1073741823u && host::initial_queue_cap("x") == (1u << 20), "ALP_QUEUE_CAP");
+    for (unsigned cap : {1u, 8u, 1000u, 1u << 20, (1u << 20) + 1, (1u << 30) - 1}) {
+        host::FrameQueues q;
+        host::initial_park_caps(cap, &q);
+        CHECK(q.park[0] == cap && q.park[1] == cap && q.park[2] == (cap == (1u << 20) ? 2u << 20 : cap), "parked queues of a start at %u", cap);
+        for (int k = 0; k < 3; ++k) CHECK(q.park_b[k] == q.park[k] / 8 + 64, "second round of a start at %u", cap);
+    }
+    // the overflow verdict
+    std::mt19937_64 rng(6);
+    const unsigned levels[] = {0, 1, 7, 8, 9, 72, 1000, 1u << 20, (1u << 20) + 1, 3000000, 1u << 31};
+    auto pick = [&] { return levels[rng() % (sizeof(levels) / sizeof(levels[0]))]; };
+    for (int trial = 0; trial < 20000; ++trial) {
+        const int stride = 8;
+        unsigned c[16];
+        for (unsigned &x : c) x = pick();
+        host::FrameQueues have;
+        have.items = std::max(pick(), 1u);
+        have.general = std::max(pick(), 1u);
+        const bool has_park = trial % 4 != 0;
+        if (has_park) {
+            host::FrameQueues start;
+            host::initial_park_caps(std::max(pick(), 1u), &start);
+            for (int k = 0; k < 3; ++k) {
+                have.park[k] = trial % 3 ? start.park[k] : std::max(pick(), 1u);
+                have.park_b[k] = trial % 3 ? start.park_b[k] : std::max(pick(), 1u);
+            }
+        }
+        const host::QueueVerdict v = host::frame_verdict(c, stride, has_park, have);
+        const unsigned items = std::max(c[0], c[stride]), general = std::max(c[1], c[stride + 1]);
+        CHECK(v.items == (items > have.items) && v.general == (general > have.general), "work items / general entries: which overflowed");
+        CHECK(v.items ? v.caps.items > items : v.caps.items == have.items, "work items %u of %u -> %u", items, have.items, v.caps.items);
+        CHECK(v.general ? v.caps.general > general : v.caps.general == have.general, "general entries %u of %u -> %u", general, have.general, v.caps.general);
+        bool park_over = false;
+        for (int k = 0; k < 3; ++k) {
+            const unsigned a = c[2 + k], b = c[stride + 2 + k];
+            park_over |= has_park && (a > have.park[k] || b > have.park_b[k]);
+            if (!has_park) {
+                CHECK(v.caps.park[k] == have.park[k] && v.caps.park_b[k] == have.park_b[k], "parked counters count although no parked queues exist");
+                continue;
+            }
+            CHECK(a > have.park[k] ? v.caps.park[k] > a : v.caps.park[k] == have.park[k], "first round, kind %d: %u of %u -> %u", k, a, have.park[k],
+                  v.caps.park[k]);
+            CHECK(v.caps.park_b[k] >= have.park_b[k] && v.caps.park_b[k] >= b, "second round, kind %d: %u of %u -> %u", k, b, have.park_b[k], v.caps.park_b[k]);
+            CHECK(!v.park || v.caps.park_b[k] >= v.caps.park[k] / 8 + 64, "second round, kind %d, below an eighth of the first", k);
+        }
+        CHECK(v.park == park_over, "parked queues: which overflowed");
+        if (!v.park)
+            for (int k = 0; k < 3; ++k) CHECK(v.caps.park_b[k] == have.park_b[k], "second round changed without an overflow");
+        CHECK(v.none() == !(v.items || v.general || v.park), "none()");
+        const host::QueueVerdict again = host::frame_verdict(c, stride, has_park, v.caps);
+        CHECK(again.none(), "the verdict on the grown queues is not none");
+        CHECK(again.caps.items == v.caps.items && again.caps.general == v.caps.general, "none changes a capacity");
+        for (int k = 0; k < 3; ++k) CHECK(again.caps.park[k] == v.caps.park[k] && again.caps.park_b[k] == v.caps.park_b[k], "none changes a capacity");
+    }
+}
+
 // RowDiv::div(e) == e / w for every row length the grid form accepts (w <= 2^16) at the indices where a magic-number division
 // fails first: around the multiples of w, spread over [0, 2^31), and at the top of the range
 void check_row_div() {
@@ -446,7 +546,50 @@ int canary(const char *which) {
 // --plan: one query per argument, or per line of stdin when there is none: n,P,f32|f64,V,TC,cu,batched,pairs[,stripes,tile_cols]
 // (the last two: an ALP_POP_GRID pair) -> "stripes tile_cols chunk_points stream_grid confirm_grid";
 // normal,n,cu -> "blocks groups_per" of normal_grid
+// frame,implicit,grid_h,grid_w,n_tri,w,h,cu,tile_w,tile_h -> "tiles_x tiles plan_grid grid_wgs parked_wgs[0] parked_wgs[1] general_wgs large_wgs
+//   index_grid resolve_grid tile_bounds_bytes tile_lists_bytes" of frame_plan
+// queues,ALP_QUEUE_CAP text or '-' -> "cap small large cells small_b large_b cells_b": the start capacities
+// verdict,has_park,items,general,small,large,cells,small_b,large_b,cells_b,<10 counters: [0] .. [4] of round 0, then of round 1>
+//   -> "items|-  general|-  park|-" then the eight capacities in the order given: what must be allocated anew, and how large
+int frame_query(const char *q) {
+    if (!strncmp(q, "frame,", 6)) {
+        int implicit = 0, w = 0, h = 0, cu = 0, tw = 0, th = 0;
+        long long gh = 0, gw = 0, n_tri = 0;
+        if (sscanf(q + 6, "%d,%lld,%lld,%lld,%d,%d,%d,%d,%d", &implicit, &gh, &gw, &n_tri, &w, &h, &cu, &tw, &th) != 9 || w < 1 || h < 1 || cu < 1 ||
+            tw < 1 || th < 1)
+            return 2;
+        const host::FramePlan p = host::frame_plan(implicit != 0, gh, gw, n_tri, w, h, cu, tw, th);
+        printf("%d %lld %u %u %d %d %d %d %d %d %lld %lld\n", p.tiles_x, (long long)p.tiles, p.plan_grid, p.grid_wgs, p.parked_wgs[0], p.parked_wgs[1],
+               p.general_wgs, p.large_wgs, p.index_grid, p.resolve_grid, (long long)p.tile_bounds_bytes, (long long)p.tile_lists_bytes);
+        return 0;
+    }
+    if (!strncmp(q, "queues,", 7)) {
+        char text[32] = "";
+        if (sscanf(q + 7, "%31[^,\n]", text) != 1) return 2;
+        host::FrameQueues fq;
+        const unsigned cap = host::initial_queue_cap(strcmp(text, "-") ? text : nullptr);
+        host::initial_park_caps(cap, &fq);
+        printf("%u %u %u %u %u %u %u\n", cap, fq.park[0], fq.park[1], fq.park[2], fq.park_b[0], fq.park_b[1], fq.park_b[2]);
+        return 0;
+    }
+    int has_park = 0;
+    unsigned c[16] = {0}, *r1 = c + 8;
+    host::FrameQueues have;
+    if (sscanf(q, "verdict,%d,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,%u", &has_park, &have.items, &have.general, &have.park[0], &have.park[1],
+               &have.park[2], &have.park_b[0], &have.park_b[1], &have.park_b[2], c, c + 1, c + 2, c + 3, c + 4, r1, r1 + 1, r1 + 2, r1 + 3, r1 + 4) != 19)
+        return 2;
+    const host::QueueVerdict v = host::frame_verdict(c, 8, has_park != 0, have);
+    printf("%s %s %s %u %u %u %u %u %u %u %u\n", v.items ? "items" : "-", v.general ? "general" : "-", v.park ? "park" : "-", v.caps.items, v.caps.general,
+           v.caps.park[0], v.caps.park[1], v.caps.park[2], v.caps.park_b[0], v.caps.park_b[1], v.caps.park_b[2]);
+    return 0;
+}
+
 int plan_query(const char *q) {
+    if (!strncmp(q, "frame,", 6) || !strncmp(q, "queues,", 7) || !strncmp(q, "verdict,", 8)) {
+        const int rc = frame_query(q);
+        if (rc) fprintf(stderr, "bad plan query: %s\n", q);
+        return rc;
+    }
     if (!strncmp(q, "normal,", 7)) {
         long long nn = -1;
         int ncu = 0;
@@ -488,7 +631,7 @@ int main(int argc, char **argv) {
     struct Group { const char *name; void (*fn)(); };
     const Group groups[] = {{"hash", check_hash},     {"minmax", check_minmax},   {"prefault", check_prefault}, {"fold_pose", check_fold_pose},
                             {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors},
-                            {"plan", check_plan},       {"row_div", check_row_div}};
+                            {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}};
     const bool concurrent = !(argc > 1 && !strcmp(argv[1], "--serial"));
     // every group on its own caller thread at once: the library promises that independent calls may overlap
     std::vector<std::thread> th;

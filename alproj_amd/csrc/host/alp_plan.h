@@ -1,11 +1,15 @@
 // Launch planning of the point-set kernels (alp_points.hip): the stripes x tile columns of a population evaluation, the points of
 // one staged residual / Jacobian launch, the stripes of the normal-equations kernel, the grid of a streaming kernel, the
-// magic-number division by a grid set's row length.
-// Integer arithmetic on (n, P, precision, V, cu_count) alone; the caller allocates and launches.  Included by host/alp_host.h
-// after host/alp_fold.h (ALP_HD); no HIP header.  host/alp_host_selfcheck.cpp sweeps it (check_plan) and prints it (--plan).
+// magic-number division by a grid set's row length -- and of a render frame (alp_raster.hip): the grid of every kernel of the
+// frame, the sizes of the once-per-mesh tile plan, the capacities of the device queues and which of them a finished frame's
+// counters say must grow.
+// Integer arithmetic on (n, P, precision, V, cu_count) resp. (mesh shape, frame size, tile size, cu_count, counters) alone; the
+// caller allocates and launches.  Included by host/alp_host.h after host/alp_fold.h (ALP_HD); no HIP header.
+// host/alp_host_selfcheck.cpp sweeps it (check_plan, check_frame_plan) and prints it (--plan).
 #pragma once
 
 #include <cstdint>
+#include <cstdlib>
 
 namespace alp {
 
@@ -135,6 +139,114 @@ inline NormalGrid normal_grid(int64_t n, int cu_count) {
     if (want > groups) want = groups;
     const int64_t per = (groups + want - 1) / want;
     return {(int)((groups + per - 1) / per), per};
+}
+
+// ------------------------------------------------------------------ the render frame (alp_raster.hip)
+// The launch shapes of one frame.  (tile_w, tile_h) = the cells of a raster_grid_kernel tile (GT_W x GT_H); the two
+// blocks-per-CU figures are the tunables next to raster_kernel and resolve_kernel.
+struct FramePlan {
+    // regular-grid meshes
+    int tiles_x = 0;
+    int64_t tiles = 0;                          // tiles_x x tile rows: one raster_grid_kernel workgroup each
+    unsigned plan_grid = 0;                     // tile_plan_kernel, tile_occlusion_kernel: one thread per tile
+    unsigned grid_wgs = 0;                      // raster_grid_kernel: whole turns of the 8 XCDs (see the kernel's phase 0)
+    int parked_wgs[2] = {0, 0};                 // raster_parked_kernel, first / second round
+    int64_t tile_bounds_bytes = 0;              // once per mesh: six floats per tile ...
+    int64_t tile_lists_bytes = 0;               // ... and three tile lists (near, far, far survivors)
+    // index arrays
+    int index_grid = 0;                         // raster_kernel (0 for a mesh without triangles: not launched)
+    // both
+    int general_wgs = 0, large_wgs = 0;         // raster_general_kernel, raster_large_kernel
+    int resolve_grid = 0;                       // resolve_kernel
+};
+
+// min(ceil(items / 256), cu_count * blocks_per_cu): grid-stride kernels with one thread per item
+inline int capped_grid(int64_t items, int cu_count, int blocks_per_cu) {
+    const int64_t want = (items + 255) / 256, cap = (int64_t)cu_count * blocks_per_cu;
+    return (int)(want < cap ? want : cap);
+}
+
+inline FramePlan frame_plan(bool implicit, int64_t grid_h, int64_t grid_w, int64_t n_tri, int w, int h, int cu_count, int tile_w,
+                            int tile_h, int raster_blocks_per_cu = 64, int resolve_blocks_per_cu = 64) {
+    FramePlan p;
+    if (implicit) {
+        p.tiles_x = (int)((grid_w - 1 + tile_w - 1) / tile_w);
+        p.tiles = (int64_t)p.tiles_x * ((grid_h - 1 + tile_h - 1) / tile_h);
+        p.plan_grid = (unsigned)((p.tiles + 255) / 256);
+        p.grid_wgs = (unsigned)((p.tiles + 7) / 8 * 8);
+        p.parked_wgs[0] = cu_count * 8;
+        p.parked_wgs[1] = cu_count * 2;
+        p.tile_bounds_bytes = p.tiles * 6 * (int64_t)sizeof(float);
+        p.tile_lists_bytes = 3 * p.tiles * (int64_t)sizeof(unsigned);
+    } else {
+        p.index_grid = capped_grid(n_tri, cu_count, raster_blocks_per_cu);
+    }
+    p.general_wgs = cu_count * 2;
+    p.large_wgs = cu_count * 8;
+    p.resolve_grid = capped_grid((int64_t)w * h, cu_count, resolve_blocks_per_cu);
+    return p;
+}
+
+// The device queues of a mesh, in entries: work items (raster_large_kernel), general entries (raster_general_kernel) and the
+// parked work of the grid kernel -- small triangles, large triangles, cells -- of the first and of the second round.
+struct FrameQueues {
+    unsigned items = 0, general = 0;
+    unsigned park[3] = {0, 0, 0}, park_b[3] = {0, 0, 0};
+};
+
+// The queues start at 2^20 entries and grow on demand; ALP_QUEUE_CAP (`env`: its text, or NULL) lowers the start so that tests
+// can exercise the growth.
+constexpr unsigned QUEUE_CAP_DEFAULT = 1u << 20;
+inline unsigned initial_queue_cap(const char *env) {
+    if (env) {
+        const long v = atol(env);
+        if (v >= 1 && v < (1l << 30)) return (unsigned)v;
+    }
+    return QUEUE_CAP_DEFAULT;
+}
+// a queue that held `n` entries too few is grown to a quarter more than was asked for
+inline unsigned grown_cap(unsigned n) { return n + n / 4 + 1024; }
+// The second round (far tiles: hardly anything to park) gets an eighth of the first round's capacity, and never less than it had.
+inline unsigned second_round_cap(unsigned previous, unsigned first_round) {
+    const unsigned c = first_round / 8 + 64;
+    return previous > c ? previous : c;
+}
+// the parked queues of the first grid frame: ~0.7 M parked cells and a few 100 k parked triangles per 5616 x 3744 frame of the
+// 100 M-vertex DSM, so the cells start at twice the default; an overridden start is taken for all three
+inline void initial_park_caps(unsigned cap, FrameQueues *q) {
+    q->park[0] = q->park[1] = cap;
+    q->park[2] = cap == QUEUE_CAP_DEFAULT ? 2u << 20 : cap;
+    for (int k = 0; k < 3; ++k) q->park_b[k] = second_round_cap(q->park_b[k], q->park[k]);
+}
+
+// What a finished frame says about its queues.  `counters`: the frame's pinned counters, per round (stride `stride`) [0] work
+// items, [1] general entries, [2] small parked, [3] large parked, [4] parked cells -- what the kernels ASKED for, whether it
+// fitted or not.  `have`: the capacities the frame ran with; `has_park`: the parked queues exist (a grid mesh that has drawn).
+// Work items and general entries of both rounds share one queue each and the second round's counters continue the first's, so
+// the larger one decides.  caps = `have` with every overflowed queue grown; a grown first-round parked queue takes its second
+// round along (second_round_cap).  Asked again with the same counters and `caps`, the answer is none(): the frame is redone
+// once per overflow, not for ever.
+struct QueueVerdict {
+    bool items = false, general = false, park = false;      // which allocations must be made anew
+    FrameQueues caps;
+    bool none() const { return !items && !general && !park; }
+};
+
+inline QueueVerdict frame_verdict(const unsigned *counters, int stride, bool has_park, const FrameQueues &have) {
+    QueueVerdict v;
+    v.caps = have;
+    const unsigned *a = counters, *b = counters + stride;
+    const unsigned items = a[0] > b[0] ? a[0] : b[0], general = a[1] > b[1] ? a[1] : b[1];
+    if (items > have.items) { v.items = true; v.caps.items = grown_cap(items); }
+    if (general > have.general) { v.general = true; v.caps.general = grown_cap(general); }
+    if (!has_park) return v;
+    for (int k = 0; k < 3; ++k) {
+        if (a[2 + k] > have.park[k]) { v.park = true; v.caps.park[k] = grown_cap(a[2 + k]); }
+        if (b[2 + k] > have.park_b[k]) { v.park = true; v.caps.park_b[k] = grown_cap(b[2 + k]); }
+    }
+    if (v.park)
+        for (int k = 0; k < 3; ++k) v.caps.park_b[k] = second_round_cap(v.caps.park_b[k], v.caps.park[k]);
+    return v;
 }
 
 }  // namespace host

@@ -32,6 +32,9 @@ __global__ __launch_bounds__(256) void distort_map_kernel(int w, int h, RemapCoe
     }
 }
 
+#ifndef RESOLVE_BLOCKS_PER_CU
+#define RESOLVE_BLOCKS_PER_CU 64       // grid cap of resolve_kernel.  16: 0.200 ms, 64: 0.176, one block per 256 pixels: 0.176 (100 M-vertex frame)
+#endif
 // (Measured and not kept, round 2: a two-stage software pipeline -- the loads of a thread's next pixel in
 // flight during the float64 interpolation of the current one.  The kernel without its float64 arithmetic
 // takes 115 us, with it 176 us; the pipelined form needs 111 VGPRs (4 waves per SIMD) and takes 167 us,

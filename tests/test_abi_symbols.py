@@ -97,12 +97,17 @@ def test_shipped_library_has_no_development_switch():
     assert _lib.build_flags() == ""
     csrc = os.path.join(ROOT, "alproj_amd", "csrc")
     src = open(os.path.join(csrc, "alp_raster.hip")).read()
-    head = src[:src.index("namespace alp {")]
+    head = src[:src.index("namespace alp {")]       # the list of the unit's switches in its opening comment
+    # the two guard blocks: the head of raster_dev.h, which alp_raster.hip includes before every other part of the unit
+    dev = open(os.path.join(csrc, "raster_dev.h")).read()
+    guard = dev[:dev.index("const char *raster_dev_flags()")]
+    assert guard.count("#error") == 2
     stages = re.findall(r'#include "(raster_[a-z]+\.h)"', src)
-    assert len(stages) >= 6
+    assert len(stages) >= 6 and stages[0] == "raster_dev.h"
     for name in ["alp_raster.hip"] + stages:
         text = open(os.path.join(csrc, name)).read()
         for switch in re.findall(r"#\s*(?:if|elif)(?:def|ndef)?\s+(?:!?defined\()?([A-Z][A-Z0-9_]+)", text):
             if switch.startswith(("ALP_DEV", "__")):
                 continue
-            assert switch in head, f"{switch} is used in {name} but not listed in the development-switch guard of alp_raster.hip"
+            assert switch in head, f"{switch} is used in {name} but not listed in the opening comment of alp_raster.hip"
+            assert re.search(r"defined\(%s\)" % switch, guard), f"{switch} is used in {name} but not in the development-switch guard of raster_dev.h"

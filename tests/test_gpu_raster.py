@@ -9,6 +9,7 @@ the reference has no fixture for the render).  What IS checked:
   * image values: float64 interpolation on both sides, 1e-6 relative (+1e-6 absolute);
   * the wrappers' semantics (flip, channel order, uint8 cast, x > 0 filter, offsets).
 """
+import functools
 import warnings
 
 import os
@@ -164,6 +165,27 @@ def test_queue_growth_redoes_the_frame(L, scene, monkeypatch):
             for _ in range(2):                     # second frame: queues already large enough
                 m.render_enqueue(L.params_vector(p), scene["offsets"])
                 assert_vis_equal(m.fetch_visibility(), ref)
+
+
+def test_queue_growth_on_a_frame_of_two_rounds_with_parked_cells(L, monkeypatch):
+    """the scene of test_mid_field_frames_with_depth_patches_stay_exact at seed 0 (a 420 x 610 grid, a 640 x 427 frame: both rounds,
+    parked cells and parked triangles) with every queue starting at 8 entries: the first frame is redone with grown queues
+    until nothing overflowed -- the full-frame counter advances by at least 2 -- the second one is drawn once, and both
+    equal the frozen oracle's in every visibility word"""
+    vert, p, valid, keep, ref = mid_field_scene(0)
+    monkeypatch.setenv("ALP_QUEUE_CAP", "8")
+    monkeypatch.setenv("ALP_NO_VIS_CACHE", "1")        # the second frame is drawn again, not served from the first one's visibility
+    with L.Mesh(vert, None, None, grid=MID_FIELD_GRID) as m:
+        m.set_valid(valid)
+        pv = L.params_vector(p)
+        for at_least, at_most in ((2, None), (1, 1)):
+            before = m.frame_counts()[0]
+            m.render_enqueue(pv, None)
+            got = m.fetch_visibility()
+            drawn = m.frame_counts()[0] - before
+            print("full frames drawn:", drawn)
+            assert drawn >= at_least and (at_most is None or drawn <= at_most), drawn
+            assert_mid_field_vis_equal(got, ref, keep)
 
 
 def test_non_square_grid_with_mask(L):
@@ -605,15 +627,16 @@ def test_random_poses_culling_and_occlusion_stay_exact(L, seed):
                 os.environ.pop("ALP_NO_VIS_CACHE", None)
 
 
-@pytest.mark.parametrize("seed", range(8))
-def test_mid_field_frames_with_depth_patches_stay_exact(L, seed):
-    """Frames in which a cell is 0.5 ... 8 pixels and a tile of 64 x 16 cells has a footprint of 1 000 ... 30 000
-    pixels: the first-round tiles that collect their fragments in an LDS depth patch, those that do not fit one,
-    parked cells and parked triangles next to each other.  Every visibility word against the frozen oracle,
-    with the patches on, and the same frame with the culling switched off."""
-    import os
+MID_FIELD_GRID = (420, 610)
+
+
+@functools.lru_cache(maxsize=None)
+def mid_field_scene(seed):
+    """(vertices of a 420 x 610 grid, pose, vertex mask or None, kept triangles or None, the frozen oracle's visibility): frames in
+    which a cell is 0.5 ... 8 pixels and a tile of 64 x 16 cells has a footprint of 1 000 ... 30 000 pixels.  Made once per seed
+    and shared; nobody writes to it."""
     rng = np.random.default_rng(500 + seed)
-    gh, gw = 420, 610
+    gh, gw = MID_FIELD_GRID
     yy, xx = np.mgrid[0:gh, 0:gw].astype(np.float64)
     z = 40 * np.sin(xx / 70.0 + seed) * np.cos(yy / 55.0) + 6 * np.sin(xx / 5.0) * np.sin(yy / 6.0) + rng.normal(0, 0.25, (gh, gw))
     vert = np.stack([xx.ravel(), (z - z.min()).ravel(), (gh - 1 - yy).ravel()], 1).astype(np.float32)      # X, Z(up), Y
@@ -636,20 +659,36 @@ def test_mid_field_frames_with_depth_patches_stay_exact(L, seed):
     keep = np.flatnonzero(valid[full].all(axis=1)) if valid is not None else None
     ref = orast.visibility(vert, full if keep is None else full[keep], p, None)
     assert (ref != 0).mean() > 0.03         # the camera sees the surface (a sanity check of the case, not of the kernel)
-    with L.Mesh(vert, None, None, grid=(gh, gw)) as m:
+    return vert, p, valid, keep, ref
+
+
+def assert_mid_field_vis_equal(got, ref, keep):
+    """every visibility word; `keep`: the oracle drew the index array of the kept triangles, the device the masked grid"""
+    if keep is None:
+        assert_vis_equal(got, ref)
+    else:
+        hit = ref != 0
+        np.testing.assert_array_equal(got != 0, hit)
+        np.testing.assert_array_equal(got[hit] >> np.uint64(32), ref[hit] >> np.uint64(32))
+        np.testing.assert_array_equal(0xFFFFFFFF - (got[hit] & np.uint64(0xFFFFFFFF)).astype(np.int64),
+                                      keep[0xFFFFFFFF - (ref[hit] & np.uint64(0xFFFFFFFF)).astype(np.int64)])
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_mid_field_frames_with_depth_patches_stay_exact(L, seed):
+    """Frames in which a cell is 0.5 ... 8 pixels and a tile of 64 x 16 cells has a footprint of 1 000 ... 30 000
+    pixels: the first-round tiles that collect their fragments in an LDS depth patch, those that do not fit one,
+    parked cells and parked triangles next to each other.  Every visibility word against the frozen oracle,
+    with the patches on, and the same frame with the culling switched off."""
+    import os
+    vert, p, valid, keep, ref = mid_field_scene(seed)
+    with L.Mesh(vert, None, None, grid=MID_FIELD_GRID) as m:
         if valid is not None:
             m.set_valid(valid)
         pv = L.params_vector(p)
         m.render_enqueue(pv, None)
         got = m.fetch_visibility()
-        if keep is None:
-            assert_vis_equal(got, ref)
-        else:
-            hit = ref != 0
-            np.testing.assert_array_equal(got != 0, hit)
-            np.testing.assert_array_equal(got[hit] >> np.uint64(32), ref[hit] >> np.uint64(32))
-            np.testing.assert_array_equal(0xFFFFFFFF - (got[hit] & np.uint64(0xFFFFFFFF)).astype(np.int64),
-                                          keep[0xFFFFFFFF - (ref[hit] & np.uint64(0xFFFFFFFF)).astype(np.int64)])
+        assert_mid_field_vis_equal(got, ref, keep)
         for env in ("ALP_NO_TILE_CULL", "ALP_NO_OCCLUSION"):
             os.environ[env] = "1"
             os.environ["ALP_NO_VIS_CACHE"] = "1"          # same view again: really draw it again

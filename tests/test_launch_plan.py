@@ -1,5 +1,5 @@
 """CPU: the launch planning of the point-set kernels (alproj_amd/csrc/host/alp_plan.h: pop_grid, stage_chunk_points,
-stream_grid) against the Python restatements the GPU tests lean on (tests/cma_cases.py: batched_grid; tests/residual_cases.py:
+stream_grid) and of a render frame (frame_plan, initial_park_caps, frame_verdict: read off the C++ at hand-worked cases) against the Python restatements the GPU tests lean on (tests/cma_cases.py: batched_grid; tests/residual_cases.py:
 chunk_points, launches, stride_pass).  The C++ is reached through the self-checking driver of the HIP-free host code
 (csrc/host/alp_host_selfcheck.cpp --plan), built without HIP by the library's own clang++: what it prints is what
 popeval_launch_t, residuals_impl and jacobian_impl launch with.  A mismatch is a bug in one of the two statements."""
@@ -20,17 +20,22 @@ CUS = (256, 64, 304)
 CHUNK22 = rc.chunk_points(1 << 40, 22)
 
 
-def plan(queries):
-    """[(stripes, tile columns, chunk points, stream grid, confirm grid)] of [(n, P, prec, V, cu, batched, pairs[, a, b])]"""
+def ask(queries):
+    """the driver's answer to each query line, split into words"""
     if _build.host_compiler("clang") is None:
         pytest.skip("no clang compiler")
     exe = _build.build_host("plain", "clang")
-    text = "".join(",".join(str(v) for v in (q[0], q[1], q[2], q[3], cc.POP_TC) + tuple(q[4:])) + "\n" for q in queries)
-    r = subprocess.run([exe, "--plan"], input=text, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe, "--plan"], input="".join(q + "\n" for q in queries), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    out = [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
+    out = [line.split() for line in r.stdout.splitlines()]
     assert len(out) == len(queries)
     return out
+
+
+def plan(queries):
+    """[(stripes, tile columns, chunk points, stream grid, confirm grid)] of [(n, P, prec, V, cu, batched, pairs[, a, b])]"""
+    return [tuple(int(v) for v in words)
+            for words in ask([",".join(str(v) for v in (q[0], q[1], q[2], q[3], cc.POP_TC) + tuple(q[4:])) for q in queries])]
 
 
 @pytest.mark.parametrize("batched", [True, False])
@@ -88,3 +93,72 @@ def test_stream_grid_cap_is_one_stride_pass(cu):
     for n, g in zip(items, got):
         assert g[3] == min(-(-n // 256), 8 * cu), (n, g)
     assert got[-1][3] * 256 * rc.RES_V == S
+
+
+# ---------------------------------------------------------------- the render frame (alp_raster.hip)
+GT = (64, 16)          # cells of a raster_grid_kernel tile (raster_plan.h: GT_W x GT_H)
+FRAME_FIELDS = ("tiles_x", "tiles", "plan_grid", "grid_wgs", "parked_wgs0", "parked_wgs1", "general_wgs", "large_wgs", "index_grid",
+                "resolve_grid", "tile_bounds_bytes", "tile_lists_bytes")
+
+
+def frame_plan(implicit, gh, gw, n_tri, w, h, cu):
+    q = ",".join(str(v) for v in ("frame", int(implicit), gh, gw, n_tri, w, h, cu) + GT)
+    return dict(zip(FRAME_FIELDS, (int(v) for v in ask([q])[0])))
+
+
+def test_frame_plan_of_the_full_size_frame():
+    """the 100 M-vertex DSM on the 5616 x 3744 frame at 256 CUs: 157 x 625 tiles of 64 x 16 cells"""
+    p = frame_plan(True, 10000, 10000, 2 * 9999 * 9999, 5616, 3744, 256)
+    assert (p["tiles_x"], p["tiles"], p["plan_grid"], p["grid_wgs"], p["resolve_grid"]) == (157, 98125, 384, 98128, 16384)
+    assert (p["parked_wgs0"], p["parked_wgs1"], p["general_wgs"], p["large_wgs"]) == (2048, 512, 512, 2048)
+    assert (p["tile_bounds_bytes"], p["tile_lists_bytes"], p["index_grid"]) == (98125 * 24, 98125 * 12, 0)
+
+
+def test_frame_plan_of_the_smallest_meshes():
+    """one cell: one tile, one whole turn of the 8 XCDs; one triangle and one pixel: one workgroup each"""
+    p = frame_plan(True, 2, 2, 2, 640, 427, 256)
+    assert (p["tiles_x"], p["tiles"], p["plan_grid"], p["grid_wgs"]) == (1, 1, 1, 8)
+    p = frame_plan(False, 0, 0, 1, 1, 1, 256)
+    assert (p["index_grid"], p["resolve_grid"], p["tiles"], p["grid_wgs"]) == (1, 1, 0, 0)
+    assert (p["general_wgs"], p["large_wgs"]) == (512, 2048)
+    # the caps: 64 workgroups per CU
+    p = frame_plan(False, 0, 0, 3 * 64 * 256, 5616, 3744, 1)
+    assert (p["index_grid"], p["resolve_grid"]) == (64, 64)
+
+
+def test_queue_start_capacities():
+    """ALP_QUEUE_CAP: the default start gives the cells twice the entries, an override gives every queue the override; the second
+    round starts at an eighth + 64"""
+    got = [[int(v) for v in line] for line in ask(["queues,-", "queues,8", "queues,0", "queues,1048576", "queues,5000"])]
+    M = 1 << 20
+    assert got[0] == [M, M, M, 2 * M, M // 8 + 64, M // 8 + 64, 2 * M // 8 + 64]
+    assert got[1] == [8, 8, 8, 8, 65, 65, 65]
+    assert got[2] == got[0] and got[3] == got[0]            # out of range: ignored; the default spelled out: the default
+    assert got[4] == [5000, 5000, 5000, 5000, 689, 689, 689]
+
+
+def grown(n):
+    return n + n // 4 + 1024
+
+
+@pytest.mark.parametrize("name,has_park,have,round0,round1,want", [
+    # have: items, general, small, large, cells, small_b, large_b, cells_b; counters per round: items, general, small, large, cells
+    ("no overflow", 1, (8, 8, 8, 8, 8, 65, 65, 65), (8, 8, 8, 8, 8), (8, 8, 65, 65, 65),
+     ("-", "-", "-", 8, 8, 8, 8, 8, 65, 65, 65)),
+    ("first-round cells alone", 1, (8, 8, 8, 8, 8, 65, 65, 65), (0, 3, 8, 0, 70000), (0, 3, 1, 0, 65),
+     ("-", "-", "park", 8, 8, 8, 8, grown(70000), 65, 65, grown(70000) // 8 + 64)),
+    ("second-round small triangles alone", 1, (8, 8, 8, 8, 8, 65, 65, 65), (1, 1, 8, 8, 8), (1, 1, 66, 65, 0),
+     ("-", "-", "park", 8, 8, 8, 8, 8, grown(66), 65, 65)),
+    ("work items of round 1 above those of round 0", 1, (100, 8, 8, 8, 8, 65, 65, 65), (90, 8, 0, 0, 0), (101, 2, 0, 0, 0),
+     ("items", "-", "-", grown(101), 8, 8, 8, 8, 65, 65, 65)),
+    # no parked queues yet (an index array): their counters are not looked at
+    ("parked counters without parked queues", 0, (8, 8, 0, 0, 0, 0, 0, 0), (8, 9, 500, 500, 500), (0, 0, 500, 500, 500),
+     ("-", "general", "-", 8, grown(9), 0, 0, 0, 0, 0, 0)),
+])
+def test_overflow_verdicts(name, has_park, have, round0, round1, want):
+    q = ",".join(str(v) for v in ("verdict", has_park) + have + round0 + round1)
+    got = ask([q])[0]
+    assert got[:3] == list(want[:3]) and [int(v) for v in got[3:]] == list(want[3:]), (name, got)
+    # asked again with the capacities it gave, the verdict is none
+    again = ask([",".join(str(v) for v in ["verdict", has_park] + got[3:] + list(round0 + round1))])[0]
+    assert again == ["-", "-", "-"] + got[3:], (name, again)

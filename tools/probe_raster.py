@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Development probe of the render path: N-vertex synthetic DSM onto the 5616x3744 frame.
-   python3 tools/probe_raster.py [N] [reps] [explicit|implicit|shuffled] [distorted]
-   (shuffled: the index array's rows in random order -- an array without locality; ALP_INDEX_LDS=0|1 forces either index kernel)"""
+   python3 tools/probe_raster.py [N] [reps] [explicit|implicit|shuffled] [distorted] [cached]
+   (shuffled: the index array's rows in random order -- an array without locality)
+   `reps` full frames; with the word `cached` after the mode, the same view once more from the visibility cache."""
 import os
 os.environ.setdefault("ALP_NO_VIS_CACHE", "1")     # every frame of a probe is drawn (no visibility cache)
 import sys
@@ -16,7 +17,8 @@ from alproj_amd import synthetic as syn     # noqa: E402
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000_000
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 mode = sys.argv[3] if len(sys.argv) > 3 else "implicit"
-distorted = len(sys.argv) > 4
+cached = "cached" in sys.argv[4:]
+distorted = len([a for a in sys.argv[4:] if a != "cached"]) > 0
 
 L.init(0)
 n = syn.grid_side(N)
@@ -47,9 +49,16 @@ for r in range(reps):
     ms = L.event_elapsed_ms(0, 1)
     best = min(best, ms)
     print(f"rep {r}: {ms:.3f} ms", flush=True)
+if cached:                                        # one more frame: the same view again, served by the resolve alone
+    del os.environ["ALP_NO_VIS_CACHE"]
+    L.event_record(0)
+    mesh.render_enqueue(pv, s["offsets"])
+    L.event_record(1)
+    L.synchronize()
+    print(f"same view again: {L.event_elapsed_ms(0, 1):.3f} ms", flush=True)
 img = mesh.fetch()
 if mode != "implicit":
     import hashlib
-    print("image sha256", hashlib.sha256(img.tobytes()).hexdigest()[:16], "ALP_INDEX_LDS =", os.environ.get("ALP_INDEX_LDS"))
+    print("image sha256", hashlib.sha256(img.tobytes()).hexdigest()[:16])
 print(f"N={n * n} T={2 * (n - 1) ** 2} {mode}: best {best:.3f} ms/frame  {n * n / best / 1e6:.2f} Gvertices/s  "
       f"covered {float((img[:, :, 0] > 0).mean()):.3f}")
