@@ -14,6 +14,7 @@ import pytest
 
 from oracle import raster as orast
 from oracle import ref_numpy as orc
+from tests import frame_cases
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 SIZES = ["48x64", "97x131", "187x281"]
@@ -63,11 +64,7 @@ class _HostMesh:
         self.raw = raw
 
     def fetch_valid(self, offsets=None):
-        flat = self.raw.reshape(-1, 3)
-        idx = np.flatnonzero(flat[:, 0] > 0).astype(np.uint32)
-        off = np.zeros(3) if offsets is None else np.asarray(offsets, dtype=np.float64)
-        xyz = np.stack([flat[idx, 0].astype(np.float64) + off[0], flat[idx, 2].astype(np.float64) + off[2],
-                        flat[idx, 1].astype(np.float64) + off[1]], axis=1)
+        idx, xyz, _, _, _ = frame_cases.valid_table(self.raw, offsets)
         return idx, xyz
 
 
