@@ -209,6 +209,8 @@ _SIGNATURES = {
     "alp_eval_population_wait": [_c_void_p, _c_dp, ctypes.POINTER(_c_i64)],
     "alp_eval_population_timing": [_c_void_p, _c_fp, _c_fp],
     "alp_eval_population_info": [_c_void_p, ctypes.POINTER(_c_i64)],
+    "alp_points_set_mend": [_c_void_p, _c_int],
+    "alp_eval_population_mended": [_c_void_p, ctypes.POINTER(_c_i64)],
     "alp_loss_uv": [_c_dp, _c_dp, _c_i64, _c_int, _c_double, _c_dp],
     "alp_loss_uv_columns": [_c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_int, _c_double, _c_dp],
     "alp_cma_sample": [_c_dp, _c_double, _c_dp, _c_dp, _c_dp, _c_int, _c_i64, _c_int, ctypes.c_uint64, ctypes.c_uint64, _c_dp,
@@ -600,6 +602,20 @@ class Points:
         info = (_c_i64 * 3)()
         check(lib().alp_eval_population_info(self._h, info))
         return self.POP_VARIANTS[int(info[0])], int(info[1]), int(info[2])
+
+    def set_mend(self, enable):
+        """Turn the mend pass of a float32 set on or off (off at creation): every candidate of a population evaluation whose
+        float32 sum is infinite or NaN is evaluated again on the device in float64 arithmetic on the stored float32 points,
+        in ``eval_population`` and in the device loop alike; every other loss keeps its bits.  A float64 set accepts the call
+        and runs no pass.  Refused while an evaluation or a device loop is pending: alp_points_set_mend"""
+        check(self._lib.alp_points_set_mend(self._h, 1 if enable else 0))
+
+    def eval_population_mended(self):
+        """(re-evaluated candidates of the last completed evaluation, their total since mend was enabled, stripes, tile
+        columns of the mend launch): alp_eval_population_mended"""
+        info = (_c_i64 * 4)()
+        check(self._lib.alp_eval_population_mended(self._h, info))
+        return tuple(int(v) for v in info)
 
     def eval_population_wait(self, P):
         losses = np.empty(P, dtype=np.float64)

@@ -684,7 +684,7 @@ int alp_cma_run(alp_cma_t *h, int64_t generations, int loss_kind, double f_scale
         if (p->precision == ALP_F64) launch_generation_t<double>(h, grid, st);
         else launch_generation_t<float>(h, grid, st);
         ALP_HIP(hipGetLastError());
-        if (int rc = popeval_launch(p, R, loss_kind, f_scale, h->lens_free, h->shared_pose, batched)) return rc;
+        if (int rc = popeval_launch(p, R, loss_kind, f_scale, h->lens_free, h->shared_pose, batched, h->cand)) return rc;
         hipLaunchKernelGGL(cma_tell_kernel<true>, dim3(h->hy.K), dim3(TELL_THREADS), 0, st, h->hy, h->st, (const double *)h->w,
                            (const double *)h->X, (const double *)p->sums_dev, (const double *)nullptr, h->loss, h->order, h->ys, h->wio);
         ALP_HIP(hipGetLastError());

@@ -904,8 +904,9 @@ __device__ __forceinline__ void pop_walk_stripe(const TS *__restrict__ x, const 
 
 // LENS_FREE: `cands` holds the lens-free records (fold_pose_lens_free) the first walk runs on, `cands_general` the general ones
 // (fold_pose) of the same candidates for the second walk; otherwise both are the general records.
-template <typename T, int LOSS, typename Cfg = PopCfg<T>, bool SHARED_POSE = false, typename TS = T, bool LENS_FREE = false>
-__global__ __launch_bounds__(256, Cfg::MINW) void popeval_kernel(
+// (the body of popeval_kernel and of popeval_counted_kernel below, which takes P from device memory)
+template <typename T, int LOSS, typename Cfg, bool SHARED_POSE, typename TS, bool LENS_FREE>
+__device__ __forceinline__ void popeval_body(
     const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z, const TS *__restrict__ uo,
     const TS *__restrict__ vo, int64_t n, const PoseRec<T> *__restrict__ cands, int P, T f_scale,
     double *__restrict__ partials, const PoseRec<T> *__restrict__ cands_general) {
@@ -968,6 +969,108 @@ __global__ __launch_bounds__(256, Cfg::MINW) void popeval_kernel(
             partials[(int64_t)blockIdx.x * P + c0 + tid] =
                 ((s_sum[0][tid] + s_sum[1][tid]) + s_sum[2][tid]) + s_sum[3][tid];
     }
+}
+
+template <typename T, int LOSS, typename Cfg = PopCfg<T>, bool SHARED_POSE = false, typename TS = T, bool LENS_FREE = false>
+__global__ __launch_bounds__(256, Cfg::MINW) void popeval_kernel(
+    const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z, const TS *__restrict__ uo,
+    const TS *__restrict__ vo, int64_t n, const PoseRec<T> *__restrict__ cands, int P, T f_scale,
+    double *__restrict__ partials, const PoseRec<T> *__restrict__ cands_general) {
+    popeval_body<T, LOSS, Cfg, SHARED_POSE, TS, LENS_FREE>(x, y, z, uo, vo, n, cands, P, f_scale, partials, cands_general);
+}
+
+// ------------------------------------------------------------------ K2m: the mend pass of a float32 population evaluation
+// (alp_points_set_mend; alp_points.hip: mend_launch).  Behind the all-reduce of the float32 sums:
+//   mend_select_kernel      the candidates whose sum is not finite, compacted in ascending order, and their float64 records
+//   popeval_counted_kernel  the float64-arithmetic evaluation of those (the argmin confirmation's kernel, count from the device)
+//   mend_reduce_kernel      its partial rows in fixed order
+//   (the all-reduce of the mended sums when a communicator exists)
+//   mend_scatter_kernel     sums[idx[k]] = mended[k]
+// MendCount: what the pass keeps on the device between its kernels and for alp_eval_population_mended.
+struct MendCount {
+    long long last;       // candidates selected by the last pass
+    long long total;      // ... since mend was enabled
+};
+
+// popeval_kernel<double, LOSS, PopCfg<double>, false, float> over the first cnt->last records: the grid is planned for the worst
+// case (host::mend_grid: every candidate selected), and a workgroup whose first tile lies at or beyond the count returns at
+// once.  The partial rows are `count` doubles long.
+template <int LOSS>
+__global__ __launch_bounds__(256, PopCfg<double>::MINW) void popeval_counted_kernel(
+    const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, const float *__restrict__ uo,
+    const float *__restrict__ vo, int64_t n, const PoseRec<double> *__restrict__ cands, const MendCount *__restrict__ cnt,
+    double f_scale, double *__restrict__ partials) {
+    const int count = (int)cnt->last;
+    if ((int)blockIdx.y * PopCfg<double>::TC >= count) return;
+    popeval_body<double, LOSS, PopCfg<double>, false, float, false>(x, y, z, uo, vo, n, cands, count, f_scale, partials, cands);
+}
+
+// One workgroup.  idx[0 .. count) = the candidates c < P whose sums[c] is infinite or NaN, ascending (ballot + prefix, no
+// atomics: the same list on every run and on every rank, whose sums are identical after the all-reduce); cnt->last = count,
+// cnt->total += count; recs[k] = the float64 fold of candidate idx[k]'s 25 parameters (host/alp_fold.h, as cma_generation_kernel
+// folds them).
+__global__ __launch_bounds__(256) void mend_select_kernel(const double *__restrict__ sums, int P, const double *__restrict__ params,
+                                                          double o0, double o1, double o2, int *__restrict__ idx,
+                                                          PoseRec<double> *__restrict__ recs, MendCount *__restrict__ cnt) {
+    __shared__ int s_wave[4];
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < P; c0 += 256) {
+        const int c = c0 + tid;
+        const bool bad = c < P && (__builtin_bit_cast(unsigned long long, sums[c < P ? c : 0]) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(bad);
+        if (lane == 0) s_wave[wave] = __builtin_popcountll(m);
+        __syncthreads();
+        int before = s_base;
+        for (int w = 0; w < wave; ++w) before += s_wave[w];
+        if (bad) idx[before + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = c;
+        __syncthreads();
+        if (tid == 0) s_base += (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+        __syncthreads();
+    }
+    const int count = s_base;
+    if (tid == 0) {
+        cnt->last = count;
+        cnt->total += count;
+    }
+    const double origin[3] = {o0, o1, o2};
+    for (int k = tid; k < count; k += 256) {
+        double prm[ALP_NPARAM], g[POSE_WORDS];
+        const double *src = params + (int64_t)idx[k] * ALP_NPARAM;
+        for (int j = 0; j < ALP_NPARAM; ++j) prm[j] = src[j];
+        fold_pose_hd(prm, origin, g);
+        for (int j = 0; j < POSE_WORDS; ++j) recs[k].v[j] = g[j];
+    }
+}
+
+// mended[k] = sum over the stripes of partials[b][k] (fixed order: reduce_partials_kernel's) for k < count, 0 for count <= k < P:
+// the buffer has a fixed size for the all-reduce.  One workgroup handles 32 candidates x 8 row-groups.
+__global__ __launch_bounds__(256) void mend_reduce_kernel(const double *__restrict__ partials, int nblk, int P,
+                                                          const MendCount *__restrict__ cnt, double *__restrict__ mended) {
+    __shared__ double s[8][32];
+    const int count = (int)cnt->last;
+    const int cl = threadIdx.x & 31;
+    const int g = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cl;
+    double acc = 0.0;
+    if (c < count)
+        for (int b = g; b < nblk; b += 8) acc += partials[(int64_t)b * count + c];
+    s[g][cl] = acc;
+    __syncthreads();
+    if (g == 0 && c < P) {
+        double t = s[0][cl];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) t += s[k][cl];
+        mended[c] = t;
+    }
+}
+
+__global__ __launch_bounds__(256) void mend_scatter_kernel(const int *__restrict__ idx, const double *__restrict__ mended,
+                                                           const MendCount *__restrict__ cnt, double *__restrict__ sums) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < (int)cnt->last) sums[idx[k]] = mended[k];
 }
 
 // sums[c] = sum over workgroups of partials[b][c] (fixed order); sums[P] = local point count.

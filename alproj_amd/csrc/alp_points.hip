@@ -221,23 +221,74 @@ int ensure_pop_scratch(alp_points *p, int64_t P, int nblk) {
     return ALP_OK;
 }
 
-// the three timing events of a handle, all or none: a partial failure must not leave ev[1] / ev[2] NULL for good
+// the four timing events of a handle, all or none: a partial failure must not leave ev[1] .. ev[3] NULL for good
 int ensure_pop_events(alp_points *p) {
     if (p->ev[0]) return ALP_OK;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     for (auto &e : ev)
         if (hipEventCreate(&e) != hipSuccess) {
             for (auto &d : ev)
                 if (d) hipEventDestroy(d);
             return fail(ALP_EHIP, "hipEventCreate failed");
         }
-    for (int k = 0; k < 3; ++k) p->ev[k] = ev[k];
+    for (int k = 0; k < 4; ++k) p->ev[k] = ev[k];
+    return ALP_OK;
+}
+
+// ------------------------------------------------------------------ the mend pass (alp_points_set_mend)
+// One allocation for cap candidates: the compacted indices, the mended sums, the float64 records.
+int *mend_idx(const alp_points *p) { return (int *)p->mend_dev; }
+double *mend_sums(const alp_points *p) { return (double *)((char *)p->mend_dev + round_up(p->mend_cap * 4, 256)); }
+PoseRec<double> *mend_recs(const alp_points *p) { return (PoseRec<double> *)(mend_sums(p) + p->mend_cap); }
+
+int ensure_mend_scratch(alp_points *p) {
+    if (!p->mend_cnt) {
+        ALP_HIP(hipMalloc(&p->mend_cnt, sizeof(MendCount)));
+        ALP_HIP(hipMemsetAsync(p->mend_cnt, 0, sizeof(MendCount), ctx().stream));
+    }
+    if (p->mend_cap >= p->cand_cap) return ALP_OK;
+    if (p->mend_dev) hipFree(p->mend_dev);
+    p->mend_dev = nullptr;
+    p->mend_cap = 0;
+    const int64_t cap = p->cand_cap;          // a multiple of 256
+    ALP_HIP(hipMalloc(&p->mend_dev, (size_t)round_up(cap * 4, 256) + (size_t)cap * (8 + sizeof(PoseRec<double>))));
+    p->mend_cap = cap;
+    return ALP_OK;
+}
+
+// Behind the all-reduce of the float32 sums in p->sums_dev (identical on every rank, so every rank selects the same
+// candidates): every candidate whose sum is not finite gets the sum float64 arithmetic gives on the stored points.  No host
+// round trip: the count stays on the device.  `g` = host::mend_grid for (n, P); p->partials holds g.stripes x P doubles and
+// is free again (reduce_partials_kernel has read it, in stream order).
+int mend_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, const double *params_dev, const host::PopGrid &g) {
+    hipStream_t st = ctx().stream;
+    MendCount *cnt = (MendCount *)p->mend_cnt;
+    const float *x = (const float *)p->x, *y = (const float *)p->y, *z = (const float *)p->z;
+    const float *uo = (const float *)p->uo, *vo = (const float *)p->vo;
+    hipLaunchKernelGGL(mend_select_kernel, dim3(1), dim3(256), 0, st, (const double *)p->sums_dev, (int)P, params_dev, p->origin[0],
+                       p->origin[1], p->origin[2], mend_idx(p), mend_recs(p), cnt);
+    ALP_HIP(hipGetLastError());
+    if (loss_kind == ALP_LOSS_HUBER)
+        hipLaunchKernelGGL(popeval_counted_kernel<ALP_LOSS_HUBER>, dim3(g.stripes, g.tile_cols), dim3(256), 0, st, x, y, z, uo, vo, p->n,
+                           (const PoseRec<double> *)mend_recs(p), (const MendCount *)cnt, f_scale, p->partials);
+    else
+        hipLaunchKernelGGL(popeval_counted_kernel<ALP_LOSS_MEAN_DIST>, dim3(g.stripes, g.tile_cols), dim3(256), 0, st, x, y, z, uo, vo,
+                           p->n, (const PoseRec<double> *)mend_recs(p), (const MendCount *)cnt, f_scale, p->partials);
+    ALP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(mend_reduce_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, st, (const double *)p->partials, g.stripes,
+                       (int)P, (const MendCount *)cnt, mend_sums(p));
+    ALP_HIP(hipGetLastError());
+    if (int rc = comm_allreduce_sum_f64(mend_sums(p), P)) return rc;
+    hipLaunchKernelGGL(mend_scatter_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (const int *)mend_idx(p),
+                       (const double *)mend_sums(p), (const MendCount *)cnt, p->sums_dev);
+    ALP_HIP(hipGetLastError());
     return ALP_OK;
 }
 
 // the launch half of enqueue_popeval (alp_points_internal.h: popeval_launch): the records lie in p->cand_dev
 template <typename T>
-int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false) {
+int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false,
+                     const double *params_dev = nullptr) {
     using Kernel = void (*)(const T *, const T *, const T *, const T *, const T *, int64_t, const PoseRec<T> *, int, T,
                             double *, const PoseRec<T> *);
     const int which = (loss_kind == ALP_LOSS_HUBER ? 3 : 0) + (lens_free ? 2 : (shared_pose ? 1 : 0));
@@ -254,8 +305,17 @@ int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bo
     if (const char *e = getenv("ALP_POP_GRID")) sscanf(e, "%d,%d", &ov[0], &ov[1]);
     const host::PopGrid g = host::pop_grid(p->n, P, sizeof(T) == 8, lens_free ? PopCfgLF<T>::V : PopCfg<T>::V, PopCfg<T>::TC,
                                            ctx().cu_count, batched, ov[0], ov[1]);
-    if (int rc = ensure_pop_scratch(p, P, g.stripes)) return rc;
+    // the mend pass (float32 sets that asked for it) takes its partial rows from the same buffer, after the first pass is done with it
+    const bool mend = sizeof(T) == 4 && p->mend;
+    host::PopGrid mg = {0, 0};
+    if (mend) {
+        if (!params_dev) return fail(ALP_EINVAL, "population evaluation with mend on: the candidates' parameter rows are missing");
+        mg = host::mend_grid(p->n, P, PopCfg<double>::V, PopCfg<double>::TC, ctx().cu_count);
+    }
+    if (int rc = ensure_pop_scratch(p, P, g.stripes > mg.stripes ? g.stripes : mg.stripes)) return rc;
     if (int rc = ensure_pop_events(p)) return rc;
+    if (mend)
+        if (int rc = ensure_mend_scratch(p)) return rc;
     p->last_info[0] = lens_free ? ALP_POP_LENS_FREE : (shared_pose ? ALP_POP_SHARED_POSE : ALP_POP_GENERAL);
     p->last_info[1] = g.stripes;
     p->last_info[2] = g.tile_cols;
@@ -271,6 +331,13 @@ int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bo
     ALP_HIP(hipEventRecord(p->ev[1], ctx().stream));
     if (int rc = comm_allreduce_sum_f64(p->sums_dev, P + 1)) return rc;
     ALP_HIP(hipEventRecord(p->ev[2], ctx().stream));
+    p->mend_ran = mend;
+    p->mend_info[0] = mg.stripes;
+    p->mend_info[1] = mg.tile_cols;
+    if (mend) {
+        if (int rc = mend_launch(p, P, loss_kind, f_scale, params_dev, mg)) return rc;
+        ALP_HIP(hipEventRecord(p->ev[3], ctx().stream));
+    }
     p->timed = true;
     return ALP_OK;
 }
@@ -313,13 +380,28 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
     bool shared_pose = P > 1 && !lens_free;
     for (int64_t i = 1; i < P && shared_pose; ++i)
         shared_pose = memcmp(h[i].v, h[0].v, 12 * sizeof(T)) == 0;
-    if (int rc = popeval_launch_t<T>(p, P, loss_kind, f_scale, lens_free, shared_pose)) return rc;
+    // (float32 sets keep the call's parameter vectors: the argmin confirmation folds them again in float64, and so does the
+    // mend pass, on the device, from a copy uploaded beside the records)
+    if (sizeof(T) == 4) p->cand_copy.assign(cand, cand + P * ALP_NPARAM);
+    const double *params_dev = nullptr;
+    if (sizeof(T) == 4 && p->mend) {
+        if (p->mend_params_cap < P) {
+            if (p->mend_params) hipFree(p->mend_params);
+            p->mend_params = nullptr;
+            p->mend_params_cap = 0;
+            ALP_HIP(hipMalloc((void **)&p->mend_params, (size_t)p->cand_cap * ALP_NPARAM * sizeof(double)));
+            p->mend_params_cap = p->cand_cap;
+        }
+        ALP_HIP(hipMemcpyAsync(p->mend_params, p->cand_copy.data(), (size_t)P * ALP_NPARAM * sizeof(double), hipMemcpyHostToDevice,
+                               ctx().stream));
+        params_dev = p->mend_params;
+    }
+    if (int rc = popeval_launch_t<T>(p, P, loss_kind, f_scale, lens_free, shared_pose, false, params_dev)) return rc;
     ALP_HIP(hipMemcpyAsync(p->sums_host, p->sums_dev, (size_t)(P + 1) * sizeof(double),
                            hipMemcpyDeviceToHost, ctx().stream));
     p->pending_P = P;
     p->pending_loss = loss_kind;
     p->pending_f_scale = f_scale;
-    if (sizeof(T) == 4) p->cand_copy.assign(cand, cand + P * ALP_NPARAM);
     return ALP_OK;
 }
 
@@ -458,9 +540,10 @@ int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, do
 }  // namespace
 
 namespace alp {
-int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched) {
-    return p->precision == ALP_F64 ? popeval_launch_t<double>(p, P, loss_kind, f_scale, lens_free, shared_pose, batched)
-                                   : popeval_launch_t<float>(p, P, loss_kind, f_scale, lens_free, shared_pose, batched);
+int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched,
+                   const double *params_dev) {
+    return p->precision == ALP_F64 ? popeval_launch_t<double>(p, P, loss_kind, f_scale, lens_free, shared_pose, batched, params_dev)
+                                   : popeval_launch_t<float>(p, P, loss_kind, f_scale, lens_free, shared_pose, batched, params_dev);
 }
 int points_pop_reserve(alp_points *p, int64_t P) { return ensure_pop_scratch(p, P, 0); }
 }  // namespace alp
@@ -609,6 +692,8 @@ int alp_points_destroy(alp_points_t *p) {
     if (p->sums_host) hipHostFree(p->sums_host);
     if (p->conf_dev) hipFree(p->conf_dev);
     if (p->conf_host) hipHostFree(p->conf_host);
+    for (void *q : {p->mend_cnt, p->mend_dev, (void *)p->mend_params})
+        if (q) hipFree(q);
     for (auto &e : p->ev)
         if (e) hipEventDestroy(e);
     delete p;
@@ -856,6 +941,11 @@ int alp_eval_population_timing(alp_points_t *p, float *kernel_ms, float *allredu
     float a = 0, b = 0;
     ALP_HIP(hipEventElapsedTime(&a, p->ev[0], p->ev[1]));
     ALP_HIP(hipEventElapsedTime(&b, p->ev[1], p->ev[2]));
+    if (p->mend_ran) {                 // the mend pass runs behind the all-reduce: its kernels (and its own all-reduce) count as kernel time
+        float m = 0;
+        ALP_HIP(hipEventElapsedTime(&m, p->ev[2], p->ev[3]));
+        a += m;
+    }
     if (kernel_ms) *kernel_ms = a;
     if (allreduce_ms) *allreduce_ms = b;
     return ALP_OK;
@@ -865,6 +955,36 @@ int alp_eval_population_info(alp_points_t *p, int64_t info[3]) {
     ALP_REQUIRE(p && info, "NULL argument");
     if (!p->timed) return fail(ALP_ESTATE, "alp_eval_population_info: no population evaluation yet");
     for (int k = 0; k < 3; ++k) info[k] = p->last_info[k];
+    return ALP_OK;
+}
+
+int alp_points_set_mend(alp_points_t *p, int enable) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p, "points handle is NULL");
+    if (p->pending_P > 0 || p->loop_pending)
+        return fail(ALP_ESTATE, "alp_points_set_mend: an evaluation or a device loop on this point set has not been waited for");
+    const bool on = enable != 0;
+    // (a float64 set takes the setting and never runs the pass: its second walk gives the reference's values already)
+    if (on && !p->mend && p->mend_cnt) ALP_HIP(hipMemsetAsync(p->mend_cnt, 0, sizeof(MendCount), ctx().stream));
+    p->mend = on;
+    return ALP_OK;
+}
+
+int alp_eval_population_mended(alp_points_t *p, int64_t info[4]) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p && info, "NULL argument");
+    if (!p->timed) return fail(ALP_ESTATE, "alp_eval_population_mended: no population evaluation yet");
+    if (p->pending_P > 0 || p->loop_pending)
+        return fail(ALP_ESTATE, "alp_eval_population_mended: wait for the pending evaluation or device loop first");
+    MendCount c = {0, 0};
+    if (p->mend_cnt) {
+        ALP_HIP(hipMemcpyAsync(&c, p->mend_cnt, sizeof(c), hipMemcpyDeviceToHost, ctx().stream));
+        ALP_HIP(hipStreamSynchronize(ctx().stream));
+    }
+    info[0] = p->mend_ran ? c.last : 0;
+    info[1] = c.total;
+    info[2] = p->mend_ran ? p->mend_info[0] : 0;
+    info[3] = p->mend_ran ? p->mend_info[1] : 0;
     return ALP_OK;
 }
 

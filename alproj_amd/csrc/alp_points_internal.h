@@ -37,11 +37,21 @@ struct alp_points {
     double pending_f_scale = 0;
     std::vector<double> cand_copy;   // the P x 25 parameter vectors of the pending call (argmin confirmation)
     // argmin confirmation (float32 sets): float64 records, partial sums and sums of up to CONFIRM_MAX candidates
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // last population evaluation: before the kernels, after them, after the all-reduce
+    // last population evaluation: before the kernels, after them, after the all-reduce, after the mend pass
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
     void *conf_dev = nullptr;
     int conf_nblk = 0;
     double *conf_host = nullptr;   // pinned, CONFIRM_MAX + 1
+    // the mend pass of a float32 set (alp_points_set_mend; alp_points.hip: mend_launch)
+    bool mend = false;
+    void *mend_cnt = nullptr;      // MendCount: the last pass's count and the total since mend was enabled
+    void *mend_dev = nullptr;      // mend_cap x (index, mended sum, PoseRec<double>)
+    int64_t mend_cap = 0;
+    double *mend_params = nullptr; // the host path's P x 25 parameter rows (the device loop passes its own)
+    int64_t mend_params_cap = 0;
+    bool mend_ran = false;         // the last population evaluation ran the pass
+    int64_t mend_info[2] = {0, 0}; // its stripes and tile columns
     // device loops of the CMA-ES generation (alp_cma.hip) built on this set: told when it is destroyed; while one of them has
     // generations enqueued (loop_pending) they use the population scratch above, and an alp_eval_population_enqueue is refused
     std::vector<alp_cma_t *> loops;
@@ -58,7 +68,10 @@ namespace alp {
 // `batched` (the device loop's multi-start launch, K starts x P candidates): the stripe count is capped so that the partial sums
 // (stripes x P doubles) stay within host::POP_BATCHED_PARTIALS_BYTES, and when the stripes alone do not fill the GPU (a GCP-sized set
 // has a handful of rows) the grid gets candidate-tile columns up to four workgroups per CU.  Every other launch keeps its grid.
-int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false);
+// `params_dev`: the P x 25 float64 parameter rows of the candidates on the device, which the mend pass folds again in float64 --
+// needed when p->mend is set on a float32 set, unused otherwise.
+int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false,
+                   const double *params_dev = nullptr);
 // population scratch (records, sums) for P candidates
 int points_pop_reserve(alp_points *p, int64_t P);
 // alp_points_destroy: a device loop built on the set loses it (its later calls return ALP_ESTATE)

@@ -359,6 +359,13 @@ void check_plan() {
                                 CHECK(i.stripes == none.stripes && i.tile_cols == none.tile_cols, "override %d,%d not ignored", bad.first, bad.second);
                             }
                         }
+            // mend_grid: planned for all P candidates -- the tile columns cover them, the stripes are rows, the partial rows fit
+            for (int64_t P : Ps) {
+                const host::PopGrid m = host::mend_grid(n, P, 5, TC, cu);
+                CHECK(m.stripes >= 1 && m.stripes <= rows && (int64_t)m.tile_cols * TC >= P && (int64_t)(m.tile_cols - 1) * TC < P,
+                      "mend_grid(%" PRId64 ", %" PRId64 ", cu=%d) = %d x %d", n, P, cu, m.stripes, m.tile_cols);
+                CHECK((int64_t)m.stripes * P * 8 <= host::POP_BATCHED_PARTIALS_BYTES, "mend partial sums: %d stripes x %" PRId64, m.stripes, P);
+            }
             for (int64_t pairs : {1, 2, 3, 11, 21, 22, 23, 4095, 4096}) {
                 const int64_t c = host::stage_chunk_points(n, pairs);
                 CHECK(c >= 1 && c <= n && (c % 1024 == 0 || c == n), "stage_chunk_points(%" PRId64 ", %" PRId64 ") = %" PRId64, n, pairs, c);
@@ -546,6 +553,7 @@ int canary(const char *which) {
 // --plan: one query per argument, or per line of stdin when there is none: n,P,f32|f64,V,TC,cu,batched,pairs[,stripes,tile_cols]
 // (the last two: an ALP_POP_GRID pair) -> "stripes tile_cols chunk_points stream_grid confirm_grid";
 // normal,n,cu -> "blocks groups_per" of normal_grid
+// mend,n,P,V,TC,cu -> "stripes tile_cols" of mend_grid
 // frame,implicit,grid_h,grid_w,n_tri,w,h,cu,tile_w,tile_h -> "tiles_x tiles plan_grid grid_wgs parked_wgs[0] parked_wgs[1] general_wgs large_wgs
 //   index_grid resolve_grid tile_bounds_bytes tile_lists_bytes" of frame_plan
 // queues,ALP_QUEUE_CAP text or '-' -> "cap small large cells small_b large_b cells_b": the start capacities
@@ -599,6 +607,17 @@ int plan_query(const char *q) {
         }
         const host::NormalGrid g = host::normal_grid(nn, ncu);
         printf("%d %lld\n", g.blocks, (long long)g.groups_per);
+        return 0;
+    }
+    if (!strncmp(q, "mend,", 5)) {
+        long long nn = -1, PP = 0;
+        int mV = 0, mTC = 0, mcu = 0;
+        if (sscanf(q + 5, "%lld,%lld,%d,%d,%d", &nn, &PP, &mV, &mTC, &mcu) != 5 || nn < 0 || PP < 1 || mV < 1 || mTC < 1 || mcu < 1) {
+            fprintf(stderr, "bad plan query: %s\n", q);
+            return 2;
+        }
+        const host::PopGrid g = host::mend_grid(nn, PP, mV, mTC, mcu);
+        printf("%d %d\n", g.stripes, g.tile_cols);
         return 0;
     }
     long long n = 0, P = 0, pairs = 0;

@@ -122,7 +122,27 @@ inline PopGrid pop_grid(int64_t n, int64_t P, bool is_f64, int V, int TC, int cu
     return {nblk, ytiles};
 }
 
-// The grid of normal_kernel (alp_normal_equations): `blocks` workgroups, each over a stripe of `groups_per` whole groups of 256
+// The grid of the mend pass over a float32 set (alp_points_set_mend; alp_points.hip: mend_launch): popeval_counted_kernel,
+// float64 arithmetic with V = PopCfg<double>::V rows per group.  The number of candidates it evaluates is known on the device
+// only, so the grid is planned for the worst case, all P of them: one column per tile of TC candidates (tile_cols x TC >= P; a
+// workgroup whose tile lies beyond the count returns at once, so the columns in use are ceil(count / TC)) times `stripes`
+// stripes of whole rows.  The stripes follow the float64 rule of pop_grid -- at least one round of the three resident
+// workgroups per CU, at most 24 per CU, never more than rows, partial sums (stripes x P doubles) within 128 MB -- and between
+// those bounds aim at four groups of V rows each: a column's workgroup stages its 128 records (32 KB) once per stripe, and a
+// stripe of one or two groups would read about as many bytes of records as of points.
+inline PopGrid mend_grid(int64_t n, int64_t P, int V, int TC, int cu_count) {
+    const int64_t rows = (n + 255) / 256, tiles = (P + TC - 1) / TC;
+    const int64_t lo = (int64_t)cu_count * 3, hi = (int64_t)cu_count * 24;
+    int64_t nblk = (rows + 4 * V - 1) / (4 * V);
+    nblk = nblk < lo ? lo : (nblk > hi ? hi : nblk);
+    const int64_t cap = POP_BATCHED_PARTIALS_BYTES / (8 * (P > 0 ? P : 1));
+    if (nblk > cap) nblk = cap;
+    if (nblk > rows) nblk = rows;
+    if (nblk < 1) nblk = 1;
+    return {(int)nblk, (int)(tiles > 0 ? tiles : 1)};
+}
+
+// The grid of normal_kernel (alp_normal_equations):`blocks` workgroups, each over a stripe of `groups_per` whole groups of 256
 // points (the last stripe may be shorter and its last group ragged); every workgroup writes ONE row of partial sums.
 // Workgroups: NORMAL_WG_PER_CU per CU -- two rounds of the three a CU holds at once (50 KB of LDS each) -- and never more than
 // NORMAL_MAX_BLOCKS, which keeps the partial rows (at most 300 doubles each) below 5 MB whatever the device.  The stripes are

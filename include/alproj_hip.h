@@ -255,6 +255,18 @@ int alp_normal_equations(alp_points_t *pts, const double params[ALP_NPARAM], con
  * second walk can mend.  tests/test_gpu_points.py constructs the case in both modes.
  * Lens-free populations (ALP_POP_LENS_FREE, below) take the second walk in either precision: it restores the NaN the
  * reference's k * inf produces at a vertex at the camera.
+ * Mended losses (float32 point sets, alp_points_set_mend; off by default): with mend on, every candidate whose float32 sum
+ * comes out infinite or NaN is evaluated again on the device -- no host round trip, in the device loop as well -- in float64
+ * ARITHMETIC ON THE STORED FLOAT32 POINTS and observations, second walk included, and loss_out holds that value for it;
+ * every other candidate keeps its float32 loss bit for bit.  A wild float32 population is then finite wherever float64
+ * arithmetic is: a vertex next to a candidate's camera plane has a squared pixel distance above FLT_MAX in float32 (inf -
+ * inf = NaN follows), which float64 holds with room to spare.  A mended loss is exact for the stored inputs (1e-7 relative
+ * and better against float64 arithmetic on the same rounded points); it is NOT the reference's loss to 1e-5, because the
+ * reference reads the unrounded points: float64 arithmetic on the fixture's points and observations rounded as a float32 set
+ * stores them differs from the fixture's own losses by 4.2e-4 relative at a candidate whose smallest lens denominator is
+ * 3.3e-4, and by 1.5e-4 at one with a depth ratio of 5e-5.  That floor is the float32 input's, and no re-evaluation on the
+ * stored planes lowers it.  A candidate whose re-evaluation is itself not finite keeps that value, which is the reference's
+ * own: +inf at an exact pole (not the NaN above), NaN at a vertex at the camera.
  * argmin_out == NULL: losses only, no confirmation pass (the reference uses the argmin of the LAST
  * generation only, src/alproj/optimize.py:427; every earlier generation needs the losses for
  * CMA.tell and nothing else).
@@ -273,7 +285,8 @@ int alp_eval_population_enqueue(alp_points_t *pts, const double *cand, int64_t P
 int alp_eval_population_wait(alp_points_t *pts, double *loss_out, int64_t *argmin_out);
 /* Device time of the last completed population evaluation of this handle, from HIP events on the
  * library stream: kernel_ms = the evaluation and reduction kernels, allreduce_ms = the
- * ncclAllReduce(sum, double, P+1) behind them (about 0 without a communicator).  What bench.py
+ * ncclAllReduce(sum, double, P+1) behind them (about 0 without a communicator); when the evaluation ran the mend pass
+ * (alp_points_set_mend), kernel_ms includes it.  What bench.py
  * reports as the collective's share of a CMA-ES generation (src/alproj/optimize.py:418-424 has no
  * counterpart: the reference is one process). */
 int alp_eval_population_timing(alp_points_t *pts, float *kernel_ms, float *allreduce_ms);
@@ -286,6 +299,17 @@ int alp_eval_population_timing(alp_points_t *pts, float *kernel_ms, float *allre
  * precision mode (float64: 1e-12 relative; float32: 2e-6), not bit for bit. */
 enum alp_pop_variant { ALP_POP_GENERAL = 0, ALP_POP_SHARED_POSE = 1, ALP_POP_LENS_FREE = 2 };
 int alp_eval_population_info(alp_points_t *pts, int64_t info[3]);
+/* The mend pass of a float32 point set (see alp_eval_population): a per-handle setting, off at creation.  ALP_ESTATE while an
+ * evaluation is enqueued or a device loop on the set has generations pending.  A float64 set accepts the call and never runs
+ * the pass (its second walk gives the reference's values already).  Enabling it (from off) clears the running total below.
+ * With a communicator the pass adds one all-reduce of P doubles per evaluation; every rank must use the same setting.
+ * alp_eval_population_timing counts the pass (select, float64 evaluation, reduction, its all-reduce, scatter) as kernel time. */
+int alp_points_set_mend(alp_points_t *pts, int enable);
+/* info[0] = candidates the mend pass re-evaluated in the last completed population evaluation (a device loop: in its last
+ * generation; 0 when that evaluation ran no pass), info[1] = their total since mend was enabled, info[2] = stripes and
+ * info[3] = candidate-tile columns of the pass's launch grid (planned for all P candidates; 0, 0 without a pass).
+ * ALP_ESTATE before any evaluation and while one is pending. */
+int alp_eval_population_mended(alp_points_t *pts, int64_t info[4]);
 
 /* The candidate sampler of the CMA-ES loop on the device: replaces the `population_size` calls of
  * `optimizer.ask()` per generation, src/alproj/optimize.py:420-421 (third-party cmaes==0.12.0,
