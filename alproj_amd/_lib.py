@@ -17,6 +17,7 @@ ALP_F32, ALP_F64, ALP_I32, ALP_I64, ALP_U8, ALP_U16 = 0, 1, 2, 3, 4, 5
 LOSS_MEAN_DIST, LOSS_HUBER = 0, 1
 # alp_normal_equations: scipy.optimize.least_squares' losses of one scalar residual (enum alp_normal_loss)
 NORMAL_LOSSES = {"linear": 0, "soft_l1": 1, "huber": 2, "cauchy": 3}
+NORMAL_BATCH_MAX = 1024         # alp_normal_equations_batch: poses per call
 NPARAM = 25
 UNIQUE_ID_BYTES = 128
 
@@ -204,6 +205,7 @@ _SIGNATURES = {
     "alp_residuals_batch": [_c_void_p, _c_dp, _c_i64, _c_dp],
     "alp_jacobian": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_int, _c_dp],
     "alp_normal_equations": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_int, _c_double, _c_dp],
+    "alp_normal_equations_batch": [_c_void_p, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_int, _c_int, _c_double, _c_dp],
     "alp_eval_population": [_c_void_p, _c_dp, _c_i64, _c_int, _c_double, _c_dp, ctypes.POINTER(_c_i64)],
     "alp_eval_population_enqueue": [_c_void_p, _c_dp, _c_i64, _c_int, _c_double],
     "alp_eval_population_wait": [_c_void_p, _c_dp, ctypes.POINTER(_c_i64)],
@@ -565,6 +567,28 @@ class Points:
         G[np.triu_indices(d)] = out[:tri]
         G = G + np.triu(G, 1).T
         return G, out[tri:tri + d].copy(), 0.5 * fs * fs * float(out[tri + d]), int(out[tri + d + 1])
+
+    def normal_equations_batch(self, cand, target_idx, loss="linear", f_scale=1.0):
+        """-> (G (B, D, D), g (B, D), cost (B,), n): ``normal_equations`` at the B parameter vectors ``cand`` (B, 25),
+        1 <= B <= NORMAL_BATCH_MAX, formed in one launch (alp_normal_equations_batch); targets, loss and f_scale are shared by
+        the rows.  Row b is what ``normal_equations(cand[b], ...)`` returns, to the order of the additions (bit for bit up to
+        256 points), and does not depend on the other rows.  ValueError, before the library is called, for what
+        ``normal_equations`` refuses and for a ``cand`` of another shape."""
+        idx = normal_targets_check(target_idx)
+        kind, fs = normal_loss_check(loss, f_scale)
+        cand = np.ascontiguousarray(cand, dtype=np.float64)
+        if cand.ndim != 2 or cand.shape[1] != NPARAM or not 1 <= cand.shape[0] <= NORMAL_BATCH_MAX:
+            raise ValueError(f"cand must have shape (B, 25) with 1 <= B <= {NORMAL_BATCH_MAX}")
+        b, d = cand.shape[0], len(idx)
+        tri = d * (d + 1) // 2
+        out = np.empty((b, tri + d + 2), dtype=np.float64)
+        check(self._lib.alp_normal_equations_batch(self._h, as_dp(cand), b, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), d, kind,
+                                                   fs, as_dp(out)))
+        iu = np.triu_indices(d)
+        G = np.zeros((b, d, d), dtype=np.float64)
+        G[:, iu[0], iu[1]] = out[:, :tri]
+        G = G + np.triu(G, 1).transpose(0, 2, 1)
+        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], int(out[0, tri + d + 1])
 
     def eval_population(self, cand, loss_kind, f_scale=10.0, want_argmin=True):
         """-> (losses (P,), argmin).  ``want_argmin=False``: losses only -- the library then skips the float64 confirmation

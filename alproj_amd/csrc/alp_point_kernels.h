@@ -745,11 +745,14 @@ __device__ __forceinline__ double normal_rho(double z, double &s, double &w) {
     return rho;
 }
 
+// The body of normal_kernel and normal_batch_kernel: the workgroup's stripe `stripe` of `groups_per` groups under `plan`, its
+// sums to row `out_row` of `partials` (T doubles each).  `stripe`, `plan` and `out_row` are the same in every lane (the plan comes in by
+// scalar loads).
 template <typename TS, int LOSS>
-__global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
-                                                     const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
-                                                     int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plan,
-                                                     double *__restrict__ partials) {
+__device__ __forceinline__ void normal_body(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+                                            const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n, int64_t groups_per,
+                                            double inv_f_scale, const JacPlan *__restrict__ plan, int64_t stripe,
+                                            double *__restrict__ partials, int64_t out_row) {
     __shared__ double s_tile[4][NRM_TILE];
     __shared__ double s_cost[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -763,7 +766,7 @@ __global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, c
     nrm_v4d a00 = {0, 0, 0, 0}, a01 = {0, 0, 0, 0}, a11 = {0, 0, 0, 0};
     double cost = 0.0;
 
-    const int64_t beg = (int64_t)blockIdx.x * groups_per * 256;
+    const int64_t beg = stripe * groups_per * 256;
     const int64_t end = (beg + groups_per * 256 < n) ? beg + groups_per * 256 : n;
     for (int64_t base = beg; base < end; base += 256) {
         const int64_t i = base + tid;
@@ -831,8 +834,58 @@ __global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, c
             const int o = row * 32 + col;
             v = ((s_tile[0][o] + s_tile[1][o]) + s_tile[2][o]) + s_tile[3][o];
         }
-        partials[(int64_t)blockIdx.x * T + t] = v;
+        partials[out_row * T + t] = v;
     }
+}
+
+template <typename TS, int LOSS>
+__global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+                                                     const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
+                                                     int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plan,
+                                                     double *__restrict__ partials) {
+    normal_body<TS, LOSS>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plan, (int64_t)blockIdx.x, partials, (int64_t)blockIdx.x);
+}
+
+// K3n for B poses over the same points (alp_normal_equations_batch): one workgroup per (stripe, pose) pair of
+// host::normal_batch_grid, under plans[pose]; its row of partials is row `stripe` of pose `pose`:
+// partials[(pose * stripes + stripe) * T ..).  Which grid index carries the pose is the launch's choice (`pose_in_x`: the
+// workgroups of one stripe under all poses are dispatched next to each other, so that the stripe's points are fetched from HBM
+// once and found in the cache by the other poses); the sums do not depend on it.
+constexpr int NORMAL_BATCH_POSE_IN_X = 1;
+template <typename TS, int LOSS>
+__global__ __launch_bounds__(256) void normal_batch_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+                                                           const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
+                                                           int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
+                                                           int pose_in_x, double *__restrict__ partials) {
+    const int pose = pose_in_x ? blockIdx.x : blockIdx.y, stripe = pose_in_x ? blockIdx.y : blockIdx.x;
+    const int stripes = pose_in_x ? gridDim.y : gridDim.x;
+    normal_body<TS, LOSS>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
+                          (int64_t)pose * stripes + stripe);
+}
+
+// sums[q * (T + 1) + c] = sum over the stripes of pose q's partial rows (reduce_partials_kernel's order: 8 row-groups, each
+// over every 8th stripe, then the 8 in order), sums[q * (T + 1) + T] = the local point count: row q has
+// alp_normal_equations' layout.  blockIdx.y = the pose; one workgroup handles 32 sums x 8 row-groups.
+__global__ __launch_bounds__(256) void reduce_normal_batch_kernel(const double *__restrict__ partials, int stripes, int T, double n_local,
+                                                                  double *__restrict__ sums) {
+    __shared__ double s[8][32];
+    const int cl = threadIdx.x & 31;
+    const int g = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cl;
+    const double *rows = partials + (int64_t)blockIdx.y * stripes * T;
+    double *out = sums + (int64_t)blockIdx.y * (T + 1);
+    double acc = 0.0;
+    if (c < T)
+        for (int b = g; b < stripes; b += 8) acc += rows[(int64_t)b * T + c];
+    s[g][cl] = acc;
+    __syncthreads();
+    if (g == 0 && c < T) {
+        double t = s[0][cl];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) t += s[k][cl];
+        out[c] = t;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = n_local;
 }
 
 // TS = element type of the planes in HBM, T = arithmetic type (TS = float with T = double is the

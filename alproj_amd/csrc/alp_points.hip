@@ -5,6 +5,7 @@
 //   residual_batch_kernel  observed - projected for B poses, interleaved (least-squares path)
 //   jacobian_kernel  d projected / d parameters for one pose, exact (least-squares path)
 //   normal_kernel    the same rows contracted to J^T J, J^T r and the cost where they are made (f64 MFMA; least-squares path)
+//   normal_batch_kernel  the same for B poses in one launch, one workgroup per (stripe, pose) pair
 //
 // Reference arithmetic: src/alproj/optimize.py  project :122-155, _distort :98-120,
 // rmse :157-178, huber_loss :181-212, compute_residuals :215-237, and the generation loop
@@ -16,7 +17,7 @@
 // element type T (float: 20 B/vertex streamed per projection pass; double: 40 B/vertex).
 // Planes are padded to a multiple of 1024 elements so that 16-byte vector accesses and
 // whole-workgroup tiles never leave the allocation.
-// The launch shapes (popeval_kernel's stripes x tiles, the residual / Jacobian chunks, normal_kernel's stripes, streaming grids, RowDiv) are planned in
+// The launch shapes (popeval_kernel's stripes x tiles, the residual / Jacobian chunks, normal_kernel's stripes (and their share per pose of a batch), streaming grids, RowDiv) are planned in
 // host/alp_plan.h, HIP-free and checked on the CPU; this unit allocates, records events and launches what it plans.
 #include "alp_internal.h"
 
@@ -537,6 +538,45 @@ int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, do
     return ALP_OK;
 }
 
+// alp_normal_equations_batch: normal_batch_kernel over host::normal_batch_grid's stripes x the B poses, reduce_normal_batch_kernel
+// over each pose's rows, one all-reduce and one copy of the B x (T + 1) sums.  The scratch holds the B plans, the partial rows
+// and the sums.  ALP_NORMAL_BATCH_ORDER = "stripe" | "pose" (a development switch, tools/probe_normal_batch.py) names the grid
+// index that runs fastest; the sums do not depend on it.
+template <typename TS>
+int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss, double f_scale, double *out) {
+    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, int, double *);
+    static const Kernel kernels[4] = {normal_batch_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1>,
+                                      normal_batch_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_kernel<TS, ALP_NORMAL_CAUCHY>};
+    const int64_t B = (int64_t)plans.size();
+    const int D = plans[0].D, T = D * (D + 1) / 2 + D + 1;
+    const host::NormalGrid g = host::normal_batch_grid(p->n, B, ctx().cu_count);
+    const size_t plan_bytes = round_up((int64_t)(B * sizeof(JacPlan)), 256);
+    char *dev = nullptr;
+    if (int rc = scratch_reserve(plan_bytes + ((size_t)B * g.blocks * T + (size_t)B * (T + 1)) * sizeof(double), (void **)&dev)) return rc;
+    JacPlan *plans_dev = (JacPlan *)dev;
+    double *partials = (double *)(dev + plan_bytes), *sums = partials + (size_t)B * g.blocks * T;
+    hipStream_t st = ctx().stream;
+    if (g.blocks > 0) {
+        const char *order = getenv("ALP_NORMAL_BATCH_ORDER");
+        const int pose_in_x = order ? !strcmp(order, "pose") : NORMAL_BATCH_POSE_IN_X;
+        const dim3 grid = pose_in_x ? dim3((unsigned)B, (unsigned)g.blocks) : dim3((unsigned)g.blocks, (unsigned)B);
+        ALP_HIP(hipMemcpyAsync(plans_dev, plans.data(), (size_t)B * sizeof(JacPlan), hipMemcpyHostToDevice, st));
+        ktime_begin();
+        hipLaunchKernelGGL(kernels[loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
+                           (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials);
+        hipLaunchKernelGGL(reduce_normal_batch_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)B), dim3(256), 0, st, partials, g.blocks, T,
+                           (double)p->n, sums);
+        ktime_end();
+        ALP_HIP(hipGetLastError());
+    } else {
+        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)B * (T + 1) * sizeof(double), st));   // an empty shard still joins the all-reduce
+    }
+    if (int rc = comm_allreduce_sum_f64(sums, B * (T + 1))) return rc;
+    ALP_HIP(hipMemcpyAsync(out, sums, (size_t)B * (T + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    ALP_HIP(hipStreamSynchronize(st));           // the plans must outlive their copy too
+    return ALP_OK;
+}
+
 }  // namespace
 
 namespace alp {
@@ -831,6 +871,21 @@ int alp_normal_equations(alp_points_t *p, const double params[ALP_NPARAM], const
     if (int rc = jacobian_plan(params, p->origin, target_idx, D, 1, &plan)) return rc;
     if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations: observed uv not set");
     return p->precision == ALP_F64 ? normal_impl<double>(p, plan, loss, f_scale, out) : normal_impl<float>(p, plan, loss, f_scale, out);
+}
+
+int alp_normal_equations_batch(alp_points_t *p, const double *params, int64_t B, const int32_t *target_idx, int D, int loss,
+                               double f_scale, double *out) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p && params && out, "NULL argument");
+    ALP_REQUIRE(B >= 1 && B <= host::NORMAL_BATCH_MAX, "B must be 1..1024");
+    ALP_REQUIRE(loss >= ALP_NORMAL_LINEAR && loss <= ALP_NORMAL_CAUCHY, "unknown loss");
+    ALP_REQUIRE(f_scale > 0 && std::isfinite(f_scale), "f_scale must be a positive finite number");
+    std::vector<JacPlan> plans((size_t)B);
+    for (int64_t b = 0; b < B; ++b)
+        if (int rc = jacobian_plan(params + b * ALP_NPARAM, p->origin, target_idx, D, 1, &plans[(size_t)b])) return rc;
+    if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations_batch: observed uv not set");
+    return p->precision == ALP_F64 ? normal_batch_impl<double>(p, plans, loss, f_scale, out)
+                                   : normal_batch_impl<float>(p, plans, loss, f_scale, out);
 }
 
 // obs_b / prj_b NULL: that array is interleaved (n x 2 row-major); else a = the u column, b = the v column

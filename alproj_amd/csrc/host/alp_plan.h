@@ -161,6 +161,26 @@ inline NormalGrid normal_grid(int64_t n, int cu_count) {
     return {(int)((groups + per - 1) / per), per};
 }
 
+// The grid of normal_batch_kernel (alp_normal_equations_batch): B poses over the same points, one workgroup per (stripe, pose)
+// pair, `blocks` stripes per pose -- blocks x B workgroups, each writing ONE row of partial sums.  The workgroups normal_grid
+// aims at are shared out among the poses: a pose gets ceil(want / B) stripes, at least one, at most one per group; the stripes
+// are then made as long as they must be and those left without a group are dropped, as in normal_grid.  B = 1 is normal_grid
+// itself; blocks x B < want + B, so the partial rows (300 doubles each) stay below 7.4 MB up to NORMAL_BATCH_MAX poses.
+// n = 0 or B < 1: no launch.
+constexpr int NORMAL_BATCH_MAX = 1024;
+
+inline NormalGrid normal_batch_grid(int64_t n, int64_t B, int cu_count) {
+    const int64_t groups = (n + 255) / 256;
+    if (groups <= 0 || B < 1) return {0, 0};
+    int64_t want = (int64_t)cu_count * NORMAL_WG_PER_CU;
+    if (want > NORMAL_MAX_BLOCKS) want = NORMAL_MAX_BLOCKS;
+    int64_t stripes = (want + B - 1) / B;
+    if (stripes < 1) stripes = 1;
+    if (stripes > groups) stripes = groups;
+    const int64_t per = (groups + stripes - 1) / stripes;
+    return {(int)((groups + per - 1) / per), per};
+}
+
 // ------------------------------------------------------------------ the render frame (alp_raster.hip)
 // The launch shapes of one frame.  (tile_w, tile_h) = the cells of a raster_grid_kernel tile (GT_W x GT_H); the two
 // blocks-per-CU figures are the tunables next to raster_kernel and resolve_kernel.

@@ -11,7 +11,7 @@ here                          reference                                device en
 ``compute_residuals``         optimize.py:215-237                      alp_residuals
 ``bounds_to_array``           optimize.py:249-276                      (host, D <= 21 scalars)
 ``CMAOptimizer.optimize``     optimize.py:359-439                      alp_eval_population, alp_cma_*
-``LsqOptimizer.optimize``     optimize.py:467-539                      alp_residuals; method="normal": alp_normal_equations
+``LsqOptimizer.optimize``     optimize.py:467-539                      alp_residuals; method="normal": alp_normal_equations(_batch)
 ``parameter_covariance``      (none: standard errors of a fit)         alp_jacobian, alp_residuals; "normal": alp_normal_equations
 ``intrinsic_mat`` etc.        optimize.py:8-96                         (host, 3x3 / 4x4)
 ============================  =======================================  ======================
@@ -38,7 +38,7 @@ from .cma import CMA
 
 __all__ = ["intrinsic_mat", "extrinsic_mat", "project", "rmse", "huber_loss",
            "compute_residuals", "DEFAULT_BOUND_WIDTHS", "bounds_to_array", "BaseOptimizer",
-           "CMAOptimizer", "LsqOptimizer", "start_seeds", "best_start", "normal_lm"]
+           "CMAOptimizer", "LsqOptimizer", "start_seeds", "best_start", "normal_lm", "normal_lm_batch"]
 
 
 # ------------------------------------------------------------------------------------------
@@ -534,28 +534,15 @@ class CMAOptimizer(BaseOptimizer):
     F64_FINAL_MAX_POINTS = F64_MAX_POINTS
 
 
-def normal_lm(fun, x0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None):
-    """Bounded Levenberg-Marquardt on the normal equations.  ``fun(x) -> (G, g, cost)``: G = J^T J (D, D), g = J^T r (D,),
-    cost = the objective (0.5 r^T r for the linear loss), all at x -- ``Points.normal_equations`` on the device, or any
-    oracle.  Minimises cost over lower <= x <= upper (either may be infinite).
-
-    Damping (Nielsen): mu_0 = 1e-3 max diag G; an accepted step with gain ratio rho = actual / predicted reduction gives
-    mu *= max(1/3, 1 - (2 rho - 1)^3), nu = 2; a failed one mu *= nu, nu *= 2.  The damping matrix is
-    mu diag(scale^2) / max(scale^2) with scale the running maximum of sqrt(diag G) (Marquardt's scaling, kept monotone).
-    Solve: Cholesky of the damped matrix scaled to a unit diagonal; a factorisation that fails is a failed step.
-    Bounds: a variable on a bound whose gradient pushes outward is left out of the solve for that iteration; the trial point
-    is clipped into the box and the predicted reduction is that of the clipped step.
-    A step is accepted only when the new cost is finite and smaller.
-    Stopping, with scipy.optimize.least_squares' names and status codes: 1 ``gtol`` (the infinity norm of g over the free
-    variables), 2 ``ftol`` (actual reduction < ftol * cost on a step with rho > 0.25), 3 ``xtol`` (|step| < xtol (xtol + |x|)),
-    4 both, 0 ``max_nfev`` evaluations (default 100 D), -1 the cost at x0 is not finite.
-
-    Returns a dict: x, cost, grad_norm, iterations (accepted steps), evaluations, status."""
+def _normal_lm_steps(x0, lower, upper, ftol, xtol, gtol, max_nfev):
+    """``normal_lm`` as a state machine: a generator that yields the next trial point, receives ``(G, g, cost)`` there and
+    returns (StopIteration.value) the result dict.  Between two yields it may raise the damping several times (failed solves
+    need no evaluation)."""
     x = np.clip(np.asarray(x0, dtype=np.float64), lower, upper)
     lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
     d = len(x)
     max_nfev = 100 * d if max_nfev is None else int(max_nfev)
-    G, g, cost = fun(x)
+    G, g, cost = yield x
     nfev, iterations, status = 1, 0, None
 
     def free_of(x, g):
@@ -607,7 +594,7 @@ def normal_lm(fun, x0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfe
                 status = 3
                 break
             continue
-        G_new, g_new, cost_new = fun(x_new)
+        G_new, g_new, cost_new = yield x_new
         nfev += 1
         actual = cost - cost_new
         step_norm, x_norm = float(np.linalg.norm(step)), float(np.linalg.norm(x))
@@ -627,6 +614,59 @@ def normal_lm(fun, x0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfe
     free = free_of(x, g)
     return dict(x=x, cost=float(cost), grad_norm=float(np.max(np.abs(g[free]))) if free.any() else 0.0,
                 iterations=iterations, evaluations=nfev, status=status)
+
+
+
+
+def normal_lm(fun, x0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None):
+    """Bounded Levenberg-Marquardt on the normal equations.  ``fun(x) -> (G, g, cost)``: G = J^T J (D, D), g = J^T r (D,),
+    cost = the objective (0.5 r^T r for the linear loss), all at x -- ``Points.normal_equations`` on the device, or any
+    oracle.  Minimises cost over lower <= x <= upper (either may be infinite).
+
+    Damping (Nielsen): mu_0 = 1e-3 max diag G; an accepted step with gain ratio rho = actual / predicted reduction gives
+    mu *= max(1/3, 1 - (2 rho - 1)^3), nu = 2; a failed one mu *= nu, nu *= 2.  The damping matrix is
+    mu diag(scale^2) / max(scale^2) with scale the running maximum of sqrt(diag G) (Marquardt's scaling, kept monotone).
+    Solve: Cholesky of the damped matrix scaled to a unit diagonal; a factorisation that fails is a failed step.
+    Bounds: a variable on a bound whose gradient pushes outward is left out of the solve for that iteration; the trial point
+    is clipped into the box and the predicted reduction is that of the clipped step.
+    A step is accepted only when the new cost is finite and smaller.
+    Stopping, with scipy.optimize.least_squares' names and status codes: 1 ``gtol`` (the infinity norm of g over the free
+    variables), 2 ``ftol`` (actual reduction < ftol * cost on a step with rho > 0.25), 3 ``xtol`` (|step| < xtol (xtol + |x|)),
+    4 both, 0 ``max_nfev`` evaluations (default 100 D), -1 the cost at x0 is not finite.
+
+    Returns a dict: x, cost, grad_norm, iterations (accepted steps), evaluations, status."""
+    steps = _normal_lm_steps(x0, lower, upper, ftol, xtol, gtol, max_nfev)
+    try:
+        x = next(steps)
+        while True:
+            x = steps.send(fun(x))
+    except StopIteration as stop:
+        return stop.value
+
+
+def normal_lm_batch(fun, X0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None):
+    """K runs of ``normal_lm`` in lockstep.  ``fun(X (k, D)) -> (G (k, D, D), g (k, D), cost (k,))``, row by row what
+    ``normal_lm``'s ``fun`` returns -- ``Points.normal_equations_batch`` on the device.  ``X0`` (K, D): the starts; bounds,
+    tolerances and ``max_nfev`` (per start) as for ``normal_lm``.  A round: every start that has not stopped advances to its
+    next trial point, and all of them go to ``fun`` in one call, in start order; a start that has stopped drops out of the
+    later calls.  Every start does the arithmetic of ``normal_lm`` run alone on its rows.  Returns the K result dicts in start
+    order."""
+    X0 = np.asarray(X0, dtype=np.float64)
+    if X0.ndim != 2:
+        raise ValueError("X0 must have shape (K, D)")
+    runs = [_normal_lm_steps(x0, lower, upper, ftol, xtol, gtol, max_nfev) for x0 in X0]
+    results = [None] * len(runs)
+    pending = {k: next(run) for k, run in enumerate(runs)}        # the first yield needs no input and always comes
+    while pending:
+        order = sorted(pending)
+        G, g, cost = fun(np.array([pending[k] for k in order], dtype=np.float64))
+        for row, k in enumerate(order):
+            try:
+                pending[k] = runs[k].send((G[row], g[row], cost[row]))
+            except StopIteration as stop:
+                results[k] = stop.value
+                del pending[k]
+    return results
 
 
 class LsqOptimizer(BaseOptimizer):
@@ -691,34 +731,93 @@ class LsqOptimizer(BaseOptimizer):
 
         return _jac
 
+    MAX_STARTS = _lib.NORMAL_BATCH_MAX
+
+    def _start_matrix(self, starts, seed, lower, upper):
+        """the (K, D) starting points of optimize(method="normal", starts=...), clipped into the box as normal_lm clips x0;
+        ValueError for K outside 1 .. MAX_STARTS, malformed starts, or an integer K with an infinite bound.  Host arithmetic."""
+        d = len(self.target_params)
+        if isinstance(starts, (bool, np.bool_)):
+            raise ValueError("starts must be a positive integer, a list of parameter dicts or a (K, D) array")
+        if isinstance(starts, (int, np.integer)):
+            k = int(starts)
+            if not 1 <= k <= self.MAX_STARTS:
+                raise ValueError(f"starts must be 1 .. {self.MAX_STARTS}")
+            if not (np.isfinite(lower).all() and np.isfinite(upper).all()):
+                raise ValueError("starts=K draws the starts uniformly in the box: every bound must be finite")
+            X0 = np.empty((k, d), dtype=np.float64)
+            X0[0] = self.target_params_init
+            X0[1:] = np.random.default_rng(seed).uniform(lower, upper, (k - 1, d))
+        else:
+            try:
+                rows = starts if isinstance(starts, np.ndarray) else list(starts)
+                if len(rows) and all(isinstance(r, dict) for r in rows):
+                    for r in rows:
+                        missing = [t for t in self.target_params if t not in r]
+                        if missing:
+                            raise ValueError(f"a start lacks the target parameters {missing}")
+                    rows = [[r[t] for t in self.target_params] for r in rows]
+                X0 = np.array(rows, dtype=np.float64)
+            except TypeError:
+                raise ValueError("starts must be a positive integer, a list of parameter dicts or a (K, D) array") from None
+            if X0.ndim != 2 or X0.shape[1] != d or not np.isfinite(X0).all():
+                raise ValueError(f"starts must hold K rows of {d} finite target values")
+            if not 1 <= X0.shape[0] <= self.MAX_STARTS:
+                raise ValueError(f"starts must be 1 .. {self.MAX_STARTS}")
+        return np.ascontiguousarray(np.clip(X0, lower, upper))
+
     def _optimize_normal(self, bound_widths, loss, f_scale, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None, precision=None,
-                         **kwargs):
+                         starts=None, seed=None, **kwargs):
         """optimize(method="normal"); every refusal comes before the device is touched"""
         if "jac" in kwargs:
             raise ValueError("method='normal' takes no jac=: it solves on J^T J and J^T r, no Jacobian exists in it")
         if kwargs:
             raise TypeError(f"method='normal' got unexpected keyword arguments {sorted(kwargs)}")
+        if starts is None and seed is not None:
+            raise TypeError("method='normal' takes seed= with starts=K alone")
         cols = _jacobian_targets(self.target_params)
         _lib.normal_loss_check(loss, f_scale)
         bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
+        X0 = None if starts is None else self._start_matrix(starts, seed, bounds[:, 0], bounds[:, 1])
         pts = self._device_points(precision)
+        keys = ("cost", "iterations", "evaluations", "status", "grad_norm")
         try:
-            def sums(values):
-                return pts.normal_equations(self._candidate_matrix(values)[0], cols, loss, f_scale)[:3]
-
-            res = normal_lm(sums, self.target_params_init, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol,
-                            max_nfev=max_nfev)
-            # every rank has run the same iteration on the same all-reduced sums; rank 0's solution is broadcast before the
-            # final error, a collective over the shards, as for the other methods
-            best = np.ascontiguousarray(res["x"], dtype=np.float64)
             _, world = _lib.comm_info()
-            if world > 1:
-                _lib.comm_bcast(best, root=0)
-            err, _ = pts.eval_population(self._candidate_matrix(best), _lib.LOSS_MEAN_DIST, 0.0)
+            if X0 is None:
+                def sums(values):
+                    return pts.normal_equations(self._candidate_matrix(values)[0], cols, loss, f_scale)[:3]
+
+                res = normal_lm(sums, self.target_params_init, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol,
+                                max_nfev=max_nfev)
+                # every rank has run the same iteration on the same all-reduced sums; rank 0's solution is broadcast before the
+                # final error, a collective over the shards, as for the other methods
+                best = np.ascontiguousarray(res["x"], dtype=np.float64)
+                if world > 1:
+                    _lib.comm_bcast(best, root=0)
+                err, _ = pts.eval_population(self._candidate_matrix(best), _lib.LOSS_MEAN_DIST, 0.0)
+            else:
+                # rank 0's starts (its own draw when seed is None) are everybody's: the sums arrive all-reduced, so every rank
+                # then runs the same K iterations in lockstep, one alp_normal_equations_batch call per round
+                if world > 1:
+                    _lib.comm_bcast(X0, root=0)
+
+                def sums_batch(X):
+                    return pts.normal_equations_batch(self._candidate_matrix(X), cols, loss, f_scale)[:3]
+
+                runs = normal_lm_batch(sums_batch, X0, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol, max_nfev=max_nfev)
+                finals = np.ascontiguousarray([r["x"] for r in runs], dtype=np.float64)
+                if world > 1:
+                    _lib.comm_bcast(finals, root=0)
+                errs, _ = pts.eval_population(self._candidate_matrix(finals), _lib.LOSS_MEAN_DIST, 0.0, want_argmin=False)
         finally:
             pts.close()
-        self.result_ = {k: res[k] for k in ("cost", "iterations", "evaluations", "status", "grad_norm")}
-        return self._result_params(best), float(err[0])
+        if X0 is None:
+            self.result_ = {k: res[k] for k in keys}
+            return self._result_params(best), float(err[0])
+        self.start_results = [(self._result_params(x), float(e), {k: r[k] for k in keys}) for x, e, r in zip(finals, errs, runs)]
+        b = best_start([r["cost"] for r in runs])
+        self.result_ = dict(self.start_results[b][2], start=b)
+        return self.start_results[b][0], self.start_results[b][1]
 
     def optimize(self, method="trf", bound_widths=None, loss="linear", f_scale=1.0, **kwargs):
         """scipy.optimize.least_squares on the device residuals.  ``jac``: "batched" (the default for trf and dogbox: 2-point
@@ -731,9 +830,22 @@ class LsqOptimizer(BaseOptimizer):
         soft_l1, huber, cauchy); bounds as for trf (``bound_widths=None``: the default widths; a width of inf leaves a target
         unbounded); ``ftol``, ``xtol``, ``gtol`` (1e-10 each) and ``max_nfev`` with scipy's meaning; ``precision`` as for
         CMAOptimizer (None: float64 up to F64_MAX_POINTS points, float32 above).  ``jac=`` is refused (there is no Jacobian in
-        this method), and so are targets w / h.  ``self.result_``: cost, iterations, evaluations, status, grad_norm."""
+        this method), and so are targets w / h.  ``self.result_``: cost, iterations, evaluations, status, grad_norm.
+
+        ``method="normal", starts=...``: K runs of that iteration in lockstep (``normal_lm_batch``), the trial points of all
+        runs that have not stopped evaluated by ONE alp_normal_equations_batch launch per round -- at GCP size a single trial
+        point leaves the device almost empty.  ``starts`` is a list of parameter dicts (``[r[1] for r in cma.start_results]``
+        polishes the K optima ``CMAOptimizer.optimize(starts=K)`` leaves) or a (K, D) array of target values: explicit starts,
+        clipped into the box, which stays centred on ``params_init``; or an integer K: start 0 is ``params_init`` and starts
+        1 .. K-1 are drawn uniformly in the box from ``np.random.default_rng(seed)`` (every bound must be finite; ``seed=None``
+        draws fresh entropy; with a communicator rank 0's starts are broadcast).  1 <= K <= 1024; ``max_nfev`` counts per
+        start.  Returns the ``(params, error)`` of the start with the smallest final cost (``best_start``'s rule);
+        ``self.result_`` is that start's record plus ``"start"``, its index; ``self.start_results``: the
+        ``(params, error, result)`` of every start in start order.  ``starts=`` with another method is refused."""
         if method == "normal":
             return self._optimize_normal(bound_widths, loss, f_scale, **kwargs)
+        if "starts" in kwargs:
+            raise ValueError("starts= belongs to method='normal' (CMAOptimizer.optimize has its own)")
         analytic = kwargs.get("jac") == "analytic"
         cols = _jacobian_targets(self.target_params) if analytic else None
         if method == "lm" and bound_widths is not None:

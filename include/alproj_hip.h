@@ -230,6 +230,19 @@ int alp_jacobian(alp_points_t *pts, const double params[ALP_NPARAM], const int32
  * ALP_EINVAL for NULL, a bad D, a bad or repeated target, an unknown loss, f_scale <= 0 or not finite. */
 int alp_normal_equations(alp_points_t *pts, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int loss,
                          double f_scale, double *out);
+/* alp_normal_equations for B parameter vectors in one launch: what a multi-start Levenberg-Marquardt needs per round -- the
+ * sums of the residual vector of src/alproj/optimize.py:215-237 at the trial points of B independent solves of :442-539 (K
+ * starts polished side by side, as the K candidate optima of the multi-start form of the CMA-ES loop of :359-439 leave them).
+ * params: B x ALP_NPARAM row-major, 1 <= B <= 1024; targets, loss and f_scale are shared by the rows.  out: B rows of
+ * D (D + 1) / 2 + D + 2 doubles, row b in alp_normal_equations' layout for params row b (the point count is repeated in every
+ * row).  One workgroup per (stripe of points, pose) pair; a pose's stripes are added in stripe order, no atomics: a row does
+ * not depend on the other rows of the call, and the same call gives the same bits.  Where the set is one stripe either way
+ * (up to 256 points) a row has the bits of the single call; above, the stripes are cut differently and the two agree to the
+ * reassociation of the sums.  With a communicator: one all-reduce of B (D (D + 1) / 2 + D + 2) doubles.  n = 0 gives B rows
+ * of zeros.  Errors as for alp_normal_equations (same codes; ALP_ESTATE without observed uv), and ALP_EINVAL for B < 1 or
+ * B > 1024. */
+int alp_normal_equations_batch(alp_points_t *pts, const double *params, int64_t B, const int32_t *target_idx, int D, int loss,
+                               double f_scale, double *out);
 
 /* Population-wide reprojection error: replaces the inner loop of CMAOptimizer.optimize,
  * src/alproj/optimize.py:420-423, i.e. P calls of _proj_error (:347-356) = project +
