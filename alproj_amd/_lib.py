@@ -226,6 +226,14 @@ _SIGNATURES = {
     "alp_cma_wait": [_c_void_p],
     "alp_cma_tell_host": [_c_void_p, _c_dp, _c_dp, ctypes.POINTER(ctypes.c_int32)],
     "alp_cma_fetch_last": [_c_void_p, _c_dp, _c_dp, _c_dp],
+    "alp_lm_create": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_dp, _c_dp, _c_dp, _c_int, _c_int, _c_double, _c_double,
+                      _c_double, _c_double, _c_i64, ctypes.POINTER(_c_void_p)],
+    "alp_lm_destroy": [_c_void_p],
+    "alp_lm_run": [_c_void_p, _c_i64],
+    "alp_lm_wait": [_c_void_p, ctypes.POINTER(_c_i64)],
+    "alp_lm_get": [_c_void_p, _c_dp, _c_dp, _c_dp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_int32), _c_dp,
+                   _c_dp, _c_dp],
+    "alp_lm_step_host": [_c_void_p, _c_dp],
     "alp_cma_create_starts": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_dp,
                               _c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_c_void_p)],
     "alp_cma_set_state_at": [_c_void_p, _c_int, _c_dp, _c_double, _c_dp, _c_dp, _c_dp, _c_i64],
@@ -1095,6 +1103,84 @@ class CmaDevice:
         X, cand, losses = np.empty((R, self.D)), np.empty((R, NPARAM)), np.empty(R)
         check(self._lib.alp_cma_fetch_last(self._h, as_dp(X), as_dp(cand), as_dp(losses)))
         return X, cand, losses
+
+
+LM_RUNNING = -2                 # alp_lm_get: the status of a start that has not stopped
+
+
+class LmDevice:
+    """The device loop of the least-squares iteration (RAII wrapper of alp_lm_t): K bounded Levenberg-Marquardt runs of
+    ``optimize.normal_lm`` with their state on the device; ``run(R)`` enqueues R rounds (evaluation of the running starts'
+    trial points, step, selection) without the host in between, ``wait()`` synchronises and returns how many starts still run.
+    ``points``: the Points (with observed uv) the sums are formed on; ``template``: the 25-vector of params_init; ``targets``:
+    ABI indices of the targets (normal_targets_check's rule); ``lower`` / ``upper``: the box; ``X0`` (K, D): the starts;
+    ``loss`` / ``f_scale`` as for ``Points.normal_equations``; tolerances and ``max_nfev`` (None: 100 D) as for normal_lm."""
+
+    def __init__(self, points, template, targets, lower, upper, X0, loss="linear", f_scale=1.0, ftol=1e-10, xtol=1e-10, gtol=1e-10,
+                 max_nfev=None):
+        l = lib()
+        idx = normal_targets_check(targets)
+        kind, fs = normal_loss_check(loss, f_scale)
+        tmpl = np.ascontiguousarray(template, dtype=np.float64)
+        self.D = int(len(idx))
+        lo = np.ascontiguousarray(lower, dtype=np.float64)
+        hi = np.ascontiguousarray(upper, dtype=np.float64)
+        X0 = np.ascontiguousarray(X0, dtype=np.float64)
+        if tmpl.shape != (NPARAM,) or lo.shape != (self.D,) or hi.shape != (self.D,) or X0.ndim != 2 or X0.shape[1] != self.D:
+            raise ValueError("template must have 25 entries, lower / upper D and X0 the shape (K, D)")
+        self.K = int(X0.shape[0])
+        h = _c_void_p()
+        check(l.alp_lm_create(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo), as_dp(hi),
+                              as_dp(X0), self.K, kind, fs, float(ftol), float(xtol), float(gtol),
+                              100 * self.D if max_nfev is None else max(1, int(max_nfev)), ctypes.byref(h)))
+        self._h = h
+        self._lib = l
+        self.points = points
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.alp_lm_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def run(self, rounds):
+        """enqueue ``rounds`` rounds (returns at once; ``wait`` synchronises)"""
+        check(self._lib.alp_lm_run(self._h, int(rounds)))
+
+    def wait(self):
+        """synchronise -> the number of starts that have not stopped"""
+        pending = _c_i64()
+        check(self._lib.alp_lm_wait(self._h, ctypes.byref(pending)))
+        return int(pending.value)
+
+    def get(self):
+        """dict of arrays over the K starts: x (K, D), cost, grad_norm, iterations, evaluations, status (LM_RUNNING for a start
+        that has not stopped), trial (K, D): the pending trial point, mu, nu"""
+        K, D = self.K, self.D
+        x, trial = np.empty((K, D)), np.empty((K, D))
+        cost, gn, mu, nu = (np.empty(K) for _ in range(4))
+        it, ev = np.empty(K, dtype=np.int64), np.empty(K, dtype=np.int64)
+        status = np.empty(K, dtype=np.int32)
+        check(self._lib.alp_lm_get(self._h, as_dp(x), as_dp(cost), as_dp(gn), it.ctypes.data_as(ctypes.POINTER(_c_i64)),
+                                   ev.ctypes.data_as(ctypes.POINTER(_c_i64)), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                   as_dp(trial), as_dp(mu), as_dp(nu)))
+        return dict(x=x, cost=cost, grad_norm=gn, iterations=it, evaluations=ev, status=status, trial=trial, mu=mu, nu=nu)
+
+    def step_host(self, sums):
+        """one round on the given sums instead of an evaluation: (K, D (D + 1) / 2 + D + 2) rows in alp_normal_equations_batch's
+        layout (upper triangle of G, g, sum of rho, point count); the rows of stopped starts are ignored.  For tests."""
+        d = self.D
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        if sums.shape != (self.K, d * (d + 1) // 2 + d + 2):
+            raise ValueError("sums must have shape (K, D (D + 1) / 2 + D + 2)")
+        check(self._lib.alp_lm_step_host(self._h, as_dp(sums)))
 
 
 def distort_map(h, w, coeffs):

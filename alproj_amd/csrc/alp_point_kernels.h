@@ -888,6 +888,48 @@ __global__ __launch_bounds__(256) void reduce_normal_batch_kernel(const double *
     if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = n_local;
 }
 
+// K3n for the starts a device loop still runs (alp_lm.hip): the grid is normal_batch_kernel's for ALL K starts, pose index
+// fastest, and workgroup (b, stripe) takes start list[b] under plans[list[b]] -- `list` holds the *count running starts in
+// ascending order; a workgroup with b >= *count returns at once.  The partial row is the one normal_batch_kernel would write for
+// pose list[b] of K, so a start's stripes and the order of its additions do not depend on which other starts still run.
+// list[b] is the same in every lane: the plan still comes in by scalar loads.
+template <typename TS, int LOSS>
+__global__ __launch_bounds__(256) void normal_batch_listed_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+                                                                  const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
+                                                                  int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
+                                                                  const int *__restrict__ list, const long long *__restrict__ count,
+                                                                  double *__restrict__ partials) {
+    if ((long long)blockIdx.x >= *count) return;
+    const int pose = list[blockIdx.x], stripe = blockIdx.y, stripes = gridDim.y;
+    normal_body<TS, LOSS>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
+                          (int64_t)pose * stripes + stripe);
+}
+
+// reduce_normal_batch_kernel for those starts: row q of `sums` for a running start (running[q] != 0) in the same order of
+// additions, zeros for a stopped one (its partial rows are stale); sums[q * (T + 1) + T] = the local point count in every row.
+__global__ __launch_bounds__(256) void reduce_normal_listed_kernel(const double *__restrict__ partials, int stripes, int T, double n_local,
+                                                                   const int *__restrict__ running, double *__restrict__ sums) {
+    __shared__ double s[8][32];
+    const int cl = threadIdx.x & 31;
+    const int g = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cl;
+    const double *rows = partials + (int64_t)blockIdx.y * stripes * T;
+    double *out = sums + (int64_t)blockIdx.y * (T + 1);
+    const bool live = running[blockIdx.y] != 0;        // the same in every lane
+    double acc = 0.0;
+    if (c < T && live)
+        for (int b = g; b < stripes; b += 8) acc += rows[(int64_t)b * T + c];
+    s[g][cl] = acc;
+    __syncthreads();
+    if (g == 0 && c < T) {
+        double t = s[0][cl];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) t += s[k][cl];
+        out[c] = t;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = n_local;
+}
+
 // TS = element type of the planes in HBM, T = arithmetic type (TS = float with T = double is the
 // float64 re-evaluation of a float32 point set: alp_eval_population's argmin confirmation)
 template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, typename TS = T, bool EXACT_POLES = false, bool LENS_FREE = false>

@@ -577,9 +577,37 @@ int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss
     return ALP_OK;
 }
 
+// The evaluation of a round of the least-squares device loop (alp_lm.hip): normal_batch_listed_kernel over the grid of all K
+// starts, reduce_normal_listed_kernel, one all-reduce of K (T + 1) doubles.  Enqueue only; the buffers are the loop's own.
+template <typename TS>
+int normal_listed_impl(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
+                       const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums) {
+    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, const int *,
+                            const long long *, double *);
+    static const Kernel kernels[4] = {normal_batch_listed_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_listed_kernel<TS, ALP_NORMAL_SOFT_L1>,
+                                      normal_batch_listed_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_listed_kernel<TS, ALP_NORMAL_CAUCHY>};
+    const int T = D * (D + 1) / 2 + D + 1;
+    hipStream_t st = ctx().stream;
+    if (g.blocks > 0) {
+        hipLaunchKernelGGL(kernels[loss], dim3((unsigned)K, (unsigned)g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
+                           (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, list, count, partials);
+        hipLaunchKernelGGL(reduce_normal_listed_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)K), dim3(256), 0, st, (const double *)partials,
+                           g.blocks, T, (double)p->n, running, sums);
+        ALP_HIP(hipGetLastError());
+    } else {
+        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)K * (T + 1) * sizeof(double), st));       // an empty shard still joins the all-reduce
+    }
+    return comm_allreduce_sum_f64(sums, (int64_t)K * (T + 1));
+}
+
 }  // namespace
 
 namespace alp {
+int normal_listed_launch(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
+                         const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums) {
+    return p->precision == ALP_F64 ? normal_listed_impl<double>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums)
+                                   : normal_listed_impl<float>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums);
+}
 int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched,
                    const double *params_dev) {
     return p->precision == ALP_F64 ? popeval_launch_t<double>(p, P, loss_kind, f_scale, lens_free, shared_pose, batched, params_dev)
@@ -725,6 +753,7 @@ int alp_points_create_columns(const void *x, const void *y, const void *z, int i
 int alp_points_destroy(alp_points_t *p) {
     if (!p) return ALP_OK;
     for (alp_cma_t *h : p->loops) cma_points_gone(h);
+    for (alp_lm_t *h : p->lm_loops) lm_points_gone(h);
     if (ctx().ready) hipStreamSynchronize(ctx().stream);
     for (void *q : {p->slab_xyz, p->slab_obs, p->slab_uv, p->cand_dev, (void *)p->partials, (void *)p->sums_dev})
         if (q) hipFree(q);

@@ -56,6 +56,8 @@ struct alp_points {
     // generations enqueued (loop_pending) they use the population scratch above, and an alp_eval_population_enqueue is refused
     std::vector<alp_cma_t *> loops;
     bool loop_pending = false;
+    // device loops of the least-squares iteration (alp_lm.hip) built on this set: told when it is destroyed (they own their scratch)
+    std::vector<alp_lm_t *> lm_loops;
     size_t esize() const { return precision == ALP_F64 ? 8 : 4; }
 };
 
@@ -76,5 +78,13 @@ int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool
 int points_pop_reserve(alp_points *p, int64_t P);
 // alp_points_destroy: a device loop built on the set loses it (its later calls return ALP_ESTATE)
 void cma_points_gone(alp_cma_t *h);
+void lm_points_gone(alp_lm_t *h);
+
+// One evaluation of the least-squares device loop (alp_lm.hip): the normal equations of the starts in `list` (*count of them, in
+// ascending order; running[k] != 0 for exactly those) under plans[k], over the fixed grid `g` = host::normal_batch_grid(n, K, cus):
+// sums = K rows of T + 1 doubles in alp_normal_equations_batch's layout, zeros (and the point count) for a start that is not
+// listed; all-reduced when a communicator exists.  partials: K * g.blocks * T doubles.  Enqueue only.
+int normal_listed_launch(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
+                         const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums);
 
 }  // namespace alp

@@ -44,35 +44,7 @@ void fold_pose_lens_free(const double p[ALP_NPARAM], const double origin[3], dou
 }
 
 // ------------------------------------------------------------------ derivative of the fold
-// A forward-mode dual number: v + d eps with eps^2 = 0.  fold_pose_any<Dual> carries d rec / d theta_j next to rec when
-// theta_j is seeded with d = 1.
-namespace {
-struct Dual {
-    double v, d;
-    Dual(double v_ = 0, double d_ = 0) : v(v_), d(d_) {}
-    Dual &operator+=(const Dual &b) { v += b.v; d += b.d; return *this; }
-};
-inline Dual operator-(const Dual &a) { return Dual(-a.v, -a.d); }
-inline Dual operator+(const Dual &a, const Dual &b) { return Dual(a.v + b.v, a.d + b.d); }
-inline Dual operator+(const Dual &a, double b) { return Dual(a.v + b, a.d); }
-inline Dual operator+(double a, const Dual &b) { return Dual(a + b.v, b.d); }
-inline Dual operator-(const Dual &a, const Dual &b) { return Dual(a.v - b.v, a.d - b.d); }
-inline Dual operator-(const Dual &a, double b) { return Dual(a.v - b, a.d); }
-inline Dual operator-(double a, const Dual &b) { return Dual(a - b.v, -b.d); }
-inline Dual operator*(const Dual &a, const Dual &b) { return Dual(a.v * b.v, a.d * b.v + a.v * b.d); }
-inline Dual operator*(const Dual &a, double b) { return Dual(a.v * b, a.d * b); }
-inline Dual operator*(double a, const Dual &b) { return Dual(a * b.v, a * b.d); }
-inline Dual operator/(const Dual &a, const Dual &b) { return Dual(a.v / b.v, (a.d * b.v - a.v * b.d) / (b.v * b.v)); }
-inline Dual operator/(const Dual &a, double b) { return Dual(a.v / b, a.d / b); }
-inline Dual operator/(double a, const Dual &b) { return Dual(a / b.v, -a * b.d / (b.v * b.v)); }
-inline Dual fold_sin(const Dual &a) { return Dual(std::sin(a.v), std::cos(a.v) * a.d); }
-inline Dual fold_cos(const Dual &a) { return Dual(std::cos(a.v), -std::sin(a.v) * a.d); }
-inline Dual fold_tan(const Dual &a) {
-    const double t = std::tan(a.v);
-    return Dual(t, (1 + t * t) * a.d);
-}
-}  // namespace
-
+// (the dual number and the arithmetic are host/alp_jacplan.h, shared with the device loop of alp_lm.hip)
 int jacobian_targets_check(const int32_t *target, int D) {
     if (!target) return fail(ALP_EINVAL, "jacobian: target list is NULL");
     if (D < 1 || D > JAC_MAX) return fail(ALP_EINVAL, "jacobian: D = %d, must be 1..%d", D, JAC_MAX);
@@ -90,36 +62,17 @@ int jacobian_targets_check(const int32_t *target, int D) {
 int fold_pose_jacobian(const double params[ALP_NPARAM], const double origin[3], const int32_t *target, int D, double *jac) {
     if (int rc = jacobian_targets_check(target, D)) return rc;
     if (!params || !origin || !jac) return fail(ALP_EINVAL, "fold_pose_jacobian: NULL argument");
-    Dual p[ALP_NPARAM], rec[POSE_WORDS];
-    for (int j = 0; j < D; ++j) {
-        for (int i = 0; i < ALP_NPARAM; ++i) p[i] = Dual(params[i], i == target[j] ? 1.0 : 0.0);
-        fold_pose_any<Dual>(p, params[21], params[22], origin, rec);
-        for (int m = 0; m < JAC_WORDS; ++m) jac[m * D + j] = rec[m].d;
-    }
+    fold_pose_jacobian_hd(params, origin, target, D, jac);
     return ALP_OK;
 }
 
 int jacobian_plan(const double params[ALP_NPARAM], const double origin[3], const int32_t *target, int D, int of_residuals,
                   JacPlan *plan) {
-    double jac[JAC_WORDS * JAC_MAX];
-    if (int rc = fold_pose_jacobian(params, origin, target, D, jac)) return rc;
+    if (int rc = jacobian_targets_check(target, D)) return rc;
+    if (!params || !origin) return fail(ALP_EINVAL, "fold_pose_jacobian: NULL argument");
     if (!plan) return fail(ALP_EINVAL, "jacobian_plan: NULL argument");
     *plan = JacPlan{};
-    fold_pose(params, origin, plan->rec);
-    plan->D = D;
-    plan->su = of_residuals ? -plan->rec[26] : plan->rec[26];
-    plan->sv = of_residuals ? -plan->rec[27] : plan->rec[27];
-    // the lens word of each lens parameter (a1 .. s4 = indices 7 .. 20), as fold_pose_any writes them
-    static const int lens_word[ALP_NPARAM] = {-1, -1, -1, -1, -1, -1, -1, 18, 19, 12, 13, 14, 15, 16, 17, 20, 21, 22, 23, 24, 25,
-                                              -1, -1, -1, -1};
-    for (int j = 0; j < D; ++j) {
-        const int m = lens_word[target[j]];
-        plan->lens_w[j] = m < 0 ? -1 : m - 12;
-        if (m < 0)
-            for (int k = 0; k < 12; ++k) plan->drow[j][k] = jac[k * D + j];
-        else
-            plan->lens_f[j] = jac[m * D + j];
-    }
+    jacobian_plan_hd(params, origin, target, D, of_residuals, plan);
     return ALP_OK;
 }
 

@@ -116,6 +116,11 @@ struct alignas(16) JacPlan {
 int jacobian_plan(const double params[ALP_NPARAM], const double origin[3], const int32_t *target, int D, int of_residuals,
                   JacPlan *plan);
 
+}  // namespace alp
+#include "host/alp_jacplan.h"   // Dual, fold_pose_jacobian_hd, jacobian_plan_hd: the arithmetic of the two functions above, host and device
+#include "host/alp_lm.h"        // LmState, lm_start / lm_consume / lm_produce: the bounded Levenberg-Marquardt of method="normal" as a state machine
+namespace alp {
+
 namespace host {
 
 // ------------------------------------------------------------------ threaded array helpers (alp_host_* entry points)

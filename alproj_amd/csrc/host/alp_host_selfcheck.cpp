@@ -6,7 +6,8 @@
 // include/alproj_hip.h), and compared with a serial restatement written here.  Exit code 0 and "host selfcheck ok" =
 // every comparison held; the sanitizers add their own verdict on stderr.  --plan prints what host/alp_plan.h plans for the
 // queries it is given (tests/test_launch_plan.py holds the Python restatements of the launch rules to it, and reads the render
-// frame's plans and overflow verdicts off it).
+// frame's plans and overflow verdicts off it); --lm runs the Levenberg-Marquardt state machine of host/alp_lm.h on sums read from
+// stdin (tests/test_lm_device_host.py holds it to alproj_amd/optimize.py: _normal_lm_steps).
 #include <cinttypes>
 #include <mutex>
 #include <random>
@@ -681,13 +682,141 @@ int plan(int argc, char **argv) {
     return 0;
 }
 
+// ------------------------------------------------------------------ the Levenberg-Marquardt state machine (host/alp_lm.h)
+// cost = 0.5 |A x - b|^2 of a small built-in problem: G = A^T A and g = A^T (A x - b) are exact, so the machine must reach the
+// least-squares solution (unbounded) or the box-constrained one (a bound active), and every stop must be one of its own.
+struct LmQuadratic {
+    static constexpr int M = 6, D = 3;
+    double A[M][D], b[M];
+    LmQuadratic() {
+        const double a[M][D] = {{4, 1, 0}, {1, 3, 1}, {0, 1, 50}, {2, 0, 1}, {1, 1, 1}, {0, 2, 3}};
+        const double want[D] = {0.5, -0.25, 0.75};
+        for (int i = 0; i < M; ++i) {
+            b[i] = 0;
+            for (int j = 0; j < D; ++j) { A[i][j] = a[i][j]; b[i] += a[i][j] * want[j]; }
+        }
+    }
+    double sums(const double *x, double *G, double *g) const {
+        double r[M], cost = 0;
+        for (int i = 0; i < M; ++i) {
+            r[i] = -b[i];
+            for (int j = 0; j < D; ++j) r[i] += A[i][j] * x[j];
+            cost += 0.5 * r[i] * r[i];
+        }
+        int t = 0;
+        for (int i = 0; i < D; ++i)
+            for (int j = i; j < D; ++j, ++t) {
+                G[t] = 0;
+                for (int k = 0; k < M; ++k) G[t] += A[k][i] * A[k][j];
+            }
+        for (int j = 0; j < D; ++j) {
+            g[j] = 0;
+            for (int k = 0; k < M; ++k) g[j] += A[k][j] * r[k];
+        }
+        return cost;
+    }
+};
+
+void lm_run(const LmConfig &cfg, const LmQuadratic &q, const double *x0, LmState *s, const double *first_cost = nullptr) {
+    double work[LM_WORK], G[LM_TRI], g[LM_MAX_D];
+    lm_start(cfg, x0, s);
+    for (int round = 0; s->phase != LM_STOPPED && round < 10000; ++round) {
+        double cost = q.sums(s->trial, G, g);
+        if (round == 0 && first_cost) cost = *first_cost;
+        lm_advance(cfg, s, G, g, cost, work);
+    }
+}
+
+void check_lm() {
+    const LmQuadratic q;
+    LmConfig cfg{};
+    cfg.D = 3;
+    cfg.ftol = cfg.xtol = cfg.gtol = 1e-10;
+    cfg.max_nfev = 300;
+    const double x0[3] = {-0.9, 0.9, -0.9}, want[3] = {0.5, -0.25, 0.75};
+    LmState s;
+    for (int i = 0; i < 3; ++i) { cfg.lower[i] = -INFINITY; cfg.upper[i] = INFINITY; }
+    lm_run(cfg, q, x0, &s);
+    CHECK(s.status >= 1 && s.status <= 4 && s.phase == LM_STOPPED, "unbounded: status %d", s.status);
+    for (int i = 0; i < 3; ++i) CHECK(std::fabs(s.x[i] - want[i]) < 1e-7, "unbounded: x[%d] = %.17g", i, s.x[i]);
+    CHECK(s.nfev >= 2 && s.nfev <= 300 && s.iterations >= 1 && s.iterations < s.nfev, "unbounded: %d evaluations, %d iterations", s.nfev, s.iterations);
+    // a box whose upper bound cuts x[2] off: the optimum lies on it, and the gradient there pushes outward
+    for (int i = 0; i < 3; ++i) { cfg.lower[i] = -1; cfg.upper[i] = 1; }
+    cfg.upper[2] = 0.5;
+    lm_run(cfg, q, x0, &s);
+    CHECK(s.status >= 1 && s.status <= 4, "bounded: status %d", s.status);
+    CHECK(s.x[2] == 0.5 && s.g[2] < 0 && lm_grad_norm(cfg, &s) < 1e-4, "bounded: x[2] = %.17g, g[2] = %g, |g| free = %g", s.x[2], s.g[2],
+          lm_grad_norm(cfg, &s));
+    for (int i = 0; i < 3; ++i) CHECK(s.x[i] >= cfg.lower[i] && s.x[i] <= cfg.upper[i], "bounded: x[%d] outside the box", i);
+    // the stops that need no solve: a cost that is not finite at x0, max_nfev = 1, every variable on a bound it is pushed against
+    const double nan = NAN;
+    lm_run(cfg, q, x0, &s, &nan);
+    CHECK(s.status == -1 && s.nfev == 1 && s.iterations == 0 && lm_grad_norm(cfg, &s) != lm_grad_norm(cfg, &s), "NaN at x0: status %d", s.status);
+    cfg.max_nfev = 1;
+    lm_run(cfg, q, x0, &s);
+    CHECK(s.status == 0 && s.nfev == 1, "max_nfev = 1: status %d after %d", s.status, s.nfev);
+    cfg.max_nfev = 300;
+    for (int i = 0; i < 3; ++i) { cfg.lower[i] = 2; cfg.upper[i] = 3; }
+    lm_run(cfg, q, x0, &s);
+    CHECK(s.status == 1 && s.nfev == 1 && s.x[0] == 2 && s.x[1] == 2 && s.x[2] == 2, "all on bounds: status %d after %d", s.status, s.nfev);
+}
+
+// --lm: the machine on sums read from stdin.  "D max_nfev ftol xtol gtol", then x0, lower and upper (D numbers each; inf and
+// hexadecimal floats are read), then rows of D (D + 1) / 2 + D + 1 numbers: G (row-major upper triangle), g and the cost at the
+// pending trial point.  Prints "trial <D numbers>" for every trial point (the first one before any row is read) and, when the
+// machine stops or the rows run out, "final status evaluations iterations cost grad_norm mu nu <x>" ("starved" instead of
+// "final" when it had not stopped).  Numbers are printed as %a.
+int lm_mode() {
+    LmConfig cfg{};
+    int D = 0, max_nfev = 0;
+    if (scanf("%d %d %lf %lf %lf", &D, &max_nfev, &cfg.ftol, &cfg.xtol, &cfg.gtol) != 5 || D < 1 || D > LM_MAX_D || max_nfev < 1) {
+        fprintf(stderr, "bad --lm header\n");
+        return 2;
+    }
+    cfg.D = D;
+    cfg.max_nfev = max_nfev;
+    double x0[LM_MAX_D], row[LM_TRI + LM_MAX_D + 1], work[LM_WORK];
+    for (double *dst : {x0, cfg.lower, cfg.upper})
+        for (int i = 0; i < D; ++i)
+            if (scanf("%lf", dst + i) != 1) {
+                fprintf(stderr, "bad --lm start or bounds\n");
+                return 2;
+            }
+    const int tri = D * (D + 1) / 2, T = tri + D + 1;
+    LmState s;
+    lm_start(cfg, x0, &s);
+    auto trial = [&] {
+        printf("trial");
+        for (int i = 0; i < D; ++i) printf(" %a", s.trial[i]);
+        printf("\n");
+    };
+    trial();
+    while (s.phase != LM_STOPPED) {
+        int got = 0;
+        while (got < T && scanf("%lf", row + got) == 1) ++got;
+        if (got == 0) break;
+        if (got != T) {
+            fprintf(stderr, "bad --lm row: %d of %d numbers\n", got, T);
+            return 2;
+        }
+        lm_advance(cfg, &s, row, row + tri, row[T - 1], work);
+        if (s.phase != LM_STOPPED) trial();
+    }
+    printf("%s %d %d %d %a %a %a %a", s.phase == LM_STOPPED ? "final" : "starved", s.status, s.nfev, s.iterations, s.cost, lm_grad_norm(cfg, &s),
+           s.mu, s.nu);
+    for (int i = 0; i < D; ++i) printf(" %a", s.x[i]);
+    printf("\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc > 2 && !strcmp(argv[1], "--canary")) return canary(argv[2]);
     if (argc > 1 && !strcmp(argv[1], "--plan")) return plan(argc - 2, argv + 2);
+    if (argc > 1 && !strcmp(argv[1], "--lm")) return lm_mode();
     struct Group { const char *name; void (*fn)(); };
     const Group groups[] = {{"hash", check_hash},     {"minmax", check_minmax},   {"prefault", check_prefault}, {"fold_pose", check_fold_pose},
                             {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors},
-                            {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}};
+                            {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}, {"lm", check_lm}};
     const bool concurrent = !(argc > 1 && !strcmp(argv[1], "--serial"));
     // every group on its own caller thread at once: the library promises that independent calls may overlap
     std::vector<std::thread> th;

@@ -767,8 +767,10 @@ class LsqOptimizer(BaseOptimizer):
         return np.ascontiguousarray(np.clip(X0, lower, upper))
 
     def _optimize_normal(self, bound_widths, loss, f_scale, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None, precision=None,
-                         starts=None, seed=None, **kwargs):
+                         starts=None, seed=None, device_loop=False, check_every=8, **kwargs):
         """optimize(method="normal"); every refusal comes before the device is touched"""
+        if device_loop and (isinstance(check_every, (bool, np.bool_)) or not isinstance(check_every, (int, np.integer)) or check_every < 1):
+            raise ValueError("check_every must be a positive integer")
         if "jac" in kwargs:
             raise ValueError("method='normal' takes no jac=: it solves on J^T J and J^T r, no Jacobian exists in it")
         if kwargs:
@@ -779,11 +781,36 @@ class LsqOptimizer(BaseOptimizer):
         _lib.normal_loss_check(loss, f_scale)
         bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
         X0 = None if starts is None else self._start_matrix(starts, seed, bounds[:, 0], bounds[:, 1])
+        single = X0 is None
+        if device_loop and single:           # the K = 1 case, from params_init (clipped on the device, as normal_lm clips x0)
+            X0 = np.ascontiguousarray(np.asarray(self.target_params_init, dtype=np.float64)[None, :])
         pts = self._device_points(precision)
         keys = ("cost", "iterations", "evaluations", "status", "grad_norm")
         try:
             _, world = _lib.comm_info()
-            if X0 is None:
+            if device_loop:
+                # the K runs on the device (alp_lm_*): rank 0's starts are everybody's, every rank enqueues the same rounds on the
+                # same all-reduced sums and computes the same states; max_nfev stops every start, so the loop ends
+                if world > 1:
+                    _lib.comm_bcast(X0, root=0)
+                with _lib.LmDevice(pts, _lib.params_vector(self.params_init), cols, bounds[:, 0], bounds[:, 1], X0, loss, f_scale, ftol,
+                                   xtol, gtol, max_nfev) as loop:
+                    pending = len(X0)
+                    while pending:
+                        loop.run(int(check_every))
+                        pending = loop.wait()
+                    rec = loop.get()
+                runs = [dict(x=rec["x"][k], cost=float(rec["cost"][k]), grad_norm=float(rec["grad_norm"][k]),
+                             iterations=int(rec["iterations"][k]), evaluations=int(rec["evaluations"][k]), status=int(rec["status"][k]))
+                        for k in range(len(X0))]
+                finals = np.ascontiguousarray(rec["x"], dtype=np.float64)
+                if world > 1:
+                    _lib.comm_bcast(finals, root=0)
+                errs, _ = pts.eval_population(self._candidate_matrix(finals), _lib.LOSS_MEAN_DIST, 0.0, want_argmin=False)
+                if single:
+                    res, best, err = runs[0], finals[0], errs[:1]
+                    X0 = None
+            elif X0 is None:
                 def sums(values):
                     return pts.normal_equations(self._candidate_matrix(values)[0], cols, loss, f_scale)[:3]
 
@@ -841,9 +868,26 @@ class LsqOptimizer(BaseOptimizer):
         draws fresh entropy; with a communicator rank 0's starts are broadcast).  1 <= K <= 1024; ``max_nfev`` counts per
         start.  Returns the ``(params, error)`` of the start with the smallest final cost (``best_start``'s rule);
         ``self.result_`` is that start's record plus ``"start"``, its index; ``self.start_results``: the
-        ``(params, error, result)`` of every start in start order.  ``starts=`` with another method is refused."""
+        ``(params, error, result)`` of every start in start order.  ``starts=`` with another method is refused.
+
+        ``method="normal", device_loop=True`` (opt-in; ``check_every=8``): the K runs keep their state on the device
+        (alp_lm_*): a round -- the evaluation of the running starts' trial points, the state-machine step of every start with
+        its Cholesky solve, the plan of the next trial point, the list of the starts that still run -- is four launches
+        enqueued with no copy and no synchronisation; the host looks every ``check_every`` rounds (8 bytes come back) until
+        no start runs, then fetches the K records once.  Without ``starts=`` it is the K = 1 case from ``params_init`` and
+        ``result_`` has no ``"start"``.  Results and attributes as above.  A device run's trajectory is NOT the host run's: the
+        device's sines and cosines in the plan and its Cholesky round differently from libm and LAPACK; near convergence
+        ``cost_new < cost`` is decided at rounding level, so evaluation counts and the status among 2 / 3 / 4 may differ; and
+        the host lockstep shrinks its batch as starts stop, which changes the stripes of the sums above 256 points, while
+        the device loop keeps K's.  What is held instead: the state machine to ``_normal_lm_steps`` on shared sums, the sums
+        to ``alp_normal_equations_batch``, the end result to the cost and the optimum.  At most 23 targets, not w / h;
+        ``device_loop`` with another method and a ``check_every`` that is no positive integer are refused."""
         if method == "normal":
             return self._optimize_normal(bound_widths, loss, f_scale, **kwargs)
+        if kwargs.get("device_loop"):
+            raise ValueError("device_loop=True belongs to method='normal' (CMAOptimizer.optimize has its own)")
+        if "device_loop" in kwargs:          # device_loop=False: the default, said aloud
+            kwargs = {k: v for k, v in kwargs.items() if k not in ("device_loop", "check_every")}
         if "starts" in kwargs:
             raise ValueError("starts= belongs to method='normal' (CMAOptimizer.optimize has its own)")
         analytic = kwargs.get("jac") == "analytic"

@@ -394,6 +394,49 @@ int alp_cma_set_state_at(alp_cma_t *h, int k, const double *mean, double sigma, 
 int alp_cma_get_state_at(alp_cma_t *h, int k, double *mean, double *sigma, double *C, double *p_sigma, double *pc, int64_t *generation,
                          double *B, double *Dvec);
 
+/* ---------------------------------------------------------------- device loop of the least-squares iteration --- */
+/* K bounded Levenberg-Marquardt runs on the normal equations (LsqOptimizer.optimize(method="normal", starts=K,
+ * device_loop=True): the solve of src/alproj/optimize.py:442-539 on the sums of the residual vector of :215-237) with their
+ * state on the device: rounds are enqueued on the library stream with no copy to the host and no synchronisation between them.
+ * The iteration is alproj_amd/optimize.py: _normal_lm_steps, statement by statement (csrc/host/alp_lm.h).  One round:
+ *   the evaluation   alp_normal_equations_batch's kernel over the starts that still run, on the grid of all K starts (a start's
+ *                    stripes, and so the order of its additions, do not depend on which other starts have stopped), its
+ *                    reduction, and -- with a communicator -- one all-reduce of K (D (D + 1) / 2 + D + 2) doubles
+ *   the step         one workgroup per start: consume the sums at the trial point (accept / reject, gain ratio, damping
+ *                    update, ftol / xtol), then produce the next trial point (gtol / max_nfev, free set, damped Cholesky solve,
+ *                    clip, predicted reduction) or stop; for a start that goes on, the 25-parameter row and its plan
+ *                    (the fold of the pose and its derivative for every target, csrc/host/alp_jacplan.h) are built there too
+ *   the selection    the list of the starts that still run, ascending
+ * No atomics anywhere: the same handle history gives the same bits.  A device run's trajectory is NOT the host run's: the
+ * plan's sines and cosines and the solve round differently from libm and LAPACK, and near convergence `cost_new < cost` is
+ * decided at rounding level, so evaluation counts and the status among 2 / 3 / 4 may differ. */
+typedef struct alp_lm alp_lm_t;
+/* The status alp_lm_get reports for a start that has not stopped (no stop uses it; the stops are normal_lm's: -1, 0 .. 4). */
+#define ALP_LM_RUNNING (-2)
+/* tmpl: the 25 ABI parameters of params_init; target_idx[D]: the targets, by alp_jacobian's rule (1 <= D <= 23, distinct, not w
+ * or h); lower / upper[D]: the box (either may be infinite); X0[K x D]: the starts (clipped into the box), 1 <= K <= 1024;
+ * loss / f_scale as for alp_normal_equations; ftol, xtol, gtol and max_nfev (>= 1, per start) with scipy's meaning.  Prepares the
+ * first trial points (X0 clipped), their plans and the list.  Needs observed uv (ALP_ESTATE).  The handle keeps `pts`; destroy it
+ * before the point set (a handle whose point set is gone returns ALP_ESTATE from alp_lm_run). */
+int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                  const double *upper, const double *X0, int K, int loss, double f_scale, double ftol, double xtol, double gtol,
+                  int64_t max_nfev, alp_lm_t **out);
+int alp_lm_destroy(alp_lm_t *h);
+/* Enqueue `rounds` rounds (enqueue only; alp_lm_wait synchronises).  A second run before the wait: ALP_ESTATE.  Rounds after
+ * the last start has stopped do nothing. */
+int alp_lm_run(alp_lm_t *h, int64_t rounds);
+/* Synchronise; *pending = the number of starts that have not stopped (8 bytes cross PCIe). */
+int alp_lm_wait(alp_lm_t *h, int64_t *pending);
+/* The K records; any output may be NULL.  x[K x D]: the current point (the result once stopped), cost, grad_norm (the infinity
+ * norm of g over the free variables; NaN with status -1), iterations (accepted steps), evaluations, status (ALP_LM_RUNNING for
+ * a start that has not stopped), trial[K x D]: the pending trial point, mu / nu: the damping. */
+int alp_lm_get(alp_lm_t *h, double *x, double *cost, double *grad_norm, int64_t *iterations, int64_t *evaluations, int32_t *status,
+               double *trial, double *mu, double *nu);
+/* One round whose evaluation is replaced by the given sums: K rows in alp_normal_equations_batch's layout
+ * (D (D + 1) / 2 + D + 2 doubles; the rows of stopped starts are ignored).  Step and selection run, then it synchronises.
+ * For tests. */
+int alp_lm_step_host(alp_lm_t *h, const double *sums);
+
 /* Loss of two host arrays of pixel coordinates (n x 2 row-major doubles each): replaces the
  * stand-alone rmse(), src/alproj/optimize.py:157-178 (loss_kind ALP_LOSS_MEAN_DIST) and
  * huber_loss(), :181-212 (ALP_LOSS_HUBER).  Float64 arithmetic on the device. */
