@@ -212,6 +212,8 @@ _SIGNATURES = {
     "alp_eval_population_timing": [_c_void_p, _c_fp, _c_fp],
     "alp_eval_population_info": [_c_void_p, ctypes.POINTER(_c_i64)],
     "alp_points_set_mend": [_c_void_p, _c_int],
+    "alp_points_set_weights": [_c_void_p, _c_void_p, _c_int],
+    "alp_points_weight_sum": [_c_void_p, ctypes.POINTER(ctypes.c_double)],
     "alp_eval_population_mended": [_c_void_p, ctypes.POINTER(_c_i64)],
     "alp_loss_uv": [_c_dp, _c_dp, _c_i64, _c_int, _c_double, _c_dp],
     "alp_loss_uv_columns": [_c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_int, _c_double, _c_dp],
@@ -431,6 +433,29 @@ def normal_targets_check(target_idx):
     return idx
 
 
+def weights_check(w, n, precision=None):
+    """(n,) float32 / float64 contiguous weights, or ValueError (host arithmetic, before the library is called): another
+    length, a negative, NaN or infinite weight, and -- when no communicator shards the points -- weights whose sum is 0.
+    ``precision``: the element type of the set that will store them (ALP_F32 rounds; the sum is taken of the rounded values)."""
+    w = np.asarray(w)
+    if w.dtype not in (np.float32, np.float64):
+        w = w.astype(np.float64)
+    w = np.ascontiguousarray(w)
+    if w.shape != (n,):
+        raise ValueError(f"weights must have shape ({n},)")
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("weights must be finite and >= 0")
+    with np.errstate(over="ignore"):
+        stored = w.astype(np.float32) if precision == ALP_F32 else w
+    if not np.isfinite(stored).all():
+        raise ValueError("a weight does not fit float32")
+    world = _c_int()
+    check(load().alp_comm_info(None, ctypes.byref(world)))          # (no initialisation: the GPU is not touched)
+    if world.value == 1 and n > 0 and not stored.astype(np.float64).sum() > 0:
+        raise ValueError("the weights sum to 0: no point is left")
+    return w
+
+
 class Points:
     """Device-resident point set (RAII wrapper of alp_points_t)."""
 
@@ -509,6 +534,31 @@ class Points:
         check(self._lib.alp_points_set_observed_columns(self._h, cols[0].ctypes.data_as(_c_void_p), cols[1].ctypes.data_as(_c_void_p),
                                                         dtype_code(cols[0])))
 
+    def set_weights(self, w):
+        """Per-point frequency weights (alp_points_set_weights): ``w`` holds N finite values >= 0, ``None`` clears them.  The
+        population losses become sum w_i loss_i / W and the normal equations count both rows of point i w_i times (W = the sum
+        of the weights, which replaces the point count in what ``normal_equations*`` return); a point of weight 0 is absent,
+        whatever its distance.  A float32 set rounds the weights to float32.  ``project``, ``residuals*`` and ``jacobian``
+        ignore them.  ValueError -- the previous weights stay in force -- for another length, a negative, NaN or infinite
+        weight, and, without a communicator, for weights that are all 0."""
+        if w is None:
+            check(self._lib.alp_points_set_weights(self._h, None, ALP_F64))
+            self._weighted = False
+            return
+        w = weights_check(w, self.n, self.precision)
+        check(self._lib.alp_points_set_weights(self._h, w.ctypes.data_as(_c_void_p), dtype_code(w)))
+        self._weighted = True
+
+    def weight_sum(self):
+        """float64 sum of this rank's stored weights in index order; N when none are set (alp_points_weight_sum)"""
+        W = ctypes.c_double()
+        check(self._lib.alp_points_weight_sum(self._h, ctypes.byref(W)))
+        return float(W.value)
+
+    def _count(self, slot):
+        """the count slot of a normal-equation result: the point count, or W (a float) on a weighted set"""
+        return float(slot) if getattr(self, "_weighted", False) else int(slot)
+
     def project(self, pvec):
         pvec = np.ascontiguousarray(pvec, dtype=np.float64)
         check(self._lib.alp_project(self._h, as_dp(pvec)))
@@ -558,7 +608,8 @@ class Points:
         """-> (G (D, D) symmetric, g (D,), cost, n): the normal equations of the least-squares problem at ``pvec``, formed on
         the device (alp_normal_equations).  G = J^T J and g = J^T r with J, r the Jacobian and the residual vector
         observed - projected, scaled row by row for the robust ``loss`` ("linear", "soft_l1", "huber", "cauchy" with scipy's
-        meaning and ``f_scale``); cost = scipy's 0.5 f_scale^2 sum rho; n = the point count.  With a communicator all four are
+        meaning and ``f_scale``); cost = scipy's 0.5 f_scale^2 sum rho; n = the point count -- on a weighted set (``set_weights``)
+        W, a float, and G, g, cost those of the set in which point i appears w_i times.  With a communicator all four are
         the sums over the ranks.  ValueError, before the library is called, for an unknown loss, f_scale <= 0 or not finite,
         w / h, an index out of range or a repeated target."""
         idx = normal_targets_check(target_idx)
@@ -574,7 +625,7 @@ class Points:
         G = np.zeros((d, d), dtype=np.float64)
         G[np.triu_indices(d)] = out[:tri]
         G = G + np.triu(G, 1).T
-        return G, out[tri:tri + d].copy(), 0.5 * fs * fs * float(out[tri + d]), int(out[tri + d + 1])
+        return G, out[tri:tri + d].copy(), 0.5 * fs * fs * float(out[tri + d]), self._count(out[tri + d + 1])
 
     def normal_equations_batch(self, cand, target_idx, loss="linear", f_scale=1.0):
         """-> (G (B, D, D), g (B, D), cost (B,), n): ``normal_equations`` at the B parameter vectors ``cand`` (B, 25),
@@ -596,7 +647,7 @@ class Points:
         G = np.zeros((b, d, d), dtype=np.float64)
         G[:, iu[0], iu[1]] = out[:, :tri]
         G = G + np.triu(G, 1).transpose(0, 2, 1)
-        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], int(out[0, tri + d + 1])
+        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], self._count(out[0, tri + d + 1])
 
     def eval_population(self, cand, loss_kind, f_scale=10.0, want_argmin=True):
         """-> (losses (P,), argmin).  ``want_argmin=False``: losses only -- the library then skips the float64 confirmation

@@ -121,6 +121,7 @@ struct alp_lm {
 
 namespace alp {
 void lm_points_gone(alp_lm_t *h) { h->pts = nullptr; }
+bool lm_loop_pending(const alp_lm_t *h) { return h->pending; }
 }  // namespace alp
 
 namespace {

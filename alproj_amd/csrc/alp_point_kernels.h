@@ -452,8 +452,12 @@ __device__ __forceinline__ void distort_group(const T *r, const NormCoords<T, V>
 }
 
 // The loss of a group of V points from their squared pixel distances d2, summed: the tail of both group_loss_sum forms.
-template <typename T, int LOSS, int V, bool MASKED>
-__device__ __forceinline__ T group_loss_tail(const T (&d2)[V], const bool (&ok)[V], T f_scale) {
+// WEIGHTED (alp_points_set_weights): point j's own term is multiplied by its frequency weight wt[j] >= 0 before it enters the
+// accumulator, and a weight of 0 SELECTS the term away -- such a point is absent even when its distance is NaN or infinite (a
+// masked lane comes in with weight 0: pop_group).  A weight of 1 leaves every bit as it is: fma(1, d, acc) = acc + d, 1 . c = c.
+// Without WEIGHTED wt is never read.
+template <typename T, int LOSS, int V, bool MASKED, bool WEIGHTED = false>
+__device__ __forceinline__ T group_loss_tail(const T (&d2)[V], const bool (&ok)[V], T f_scale, const T (&wt)[V]) {
     using N = Num<T>;
     T dist[V];
 #pragma unroll
@@ -462,7 +466,8 @@ __device__ __forceinline__ T group_loss_tail(const T (&d2)[V], const bool (&ok)[
 #pragma unroll
     for (int j = 0; j < V; ++j) {
         if constexpr (LOSS == ALP_LOSS_MEAN_DIST) {
-            acc += (MASKED && !ok[j]) ? (T)0 : dist[j];                                  // optimize.py:176
+            if constexpr (WEIGHTED) acc = wt[j] > (T)0 ? N::fma(wt[j], dist[j], acc) : acc;
+            else acc += (MASKED && !ok[j]) ? (T)0 : dist[j];                             // optimize.py:176
         } else {
             // Huber (optimize.py:207-211) without a branch: with c = min(r, f),
             // 0.5 c (2r - c) = 0.5 r^2 for r <= f and f (r - 0.5 f) beyond; a NaN r gives c = f and
@@ -470,6 +475,10 @@ __device__ __forceinline__ T group_loss_tail(const T (&d2)[V], const bool (&ok)[
             // (float64, since round 5: min and two fma instead of two multiplies, an fma, a compare, two selects and an add)
             const T c = sizeof(T) == 4 ? (T)__builtin_fminf((float)dist[j], (float)f_scale) : (T)__builtin_fmin((double)dist[j], (double)f_scale);
             const T t = N::fma((T)2, dist[j], -c);
+            if constexpr (WEIGHTED) {
+                acc = wt[j] > (T)0 ? N::fma(wt[j] * c, t, acc) : acc;
+                continue;
+            }
             if (MASKED && !ok[j]) continue;
             acc = N::fma(c, t, acc);                      // twice the loss: halved once below (exact: a power of two)
         }
@@ -481,10 +490,10 @@ __device__ __forceinline__ T group_loss_tail(const T (&d2)[V], const bool (&ok)[
 // SHARED_POSE: every candidate of the call has the same rows 0..11 (only distortion
 // coefficients are optimised, the reference's second phase, example.py:75-78): the
 // normalised coordinates `pre` were computed once per point outside the candidate loop.
-template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, bool EXACT_POLES = false>
+template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, bool EXACT_POLES = false, bool WEIGHTED = false>
 __device__ __forceinline__ T group_loss_sum(const T *r, const T (&qx)[V], const T (&qy)[V], const T (&qz)[V],
                                             const NormCoords<T, V> &pre, const T (&uoc)[V], const T (&voc)[V],
-                                            const bool (&ok)[V], T f_scale) {
+                                            const bool (&ok)[V], T f_scale, const T (&wt)[V]) {
     using N = Num<T>;
     NormCoords<T, V> own;
     if constexpr (!SHARED_POSE) norm_coords<T, V>(r, qx, qy, qz, own);
@@ -498,7 +507,7 @@ __device__ __forceinline__ T group_loss_sum(const T *r, const T (&qx)[V], const 
         const T dv = N::fma(b[j], r[29], voc[j]);
         d2[j] = N::fma(dv, dv, du * du);
     }
-    return group_loss_tail<T, LOSS, V, MASKED>(d2, ok, f_scale);
+    return group_loss_tail<T, LOSS, V, MASKED, WEIGHTED>(d2, ok, f_scale, wt);
 }
 
 // LENS-FREE populations (every candidate has k1..k6 = p1 = p2 = s1..s4 = 0: the reference's first optimisation phase,
@@ -508,9 +517,10 @@ __device__ __forceinline__ T group_loss_sum(const T *r, const T (&qx)[V], const 
 // included), 2 for the squared distance, one square root and the loss -- 16 full-rate + 2 quarter-rate vector instructions where
 // the general form needs 45 + 3.  What the general form would make of a non-finite value (0 . inf = NaN where a coefficient is
 // zero) is restored by the second walk of popeval_kernel, which runs the GENERAL arithmetic on the general records.
-template <typename T, int LOSS, int V, bool MASKED>
+template <typename T, int LOSS, int V, bool MASKED, bool WEIGHTED = false>
 __device__ __forceinline__ T group_loss_sum_lens_free(const T *r, const T (&qx)[V], const T (&qy)[V], const T (&qz)[V],
-                                                      const T (&uoc)[V], const T (&voc)[V], const bool (&ok)[V], T f_scale) {
+                                                      const T (&uoc)[V], const T (&voc)[V], const bool (&ok)[V], T f_scale,
+                                                      const T (&wt)[V]) {
     using N = Num<T>;
     T zc[V], xn[V], yn[V], d2[V];
 #pragma unroll
@@ -527,7 +537,7 @@ __device__ __forceinline__ T group_loss_sum_lens_free(const T *r, const T (&qx)[
         const T dv = N::fma(yn[j], zc[j], voc[j]);
         d2[j] = N::fma(dv, dv, du * du);
     }
-    return group_loss_tail<T, LOSS, V, MASKED>(d2, ok, f_scale);
+    return group_loss_tail<T, LOSS, V, MASKED, WEIGHTED>(d2, ok, f_scale, wt);
 }
 
 // ------------------------------------------------------------------ K3: residual vectors of B poses
@@ -748,11 +758,14 @@ __device__ __forceinline__ double normal_rho(double z, double &s, double &w) {
 // The body of normal_kernel and normal_batch_kernel: the workgroup's stripe `stripe` of `groups_per` groups under `plan`, its
 // sums to row `out_row` of `partials` (T doubles each).  `stripe`, `plan` and `out_row` are the same in every lane (the plan comes in by
 // scalar loads).
-template <typename TS, int LOSS>
+// WEIGHTED (alp_points_set_weights): both rows of point i count w_i times -- the row scalings s and w are multiplied by
+// sqrt(w_i) and the cost gets w_i rho; a point of weight 0 contributes exact zeros, like a masked lane, whatever its rows hold.
+// sqrt(1) = 1: unit weights leave every bit.  Without WEIGHTED wts is never read.
+template <typename TS, int LOSS, bool WEIGHTED = false>
 __device__ __forceinline__ void normal_body(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
                                             const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n, int64_t groups_per,
                                             double inv_f_scale, const JacPlan *__restrict__ plan, int64_t stripe,
-                                            double *__restrict__ partials, int64_t out_row) {
+                                            double *__restrict__ partials, int64_t out_row, const TS *__restrict__ wts) {
     __shared__ double s_tile[4][NRM_TILE];
     __shared__ double s_cost[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -770,8 +783,13 @@ __device__ __forceinline__ void normal_body(const TS *__restrict__ x, const TS *
     const int64_t end = (beg + groups_per * 256 < n) ? beg + groups_per * 256 : n;
     for (int64_t base = beg; base < end; base += 256) {
         const int64_t i = base + tid;
-        const bool ok = i < end;
-        const int64_t k = ok ? i : base;              // a group's first point always exists
+        const int64_t k = i < end ? i : base;         // a group's first point always exists
+        double wt = 1.0, sw = 1.0;
+        if constexpr (WEIGHTED) {
+            wt = (double)wts[k];
+            sw = __builtin_sqrt(wt);
+        }
+        const bool ok = WEIGHTED ? (i < end && wt > 0.0) : i < end;
         const double qx = (double)x[k], qy = (double)y[k], qz = (double)z[k];
         // the residuals: K3's float64 arithmetic (project_norm / to_pixels on the plan's record = fold_pose's)
         double xd, yd, pu, pv;
@@ -784,7 +802,12 @@ __device__ __forceinline__ void normal_body(const TS *__restrict__ x, const TS *
         for (int h = 0; h < 2; ++h) {                 // the u rows of the wave's 64 points, then their v rows
             const double t = r[h] * inv_f_scale;
             double s, w;
-            const double rho = normal_rho<LOSS>(t * t, s, w);
+            double rho = normal_rho<LOSS>(t * t, s, w);
+            if constexpr (WEIGHTED) {
+                s *= sw;
+                w *= sw;
+                rho *= wt;
+            }
             cost += ok ? rho : 0.0;
             for (int m = 0; m < D; ++m) tile[m * NRM_RS + lane] = ok ? s * jac_value(plan, P, h * D + m) : 0.0;
             tile[D * NRM_RS + lane] = ok ? w * r[h] : 0.0;
@@ -838,12 +861,12 @@ __device__ __forceinline__ void normal_body(const TS *__restrict__ x, const TS *
     }
 }
 
-template <typename TS, int LOSS>
+template <typename TS, int LOSS, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
                                                      const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
                                                      int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plan,
-                                                     double *__restrict__ partials) {
-    normal_body<TS, LOSS>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plan, (int64_t)blockIdx.x, partials, (int64_t)blockIdx.x);
+                                                     double *__restrict__ partials, const TS *__restrict__ wts) {
+    normal_body<TS, LOSS, WEIGHTED>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plan, (int64_t)blockIdx.x, partials, (int64_t)blockIdx.x, wts);
 }
 
 // K3n for B poses over the same points (alp_normal_equations_batch): one workgroup per (stripe, pose) pair of
@@ -852,19 +875,19 @@ __global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, c
 // workgroups of one stripe under all poses are dispatched next to each other, so that the stripe's points are fetched from HBM
 // once and found in the cache by the other poses); the sums do not depend on it.
 constexpr int NORMAL_BATCH_POSE_IN_X = 1;
-template <typename TS, int LOSS>
+template <typename TS, int LOSS, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void normal_batch_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
                                                            const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
                                                            int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
-                                                           int pose_in_x, double *__restrict__ partials) {
+                                                           int pose_in_x, double *__restrict__ partials, const TS *__restrict__ wts) {
     const int pose = pose_in_x ? blockIdx.x : blockIdx.y, stripe = pose_in_x ? blockIdx.y : blockIdx.x;
     const int stripes = pose_in_x ? gridDim.y : gridDim.x;
-    normal_body<TS, LOSS>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
-                          (int64_t)pose * stripes + stripe);
+    normal_body<TS, LOSS, WEIGHTED>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
+                                    (int64_t)pose * stripes + stripe, wts);
 }
 
 // sums[q * (T + 1) + c] = sum over the stripes of pose q's partial rows (reduce_partials_kernel's order: 8 row-groups, each
-// over every 8th stripe, then the 8 in order), sums[q * (T + 1) + T] = the local point count: row q has
+// over every 8th stripe, then the 8 in order), sums[q * (T + 1) + T] = n_local, the local point count or, on a weighted set, the local sum of the weights: row q has
 // alp_normal_equations' layout.  blockIdx.y = the pose; one workgroup handles 32 sums x 8 row-groups.
 __global__ __launch_bounds__(256) void reduce_normal_batch_kernel(const double *__restrict__ partials, int stripes, int T, double n_local,
                                                                   double *__restrict__ sums) {
@@ -893,16 +916,16 @@ __global__ __launch_bounds__(256) void reduce_normal_batch_kernel(const double *
 // ascending order; a workgroup with b >= *count returns at once.  The partial row is the one normal_batch_kernel would write for
 // pose list[b] of K, so a start's stripes and the order of its additions do not depend on which other starts still run.
 // list[b] is the same in every lane: the plan still comes in by scalar loads.
-template <typename TS, int LOSS>
+template <typename TS, int LOSS, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void normal_batch_listed_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
                                                                   const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
                                                                   int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
                                                                   const int *__restrict__ list, const long long *__restrict__ count,
-                                                                  double *__restrict__ partials) {
+                                                                  double *__restrict__ partials, const TS *__restrict__ wts) {
     if ((long long)blockIdx.x >= *count) return;
     const int pose = list[blockIdx.x], stripe = blockIdx.y, stripes = gridDim.y;
-    normal_body<TS, LOSS>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
-                          (int64_t)pose * stripes + stripe);
+    normal_body<TS, LOSS, WEIGHTED>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
+                                    (int64_t)pose * stripes + stripe, wts);
 }
 
 // reduce_normal_batch_kernel for those starts: row q of `sums` for a running start (running[q] != 0) in the same order of
@@ -932,15 +955,18 @@ __global__ __launch_bounds__(256) void reduce_normal_listed_kernel(const double 
 
 // TS = element type of the planes in HBM, T = arithmetic type (TS = float with T = double is the
 // float64 re-evaluation of a float32 point set: alp_eval_population's argmin confirmation)
-template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, typename TS = T, bool EXACT_POLES = false, bool LENS_FREE = false>
+// WEIGHTED: the weight plane `wts` is read beside uo / vo, at the same index (the masked lanes' stand-in index included, whose
+// weight is then set to 0); otherwise wts is never read.
+template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, typename TS = T, bool EXACT_POLES = false, bool LENS_FREE = false,
+          bool WEIGHTED = false>
 __device__ __forceinline__ void pop_group(const TS *__restrict__ x, const TS *__restrict__ y,
                                           const TS *__restrict__ z, const TS *__restrict__ uo,
-                                          const TS *__restrict__ vo, int64_t base, int64_t end,
+                                          const TS *__restrict__ vo, const TS *__restrict__ wts, int64_t base, int64_t end,
                                           const PoseRec<T> *s_c, double *s_sum_wave, int tc, T f_scale,
                                           unsigned long long redo_lo = ~0ull, unsigned long long redo_hi = ~0ull) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    T qx[V], qy[V], qz[V], uoc[V], voc[V];
+    T qx[V], qy[V], qz[V], uoc[V], voc[V], wt[V];
     bool ok[V];
     const T c0 = s_c[0].v[26], c1 = s_c[0].v[27];     // identical in every record of a call
 #pragma unroll
@@ -951,6 +977,7 @@ __device__ __forceinline__ void pop_group(const TS *__restrict__ x, const TS *__
         qx[j] = (T)x[i]; qy[j] = (T)y[i]; qz[j] = (T)z[i];
         uoc[j] = (T)uo[i] - c0;
         voc[j] = (T)vo[i] - c1;
+        if constexpr (WEIGHTED) wt[j] = ok[j] ? (T)wts[i] : (T)0;
     }
     NormCoords<T, V> pre;
     if constexpr (SHARED_POSE && !LENS_FREE) norm_coords<T, V>(s_c[0].v, qx, qy, qz, pre);
@@ -967,8 +994,8 @@ __device__ __forceinline__ void pop_group(const TS *__restrict__ x, const TS *__
             for (int e = 0; e < Num<T>::VEC; ++e) r[k * Num<T>::VEC + e] = vget<T>(t, e);
         }
         T acc;
-        if constexpr (LENS_FREE) acc = group_loss_sum_lens_free<T, LOSS, V, MASKED>(r, qx, qy, qz, uoc, voc, ok, f_scale);
-        else acc = group_loss_sum<T, LOSS, V, MASKED, SHARED_POSE, EXACT_POLES>(r, qx, qy, qz, pre, uoc, voc, ok, f_scale);
+        if constexpr (LENS_FREE) acc = group_loss_sum_lens_free<T, LOSS, V, MASKED, WEIGHTED>(r, qx, qy, qz, uoc, voc, ok, f_scale, wt);
+        else acc = group_loss_sum<T, LOSS, V, MASKED, SHARED_POSE, EXACT_POLES, WEIGHTED>(r, qx, qy, qz, pre, uoc, voc, ok, f_scale, wt);
         acc = wave_sum_to_lane63(acc);
         if (lane == 63) s_sum_wave[c] += (double)acc;
     }
@@ -979,9 +1006,10 @@ __device__ __forceinline__ void pop_group(const TS *__restrict__ x, const TS *__
 
 // one workgroup's stripe [beg, end) against the tc staged records: wide groups of V rows, the rows they leave over two at a
 // time, the ragged last row masked
-template <typename T, int LOSS, int V, bool SHARED_POSE, typename TS, bool EXACT_POLES, bool LENS_FREE = false>
+template <typename T, int LOSS, int V, bool SHARED_POSE, typename TS, bool EXACT_POLES, bool LENS_FREE = false, bool WEIGHTED = false>
 __device__ __forceinline__ void pop_walk_stripe(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
-                                                const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t beg, int64_t end,
+                                                const TS *__restrict__ uo, const TS *__restrict__ vo, const TS *__restrict__ wts,
+                                                int64_t beg, int64_t end,
                                                 const PoseRec<T> *recs, double *s_sum_wave, int tc, T f_scale,
                                                 unsigned long long redo_lo = ~0ull, unsigned long long redo_hi = ~0ull) {
     // (the second walk, EXACT_POLES, goes row by row: it is rare, and its two reciprocals per point over V points in flight
@@ -989,22 +1017,22 @@ __device__ __forceinline__ void pop_walk_stripe(const TS *__restrict__ x, const 
     constexpr int VW = EXACT_POLES ? 1 : V;
     int64_t base = beg;
     for (; base + 256 * VW <= end; base += 256 * VW)
-        pop_group<T, LOSS, VW, false, SHARED_POSE, TS, EXACT_POLES, LENS_FREE>(x, y, z, uo, vo, base, end, recs, s_sum_wave, tc, f_scale, redo_lo, redo_hi);
+        pop_group<T, LOSS, VW, false, SHARED_POSE, TS, EXACT_POLES, LENS_FREE, WEIGHTED>(x, y, z, uo, vo, wts, base, end, recs, s_sum_wave, tc, f_scale, redo_lo, redo_hi);
     if constexpr (VW > 2)      // the rows left over by the wide groups, two at a time
         for (; base + 512 <= end; base += 512)
-            pop_group<T, LOSS, 2, false, SHARED_POSE, TS, EXACT_POLES, LENS_FREE>(x, y, z, uo, vo, base, end, recs, s_sum_wave, tc, f_scale, redo_lo, redo_hi);
+            pop_group<T, LOSS, 2, false, SHARED_POSE, TS, EXACT_POLES, LENS_FREE, WEIGHTED>(x, y, z, uo, vo, wts, base, end, recs, s_sum_wave, tc, f_scale, redo_lo, redo_hi);
     for (; base < end; base += 256)
-        pop_group<T, LOSS, 1, true, SHARED_POSE, TS, EXACT_POLES, LENS_FREE>(x, y, z, uo, vo, base, end, recs, s_sum_wave, tc, f_scale, redo_lo, redo_hi);
+        pop_group<T, LOSS, 1, true, SHARED_POSE, TS, EXACT_POLES, LENS_FREE, WEIGHTED>(x, y, z, uo, vo, wts, base, end, recs, s_sum_wave, tc, f_scale, redo_lo, redo_hi);
 }
 
 // LENS_FREE: `cands` holds the lens-free records (fold_pose_lens_free) the first walk runs on, `cands_general` the general ones
 // (fold_pose) of the same candidates for the second walk; otherwise both are the general records.
 // (the body of popeval_kernel and of popeval_counted_kernel below, which takes P from device memory)
-template <typename T, int LOSS, typename Cfg, bool SHARED_POSE, typename TS, bool LENS_FREE>
+template <typename T, int LOSS, typename Cfg, bool SHARED_POSE, typename TS, bool LENS_FREE, bool WEIGHTED = false>
 __device__ __forceinline__ void popeval_body(
     const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z, const TS *__restrict__ uo,
     const TS *__restrict__ vo, int64_t n, const PoseRec<T> *__restrict__ cands, int P, T f_scale,
-    double *__restrict__ partials, const PoseRec<T> *__restrict__ cands_general) {
+    double *__restrict__ partials, const PoseRec<T> *__restrict__ cands_general, const TS *__restrict__ wts) {
     constexpr int TC = Cfg::TC;
     constexpr int V = Cfg::V;
     static_assert(TC <= 128, "the second walk's candidate mask is two 64-bit words");
@@ -1032,7 +1060,7 @@ __device__ __forceinline__ void popeval_body(
             for (int i = tid; i < 4 * TC; i += 256) (&s_sum[0][0])[i] = 0.0;
         }
         __syncthreads();
-        pop_walk_stripe<T, LOSS, V, SHARED_POSE, TS, false, LENS_FREE>(x, y, z, uo, vo, beg, end, s_c, s_sum[wave], tc, f_scale);
+        pop_walk_stripe<T, LOSS, V, SHARED_POSE, TS, false, LENS_FREE, WEIGHTED>(x, y, z, uo, vo, wts, beg, end, s_c, s_sum[wave], tc, f_scale);
         // A sum that is not finite stays so (inf and NaN are sticky under +): looked for ONCE per wave, tile and stripe -- nothing
         // in the loop above pays for it.  The wave's rows are its own (lane t owns points t, t + 256, ...), so are its sums:
         // it clears the sums of the candidates concerned and walks its share again for THOSE candidates, row by row, with the
@@ -1054,9 +1082,9 @@ __device__ __forceinline__ void popeval_body(
                 // (a lens-free tile: the LDS holds the folded rows only, so the general records are read where they lie in HBM --
                 // wave-uniform loads, slow and rare; SHARED_POSE's hoisted coordinates are not used by either walk then)
                 if constexpr (LENS_FREE)
-                    pop_walk_stripe<T, LOSS, V, false, TS, true>(x, y, z, uo, vo, beg, end, cands_general + c0, s_sum[wave], tc, f_scale, redo_lo, redo_hi);
+                    pop_walk_stripe<T, LOSS, V, false, TS, true, false, WEIGHTED>(x, y, z, uo, vo, wts, beg, end, cands_general + c0, s_sum[wave], tc, f_scale, redo_lo, redo_hi);
                 else
-                    pop_walk_stripe<T, LOSS, V, SHARED_POSE, TS, true>(x, y, z, uo, vo, beg, end, s_c, s_sum[wave], tc, f_scale, redo_lo, redo_hi);
+                    pop_walk_stripe<T, LOSS, V, SHARED_POSE, TS, true, false, WEIGHTED>(x, y, z, uo, vo, wts, beg, end, s_c, s_sum[wave], tc, f_scale, redo_lo, redo_hi);
             }
         }
         __syncthreads();
@@ -1066,12 +1094,13 @@ __device__ __forceinline__ void popeval_body(
     }
 }
 
-template <typename T, int LOSS, typename Cfg = PopCfg<T>, bool SHARED_POSE = false, typename TS = T, bool LENS_FREE = false>
+// WEIGHTED: `wts` = the set's weight plane (alp_points_set_weights); the unweighted kernels never read the argument.
+template <typename T, int LOSS, typename Cfg = PopCfg<T>, bool SHARED_POSE = false, typename TS = T, bool LENS_FREE = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(256, Cfg::MINW) void popeval_kernel(
     const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z, const TS *__restrict__ uo,
     const TS *__restrict__ vo, int64_t n, const PoseRec<T> *__restrict__ cands, int P, T f_scale,
-    double *__restrict__ partials, const PoseRec<T> *__restrict__ cands_general) {
-    popeval_body<T, LOSS, Cfg, SHARED_POSE, TS, LENS_FREE>(x, y, z, uo, vo, n, cands, P, f_scale, partials, cands_general);
+    double *__restrict__ partials, const PoseRec<T> *__restrict__ cands_general, const TS *__restrict__ wts) {
+    popeval_body<T, LOSS, Cfg, SHARED_POSE, TS, LENS_FREE, WEIGHTED>(x, y, z, uo, vo, n, cands, P, f_scale, partials, cands_general, wts);
 }
 
 // ------------------------------------------------------------------ K2m: the mend pass of a float32 population evaluation
@@ -1090,14 +1119,14 @@ struct MendCount {
 // popeval_kernel<double, LOSS, PopCfg<double>, false, float> over the first cnt->last records: the grid is planned for the worst
 // case (host::mend_grid: every candidate selected), and a workgroup whose first tile lies at or beyond the count returns at
 // once.  The partial rows are `count` doubles long.
-template <int LOSS>
+template <int LOSS, bool WEIGHTED = false>
 __global__ __launch_bounds__(256, PopCfg<double>::MINW) void popeval_counted_kernel(
     const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, const float *__restrict__ uo,
     const float *__restrict__ vo, int64_t n, const PoseRec<double> *__restrict__ cands, const MendCount *__restrict__ cnt,
-    double f_scale, double *__restrict__ partials) {
+    double f_scale, double *__restrict__ partials, const float *__restrict__ wts) {
     const int count = (int)cnt->last;
     if ((int)blockIdx.y * PopCfg<double>::TC >= count) return;
-    popeval_body<double, LOSS, PopCfg<double>, false, float, false>(x, y, z, uo, vo, n, cands, count, f_scale, partials, cands);
+    popeval_body<double, LOSS, PopCfg<double>, false, float, false, WEIGHTED>(x, y, z, uo, vo, n, cands, count, f_scale, partials, cands, wts);
 }
 
 // One workgroup.  idx[0 .. count) = the candidates c < P whose sums[c] is infinite or NaN, ascending (ballot + prefix, no
@@ -1168,7 +1197,8 @@ __global__ __launch_bounds__(256) void mend_scatter_kernel(const int *__restrict
     if (k < (int)cnt->last) sums[idx[k]] = mended[k];
 }
 
-// sums[c] = sum over workgroups of partials[b][c] (fixed order); sums[P] = local point count.
+// sums[c] = sum over workgroups of partials[b][c] (fixed order); sums[P] = n_local: the local point count or, on a weighted
+// set, the local sum of the weights (every consumer divides by the slot, all-reduced).
 // One workgroup handles 32 candidates x 8 row-groups.
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const double *__restrict__ partials,
                                                               int nblk, int P, double n_local,

@@ -269,12 +269,12 @@ int mend_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, const d
     hipLaunchKernelGGL(mend_select_kernel, dim3(1), dim3(256), 0, st, (const double *)p->sums_dev, (int)P, params_dev, p->origin[0],
                        p->origin[1], p->origin[2], mend_idx(p), mend_recs(p), cnt);
     ALP_HIP(hipGetLastError());
-    if (loss_kind == ALP_LOSS_HUBER)
-        hipLaunchKernelGGL(popeval_counted_kernel<ALP_LOSS_HUBER>, dim3(g.stripes, g.tile_cols), dim3(256), 0, st, x, y, z, uo, vo, p->n,
-                           (const PoseRec<double> *)mend_recs(p), (const MendCount *)cnt, f_scale, p->partials);
-    else
-        hipLaunchKernelGGL(popeval_counted_kernel<ALP_LOSS_MEAN_DIST>, dim3(g.stripes, g.tile_cols), dim3(256), 0, st, x, y, z, uo, vo,
-                           p->n, (const PoseRec<double> *)mend_recs(p), (const MendCount *)cnt, f_scale, p->partials);
+    using Kernel = void (*)(const float *, const float *, const float *, const float *, const float *, int64_t, const PoseRec<double> *,
+                            const MendCount *, double, double *, const float *);
+    static const Kernel kernels[2][2] = {{popeval_counted_kernel<ALP_LOSS_MEAN_DIST>, popeval_counted_kernel<ALP_LOSS_HUBER>},
+                                         {popeval_counted_kernel<ALP_LOSS_MEAN_DIST, true>, popeval_counted_kernel<ALP_LOSS_HUBER, true>}};
+    hipLaunchKernelGGL(kernels[p->w != nullptr][loss_kind == ALP_LOSS_HUBER], dim3(g.stripes, g.tile_cols), dim3(256), 0, st, x, y, z, uo,
+                       vo, p->n, (const PoseRec<double> *)mend_recs(p), (const MendCount *)cnt, f_scale, p->partials, (const float *)p->w);
     ALP_HIP(hipGetLastError());
     hipLaunchKernelGGL(mend_reduce_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, st, (const double *)p->partials, g.stripes,
                        (int)P, (const MendCount *)cnt, mend_sums(p));
@@ -287,18 +287,31 @@ int mend_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, const d
 }
 
 // the launch half of enqueue_popeval (alp_points_internal.h: popeval_launch): the records lie in p->cand_dev
+// The weighted shared-pose variant in float64 asks for two waves per SIMD instead of three: its unweighted form sits at the 168
+// VGPRs of three waves already (the hoisted coordinates), and the weight's two registers per row spilled 44 bytes per lane to
+// scratch under that cap.  Its V stays PopCfg's: unit weights must add in the unweighted kernel's order, bit for bit.
+template <typename T> struct PopCfgWS : PopCfg<T> {};
+template <> struct PopCfgWS<double> : PopCfgT<double, POP_VD, POP_TCD, 2> {};
+
 template <typename T>
 int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched = false,
                      const double *params_dev = nullptr) {
     using Kernel = void (*)(const T *, const T *, const T *, const T *, const T *, int64_t, const PoseRec<T> *, int, T,
-                            double *, const PoseRec<T> *);
+                            double *, const PoseRec<T> *, const T *);
     const int which = (loss_kind == ALP_LOSS_HUBER ? 3 : 0) + (lens_free ? 2 : (shared_pose ? 1 : 0));
-    const Kernel kernels[6] = {popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfg<T>, false>,
-                               popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfg<T>, true>,
-                               popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfgLF<T>, false, T, true>,
-                               popeval_kernel<T, ALP_LOSS_HUBER, PopCfg<T>, false>,
-                               popeval_kernel<T, ALP_LOSS_HUBER, PopCfg<T>, true>,
-                               popeval_kernel<T, ALP_LOSS_HUBER, PopCfgLF<T>, false, T, true>};
+    // a set without weights takes row 0: the kernels it always took; a weighted set the same variant with WEIGHTED
+    const Kernel kernels[2][6] = {{popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfg<T>, false>,
+                                   popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfg<T>, true>,
+                                   popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfgLF<T>, false, T, true>,
+                                   popeval_kernel<T, ALP_LOSS_HUBER, PopCfg<T>, false>,
+                                   popeval_kernel<T, ALP_LOSS_HUBER, PopCfg<T>, true>,
+                                   popeval_kernel<T, ALP_LOSS_HUBER, PopCfgLF<T>, false, T, true>},
+                                  {popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfg<T>, false, T, false, true>,
+                                   popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfgWS<T>, true, T, false, true>,
+                                   popeval_kernel<T, ALP_LOSS_MEAN_DIST, PopCfgLF<T>, false, T, true, true>,
+                                   popeval_kernel<T, ALP_LOSS_HUBER, PopCfg<T>, false, T, false, true>,
+                                   popeval_kernel<T, ALP_LOSS_HUBER, PopCfgWS<T>, true, T, false, true>,
+                                   popeval_kernel<T, ALP_LOSS_HUBER, PopCfgLF<T>, false, T, true, true>}};
     static_assert(PopCfg<T>::TC == PopCfgLF<T>::TC, "one candidate tile size per precision: host::pop_grid takes one TC");
     // the grid rule: host/alp_plan.h.  ALP_POP_GRID = "stripes,ytiles" (a development switch) overrides it where the pair is valid:
     // one that does not parse leaves a 0, which pop_grid ignores
@@ -322,12 +335,12 @@ int popeval_launch_t(alp_points *p, int64_t P, int loss_kind, double f_scale, bo
     p->last_info[2] = g.tile_cols;
     ALP_HIP(hipEventRecord(p->ev[0], ctx().stream));
     const PoseRec<T> *recs_general = (const PoseRec<T> *)p->cand_dev;
-    hipLaunchKernelGGL(kernels[which], dim3(g.stripes, g.tile_cols), dim3(256), 0, ctx().stream, (const T *)p->x, (const T *)p->y,
+    hipLaunchKernelGGL(kernels[p->w != nullptr][which], dim3(g.stripes, g.tile_cols), dim3(256), 0, ctx().stream, (const T *)p->x, (const T *)p->y,
                        (const T *)p->z, (const T *)p->uo, (const T *)p->vo, p->n, lens_free ? recs_general + p->cand_cap : recs_general,
-                       (int)P, (T)f_scale, p->partials, recs_general);
+                       (int)P, (T)f_scale, p->partials, recs_general, (const T *)p->w);
     ALP_HIP(hipGetLastError());
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, ctx().stream,
-                       p->partials, g.stripes, (int)P, (double)p->n, p->sums_dev);
+                       p->partials, g.stripes, (int)P, p->count_slot(), p->sums_dev);
     ALP_HIP(hipGetLastError());
     ALP_HIP(hipEventRecord(p->ev[1], ctx().stream));
     if (int rc = comm_allreduce_sum_f64(p->sums_dev, P + 1)) return rc;
@@ -408,7 +421,7 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
 
 // float64 re-evaluation of K <= CONFIRM_MAX candidates of a float32 point set (same stored
 // coordinates, double arithmetic, same fixed-order reduction and the same all-reduce):
-// sums_out[0..K) = loss sums, sums_out[K] = vertex count.  Synchronous.
+// sums_out[0..K) = loss sums, sums_out[K] = vertex count (the sum of the weights on a weighted set).  Synchronous.
 int confirm_losses(alp_points *p, const double *cand, const int64_t *which, int K, int loss_kind, double f_scale,
                    double *sums_out) {
     const int nblk = host::confirm_grid(p->n, ctx().cu_count);
@@ -428,14 +441,16 @@ int confirm_losses(alp_points *p, const double *cand, const int64_t *which, int 
     ALP_HIP(hipMemcpyAsync(recs_dev, recs, (size_t)K * sizeof(PoseRec<double>), hipMemcpyHostToDevice, ctx().stream));
     const float *x = (const float *)p->x, *y = (const float *)p->y, *z = (const float *)p->z;
     const float *uo = (const float *)p->uo, *vo = (const float *)p->vo;
-    if (loss_kind == ALP_LOSS_HUBER)
-        hipLaunchKernelGGL((popeval_kernel<double, ALP_LOSS_HUBER, PopCfg<double>, false, float>), dim3(nblk), dim3(256), 0,
-                           ctx().stream, x, y, z, uo, vo, p->n, recs_dev, K, f_scale, partials, recs_dev);
-    else
-        hipLaunchKernelGGL((popeval_kernel<double, ALP_LOSS_MEAN_DIST, PopCfg<double>, false, float>), dim3(nblk), dim3(256),
-                           0, ctx().stream, x, y, z, uo, vo, p->n, recs_dev, K, f_scale, partials, recs_dev);
+    using Kernel = void (*)(const float *, const float *, const float *, const float *, const float *, int64_t, const PoseRec<double> *, int,
+                            double, double *, const PoseRec<double> *, const float *);
+    static const Kernel kernels[2][2] = {{popeval_kernel<double, ALP_LOSS_MEAN_DIST, PopCfg<double>, false, float>,
+                                          popeval_kernel<double, ALP_LOSS_HUBER, PopCfg<double>, false, float>},
+                                         {popeval_kernel<double, ALP_LOSS_MEAN_DIST, PopCfg<double>, false, float, false, true>,
+                                          popeval_kernel<double, ALP_LOSS_HUBER, PopCfg<double>, false, float, false, true>}};
+    hipLaunchKernelGGL(kernels[p->w != nullptr][loss_kind == ALP_LOSS_HUBER], dim3(nblk), dim3(256), 0, ctx().stream, x, y, z, uo, vo, p->n,
+                       (const PoseRec<double> *)recs_dev, K, f_scale, partials, (const PoseRec<double> *)recs_dev, (const float *)p->w);
     ALP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, ctx().stream, partials, nblk, K, (double)p->n, sums_dev);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, ctx().stream, partials, nblk, K, p->count_slot(), sums_dev);
     ALP_HIP(hipGetLastError());
     if (int rc = comm_allreduce_sum_f64(sums_dev, K + 1)) return rc;
     ALP_HIP(hipMemcpyAsync(p->conf_host, sums_dev, (size_t)(K + 1) * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
@@ -510,9 +525,12 @@ int jacobian_impl(alp_points *p, const JacPlan &plan, double *out) {
 // The scratch holds the plan, the partial rows and the T + 1 sums; T + 1 doubles cross PCIe.
 template <typename TS>
 int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, double *out) {
-    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, double *);
-    static const Kernel kernels[4] = {normal_kernel<TS, ALP_NORMAL_LINEAR>, normal_kernel<TS, ALP_NORMAL_SOFT_L1>,
-                                      normal_kernel<TS, ALP_NORMAL_HUBER>, normal_kernel<TS, ALP_NORMAL_CAUCHY>};
+    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, double *,
+                            const TS *);
+    static const Kernel kernels[2][4] = {{normal_kernel<TS, ALP_NORMAL_LINEAR>, normal_kernel<TS, ALP_NORMAL_SOFT_L1>,
+                                          normal_kernel<TS, ALP_NORMAL_HUBER>, normal_kernel<TS, ALP_NORMAL_CAUCHY>},
+                                         {normal_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
+                                          normal_kernel<TS, ALP_NORMAL_HUBER, true>, normal_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
     const int D = plan.D, T = D * (D + 1) / 2 + D + 1;
     const host::NormalGrid g = host::normal_grid(p->n, ctx().cu_count);
     const size_t plan_bytes = round_up((int64_t)sizeof(JacPlan), 256);
@@ -524,9 +542,10 @@ int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, do
     if (g.blocks > 0) {
         ALP_HIP(hipMemcpyAsync(plan_dev, &plan, sizeof(JacPlan), hipMemcpyHostToDevice, st));
         ktime_begin();
-        hipLaunchKernelGGL(kernels[loss], dim3(g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z,
-                           (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plan_dev, partials);
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((T + 31) / 32)), dim3(256), 0, st, partials, g.blocks, T, (double)p->n, sums);
+        hipLaunchKernelGGL(kernels[p->w != nullptr][loss], dim3(g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z,
+                           (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plan_dev, partials,
+                           (const TS *)p->w);
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((T + 31) / 32)), dim3(256), 0, st, partials, g.blocks, T, p->count_slot(), sums);
         ktime_end();
         ALP_HIP(hipGetLastError());
     } else {
@@ -544,9 +563,12 @@ int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, do
 // index that runs fastest; the sums do not depend on it.
 template <typename TS>
 int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss, double f_scale, double *out) {
-    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, int, double *);
-    static const Kernel kernels[4] = {normal_batch_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1>,
-                                      normal_batch_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_kernel<TS, ALP_NORMAL_CAUCHY>};
+    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, int, double *,
+                            const TS *);
+    static const Kernel kernels[2][4] = {{normal_batch_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1>,
+                                          normal_batch_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_kernel<TS, ALP_NORMAL_CAUCHY>},
+                                         {normal_batch_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
+                                          normal_batch_kernel<TS, ALP_NORMAL_HUBER, true>, normal_batch_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
     const int64_t B = (int64_t)plans.size();
     const int D = plans[0].D, T = D * (D + 1) / 2 + D + 1;
     const host::NormalGrid g = host::normal_batch_grid(p->n, B, ctx().cu_count);
@@ -562,10 +584,10 @@ int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss
         const dim3 grid = pose_in_x ? dim3((unsigned)B, (unsigned)g.blocks) : dim3((unsigned)g.blocks, (unsigned)B);
         ALP_HIP(hipMemcpyAsync(plans_dev, plans.data(), (size_t)B * sizeof(JacPlan), hipMemcpyHostToDevice, st));
         ktime_begin();
-        hipLaunchKernelGGL(kernels[loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
-                           (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials);
+        hipLaunchKernelGGL(kernels[p->w != nullptr][loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
+                           (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials, (const TS *)p->w);
         hipLaunchKernelGGL(reduce_normal_batch_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)B), dim3(256), 0, st, partials, g.blocks, T,
-                           (double)p->n, sums);
+                           p->count_slot(), sums);
         ktime_end();
         ALP_HIP(hipGetLastError());
     } else {
@@ -583,16 +605,20 @@ template <typename TS>
 int normal_listed_impl(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
                        const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums) {
     using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, const int *,
-                            const long long *, double *);
-    static const Kernel kernels[4] = {normal_batch_listed_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_listed_kernel<TS, ALP_NORMAL_SOFT_L1>,
-                                      normal_batch_listed_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_listed_kernel<TS, ALP_NORMAL_CAUCHY>};
+                            const long long *, double *, const TS *);
+    static const Kernel kernels[2][4] = {
+        {normal_batch_listed_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_listed_kernel<TS, ALP_NORMAL_SOFT_L1>,
+         normal_batch_listed_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_listed_kernel<TS, ALP_NORMAL_CAUCHY>},
+        {normal_batch_listed_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_batch_listed_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
+         normal_batch_listed_kernel<TS, ALP_NORMAL_HUBER, true>, normal_batch_listed_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
     const int T = D * (D + 1) / 2 + D + 1;
     hipStream_t st = ctx().stream;
     if (g.blocks > 0) {
-        hipLaunchKernelGGL(kernels[loss], dim3((unsigned)K, (unsigned)g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
-                           (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, list, count, partials);
+        hipLaunchKernelGGL(kernels[p->w != nullptr][loss], dim3((unsigned)K, (unsigned)g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
+                           (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, list, count, partials,
+                           (const TS *)p->w);
         hipLaunchKernelGGL(reduce_normal_listed_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)K), dim3(256), 0, st, (const double *)partials,
-                           g.blocks, T, (double)p->n, running, sums);
+                           g.blocks, T, p->count_slot(), running, sums);
         ALP_HIP(hipGetLastError());
     } else {
         ALP_HIP(hipMemsetAsync(sums, 0, (size_t)K * (T + 1) * sizeof(double), st));       // an empty shard still joins the all-reduce
@@ -702,6 +728,51 @@ int fetch_converted(alp_points *p, void *u_out, void *v_out, int out_dtype) {
 }
 }  // namespace
 
+namespace {
+// the n weights as the set stores them (rounded to T), validated; *sum = their float64 sum in index order
+template <typename TIn, typename T>
+int weights_stored(const void *w, int64_t n, std::vector<T> &out, double *sum) {
+    const TIn *src = (const TIn *)w;
+    out.resize((size_t)n);
+    double s = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const double v = (double)src[i];
+        if (!(v >= 0.0) || !std::isfinite(v))
+            return fail(ALP_EINVAL, "alp_points_set_weights: weight %lld is negative, NaN or infinite", (long long)i);
+        const T t = (T)v;
+        if (!std::isfinite((double)t)) return fail(ALP_EINVAL, "alp_points_set_weights: weight %lld does not fit the set's element type", (long long)i);
+        out[(size_t)i] = t;
+        s += (double)t;
+    }
+    *sum = s;
+    return ALP_OK;
+}
+
+template <typename T>
+int set_weights_t(alp_points *p, const void *w, int in_dtype) {
+    std::vector<T> stored;
+    double sum = 0;
+    if (int rc = in_dtype == ALP_F64 ? weights_stored<double, T>(w, p->n, stored, &sum) : weights_stored<float, T>(w, p->n, stored, &sum)) return rc;
+    // (nothing of the set has changed so far: a refused call leaves the previous weights in force)
+    if (!p->w) {
+        void *plane = nullptr;
+        ALP_HIP(hipMalloc(&plane, (size_t)p->n_pad * sizeof(T)));
+        hipError_t e = hipMemsetAsync(plane, 0, (size_t)p->n_pad * sizeof(T), ctx().stream);
+        if (e != hipSuccess) {
+            hipFree(plane);
+            return fail(ALP_EHIP, "alp_points_set_weights: %s", hipGetErrorString(e));
+        }
+        p->w = plane;
+        p->w_sum = 0;           // until the copy below is through, the plane is all zeros
+    }
+    if (p->n > 0) ALP_HIP(hipMemcpyAsync(p->w, stored.data(), (size_t)p->n * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
+    ALP_HIP(hipStreamSynchronize(ctx().stream));      // `stored` must outlive its copy
+    p->w_sum = sum;
+    return ALP_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 // xyz: n x 3 row-major (cols == NULL), or cols[0..2]: the three columns as they lie
@@ -761,7 +832,7 @@ int alp_points_destroy(alp_points_t *p) {
     if (p->sums_host) hipHostFree(p->sums_host);
     if (p->conf_dev) hipFree(p->conf_dev);
     if (p->conf_host) hipHostFree(p->conf_host);
-    for (void *q : {p->mend_cnt, p->mend_dev, (void *)p->mend_params})
+    for (void *q : {p->mend_cnt, p->mend_dev, (void *)p->mend_params, p->w})
         if (q) hipFree(q);
     for (auto &e : p->ev)
         if (e) hipEventDestroy(e);
@@ -804,6 +875,33 @@ int alp_points_set_observed(alp_points_t *p, const void *uv, int in_dtype) { ret
 int alp_points_set_observed_columns(alp_points_t *p, const void *u, const void *v, int in_dtype) {
     const void *const cols[2] = {u, v};
     return set_observed(p, nullptr, cols, in_dtype);
+}
+
+int alp_points_set_weights(alp_points_t *p, const void *w, int in_dtype) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p, "points handle is NULL");
+    if (p->pending_P > 0 || p->loop_pending)
+        return fail(ALP_ESTATE, "alp_points_set_weights: an evaluation or a device loop on this point set has not been waited for");
+    for (alp_lm_t *h : p->lm_loops)
+        if (lm_loop_pending(h))
+            return fail(ALP_ESTATE, "alp_points_set_weights: a least-squares device loop on this point set has not been waited for");
+    if (!w) {
+        if (p->w) {
+            ALP_HIP(hipStreamSynchronize(ctx().stream));
+            hipFree(p->w);
+        }
+        p->w = nullptr;
+        p->w_sum = 0;
+        return ALP_OK;
+    }
+    ALP_REQUIRE(in_dtype == ALP_F32 || in_dtype == ALP_F64, "in_dtype must be ALP_F32 or ALP_F64");
+    return p->precision == ALP_F64 ? set_weights_t<double>(p, w, in_dtype) : set_weights_t<float>(p, w, in_dtype);
+}
+
+int alp_points_weight_sum(const alp_points_t *p, double *W) {
+    ALP_REQUIRE(p && W, "NULL argument");
+    *W = p->count_slot();
+    return ALP_OK;
 }
 
 int alp_project(alp_points_t *p, const double params[ALP_NPARAM]) {

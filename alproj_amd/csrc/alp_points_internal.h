@@ -23,6 +23,11 @@ struct alp_points {
     void *uo = nullptr, *vo = nullptr;
     void *u = nullptr, *v = nullptr;
     bool projected = false;
+    // per-point frequency weights (alp_points_set_weights): one more plane of the set's element type, NULL = none set.  w_sum:
+    // the float64 sum of the stored (rounded) weights in index order -- what the count slot of every reduction carries then
+    void *w = nullptr;
+    double w_sum = 0;
+    double count_slot() const { return w ? w_sum : (double)n; }
     // population-evaluation scratch
     int64_t cand_cap = 0;
     void *cand_dev = nullptr;
@@ -79,6 +84,8 @@ int points_pop_reserve(alp_points *p, int64_t P);
 // alp_points_destroy: a device loop built on the set loses it (its later calls return ALP_ESTATE)
 void cma_points_gone(alp_cma_t *h);
 void lm_points_gone(alp_lm_t *h);
+// rounds of a least-squares device loop are enqueued and not yet waited for (they read the set's planes, the weights included)
+bool lm_loop_pending(const alp_lm_t *h);
 
 // One evaluation of the least-squares device loop (alp_lm.hip): the normal equations of the starts in `list` (*count of them, in
 // ascending order; running[k] != 0 for exactly those) under plans[k], over the fixed grid `g` = host::normal_batch_grid(n, K, cus):

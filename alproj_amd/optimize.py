@@ -321,13 +321,26 @@ def bounds_to_array(params_init, target_params, bound_widths=None):
     return np.column_stack([centre - half, centre + half]).reshape(len(target_params), 2)
 
 
-class BaseOptimizer:
-    """Holds GCP object/image points and the initial parameters (reference optimize.py:279-319)."""
+def _scale_rows(a, sw):
+    """a * sw where sw > 0, exact zeros elsewhere (a NaN or infinite row of a point of weight 0 stays out)"""
+    with np.errstate(invalid="ignore"):
+        return np.where(sw > 0, a * sw, 0.0)
 
-    def __init__(self, obj_points, img_points, params_init):
+
+class BaseOptimizer:
+    """Holds GCP object/image points and the initial parameters (reference optimize.py:279-319).
+
+    ``weights`` (not in the reference): one frequency weight per point, finite and >= 0, array-like of length N -- this rank's
+    shard, like the points.  With integer weights every optimiser below solves the problem in which point i appears w_i
+    times (a weight of 0 takes the point out without another upload), and the error returned is the weighted mean distance
+    sum w_i d_i / sum w_i.  ValueError, before the GPU is touched, for another length, a negative or non-finite weight, or --
+    without a communicator -- weights that are all 0."""
+
+    def __init__(self, obj_points, img_points, params_init, weights=None):
         self.obj_points = obj_points
         self.img_points = img_points
         self.params_init = params_init
+        self.weights = None if weights is None else _lib.weights_check(weights, len(obj_points)).astype(np.float64)
 
     def set_target(self, target_params=["fov", "pan", "tilt", "roll", "a1", "a2", "k1", "k2", "k3",
                                         "k4", "k5", "k6", "p1", "p2", "s1", "s2", "s3", "s4"]):
@@ -340,7 +353,14 @@ class BaseOptimizer:
         xyz = _xyz_array(self.obj_points)
         pts = _points(xyz, _camera_origin(self.params_init), default_precision(_rows(xyz), precision))
         _set_observed(pts, _uv_array(self.img_points))
+        if self.weights is not None:
+            pts.set_weights(self.weights)
         return pts
+
+    def _row_scale(self):
+        """sqrt(w_i) for both residual rows of point i (2N,), or None without weights: what trf / dogbox / lm multiply the
+        residual vector and the rows of the Jacobian by (a weight of 0 SELECTS 0: a non-finite row of an absent point stays out)"""
+        return None if self.weights is None else np.repeat(np.sqrt(self.weights), 2)
 
     def _candidate_matrix(self, values):
         """(P, D) target values -> (P, 25) ABI parameter vectors (non-target keys from
@@ -683,9 +703,12 @@ class LsqOptimizer(BaseOptimizer):
     def _residual_function(self):
         pts = self._device_points("f64")
         _, world = _lib.comm_info()
+        sw = self._row_scale()
 
         def _residuals(values):
             r = pts.residuals(self._candidate_matrix(values)[0])
+            if sw is not None:
+                r = _scale_rows(r, sw)
             return _lib.comm_allgather(r) if world > 1 else r
 
         _residuals.points = pts
@@ -699,6 +722,7 @@ class LsqOptimizer(BaseOptimizer):
         _, world = _lib.comm_info()
         lb = np.full(len(self.target_params), -np.inf) if bounds is None else np.asarray(bounds[0], dtype=np.float64)
         ub = np.full(len(self.target_params), np.inf) if bounds is None else np.asarray(bounds[1], dtype=np.float64)
+        sw = self._row_scale()
 
         def _jac(values, *args, **kw):
             x0 = np.asarray(values, dtype=np.float64)
@@ -716,6 +740,8 @@ class LsqOptimizer(BaseOptimizer):
             dx = trial[np.arange(1, d + 1), np.arange(d)] - x0          # the representable step
             res = pts.residuals_batch(self._candidate_matrix(trial))
             jac = ((res[1:] - res[0]) / dx[:, None]).T               # (2 n_local, D): this rank's rows
+            if sw is not None:
+                jac = _scale_rows(jac, sw[:, None])
             return _lib.comm_allgather(np.ascontiguousarray(jac)) if world > 1 else jac
 
         return _jac
@@ -724,9 +750,12 @@ class LsqOptimizer(BaseOptimizer):
         """The exact Jacobian of the residual vector at ``values`` (alp_jacobian): one launch, no step, nothing to do at a
         bound.  With several ranks the rows are all-gathered in rank order as in the batched path."""
         _, world = _lib.comm_info()
+        sw = self._row_scale()
 
         def _jac(values, *args, **kw):
             jac = pts.jacobian(self._candidate_matrix(values)[0], cols, of_residuals=True)
+            if sw is not None:
+                jac = _scale_rows(jac, sw[:, None])
             return _lib.comm_allgather(jac) if world > 1 else jac
 
         return _jac
@@ -881,7 +910,11 @@ class LsqOptimizer(BaseOptimizer):
         the host lockstep shrinks its batch as starts stop, which changes the stripes of the sums above 256 points, while
         the device loop keeps K's.  What is held instead: the state machine to ``_normal_lm_steps`` on shared sums, the sums
         to ``alp_normal_equations_batch``, the end result to the cost and the optimum.  At most 23 targets, not w / h;
-        ``device_loop`` with another method and a ``check_every`` that is no positive integer are refused."""
+        ``device_loop`` with another method and a ``check_every`` that is no positive integer are refused.
+
+        ``weights=`` of the constructor: ``method="normal"`` weights on the device, for all four losses (both rows of point i
+        count w_i times); trf, dogbox and lm get residuals and Jacobian rows scaled by sqrt(w_i) on the host (0 where w_i = 0),
+        which is that problem for ``loss="linear"``; a robust loss with weights is refused there."""
         if method == "normal":
             return self._optimize_normal(bound_widths, loss, f_scale, **kwargs)
         if kwargs.get("device_loop"):
@@ -896,6 +929,10 @@ class LsqOptimizer(BaseOptimizer):
             raise ValueError("method='lm' does not support bounds. Set bound_widths=None or use 'trf'/'dogbox'.")
         if method == "lm" and loss != "linear":
             raise ValueError("method='lm' does not support robust loss functions. Use loss='linear' or method='trf'/'dogbox'.")
+        if self.weights is not None and loss != "linear":
+            # scipy applies rho to the scaled residual, rho(w r^2): another problem than w rho(r^2), the duplicated rows'
+            raise ValueError("weights with a robust loss need method='normal' (it weights rho itself); "
+                             f"method='{method}' scales the residuals by sqrt(w), which is the weighted problem for loss='linear' alone")
 
         residual_func = self._residual_function()
         pts = residual_func.points

@@ -324,6 +324,28 @@ int alp_points_set_mend(alp_points_t *pts, int enable);
  * ALP_ESTATE before any evaluation and while one is pending. */
 int alp_eval_population_mended(alp_points_t *pts, int64_t info[4]);
 
+/* Per-point frequency weights.  w: n host values of in_dtype (ALP_F32 or ALP_F64), finite and >= 0, one per point; NULL clears
+ * them.  They are stored in the set's element type -- a float32 set ROUNDS them to float32 -- as one more plane (4 B/point in
+ * float32, 8 B/point in float64) that the population kernels and the normal-equation kernels read beside the observed pixels.
+ * With W = sum w_i over all ranks:
+ *   alp_eval_population*, the CMA-ES device loop: mean distance = sum w_i d_i / W, Huber = sum w_i huber(d_i) / W -- for
+ *     integer weights the losses of the set in which point i appears w_i times.  The float64 confirmation of near-tied float32
+ *     losses and the mend pass use the same weights.
+ *   alp_normal_equations*, the least-squares device loop: both residual rows of point i count w_i times (row scalings times
+ *     sqrt(w_i), cost += w_i rho): J^T J, J^T r and the cost of that set, for all four losses.
+ *   The count slot of every one of these results (the last value of alp_normal_equations' `out`, of each row of the batch)
+ *     carries W instead of n.
+ * A point of weight 0 is ABSENT: its term is selected away even when its distance is NaN or infinite (a vertex at the camera or
+ * on the camera plane does not poison the sums).  A positive weight keeps the NaN / inf behaviour of an unweighted point.  Unit
+ * weights give the bits of the set without weights.  alp_project, alp_residuals*, alp_jacobian and alp_loss_uv* ignore the
+ * weights, and a set without weights runs exactly the kernels it ran before this call existed.
+ * ALP_EINVAL for a negative, NaN or infinite weight (checked on the host before anything is uploaded: the previous weights
+ * stay in force); ALP_ESTATE while an evaluation is enqueued or a device loop on the set is pending.  With a communicator
+ * every rank sets the weights of its own shard; a shard whose weights are all 0 is fine as long as W > 0. */
+int alp_points_set_weights(alp_points_t *pts, const void *w, int in_dtype);
+/* *W = the float64 sum of this rank's stored (rounded) weights, added in index order; n when no weights are set. */
+int alp_points_weight_sum(const alp_points_t *pts, double *W);
+
 /* The candidate sampler of the CMA-ES loop on the device: replaces the `population_size` calls of
  * `optimizer.ask()` per generation, src/alproj/optimize.py:420-421 (third-party cmaes==0.12.0,
  * requirements.txt:14; bounds handling documented at optimize.py:381-384).  Candidate c of generation g:

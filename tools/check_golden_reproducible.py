@@ -39,6 +39,7 @@ GENERATORS = [
     ("gen_golden_geotiff_float.py", ["g17_geotiff_float"]),
     ("gen_golden_geotiff_bytes.py", ["g18_geotiff_bytes"]),
     ("gen_golden_first_phase.py", ["g19_first_phase"]),
+    ("gen_golden_weighted.py", ["g20_weighted"]),
 ]
 
 

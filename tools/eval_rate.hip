@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void k(float *out, const float *rec, int iters
     float acc = 0;
     unsigned long long t0 = __builtin_amdgcn_s_memtime(), w0 = __builtin_amdgcn_s_memrealtime();
     for (int it = 0; it < iters; ++it) {
-        acc += group_loss_sum<float, ALP_LOSS_HUBER, V, false, false>(r, qx, qy, qz, none, uo, vo, ok, 10.0f);
+        acc += group_loss_sum<float, ALP_LOSS_HUBER, V, false, false>(r, qx, qy, qz, none, uo, vo, ok, 10.0f, uo);      // (the last argument: the weights, never read without WEIGHTED)
 #pragma unroll
         for (int j = 0; j < V; ++j) qy[j] += 0.001f;
     }

@@ -20,9 +20,9 @@ subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++
                 "--cuda-device-only", "-S", f"{ROOT}/alproj_amd/csrc/alp_points.hip", "-o", asm] + DEFS, check=True,
                stderr=subprocess.DEVNULL)
 lines = open(asm).read().split("\n")
-sym = r"^_ZN3alp14popeval_kernelIdLi1ENS_6PopCfgIdEELb0EdLb0EE.*:" if F64 else r"^_ZN3alp14popeval_kernelIfLi1ENS_6PopCfgIfEELb0EfLb0EE.*:"
+sym = r"^_ZN3alp14popeval_kernelIdLi1ENS_6PopCfgIdEELb0EdLb0ELb0EE.*:" if F64 else r"^_ZN3alp14popeval_kernelIfLi1ENS_6PopCfgIfEELb0EfLb0ELb0EE.*:"
 if LF:
-    sym = r"^_ZN3alp14popeval_kernelIdLi1ENS_8PopCfgLFIdEELb0EdLb1EE.*:" if F64 else r"^_ZN3alp14popeval_kernelIfLi1ENS_8PopCfgLFIfEELb0EfLb1EE.*:"
+    sym = r"^_ZN3alp14popeval_kernelIdLi1ENS_8PopCfgLFIdEELb0EdLb1ELb0EE.*:" if F64 else r"^_ZN3alp14popeval_kernelIfLi1ENS_8PopCfgLFIfEELb0EfLb1ELb0EE.*:"
 start = next(i for i, l in enumerate(lines) if re.match(sym, l))
 end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
 body = lines[start:end]

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void popeval_lc_kernel(const float *__restrict
             }
 #pragma unroll
             for (int k = 0; k < CPL; ++k)
-                acc[k] += group_loss_sum<float, LOSS, V, false, false>(r[k], qx, qy, qz, none, uoc, voc, ok, f_scale);
+                acc[k] += group_loss_sum<float, LOSS, V, false, false>(r[k], qx, qy, qz, none, uoc, voc, ok, f_scale, uoc);      // (the last argument: the weights, never read without WEIGHTED)
         }
 #pragma unroll
         for (int k = 0; k < CPL; ++k) acc64[k] += (double)acc[k];
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void popeval_lc_kernel(const float *__restrict
             const bool ok[1] = {true};
 #pragma unroll
             for (int k = 0; k < CPL; ++k)
-                acc[k] += group_loss_sum<float, LOSS, 1, false, false>(r[k], qx, qy, qz, none1, uoc, voc, ok, f_scale);
+                acc[k] += group_loss_sum<float, LOSS, 1, false, false>(r[k], qx, qy, qz, none1, uoc, voc, ok, f_scale, uoc);      // (the last argument: the weights, never read without WEIGHTED)
         }
 #pragma unroll
         for (int k = 0; k < CPL; ++k) acc64[k] += (double)acc[k];
