@@ -98,7 +98,7 @@ def build_host(kind="plain", compiler="clang", force=False):
         raise RuntimeError(f"no {compiler} C++ compiler found")
     os.makedirs(HOST_SAN, exist_ok=True)
     srcs = [os.path.join(HOST_DIR, f) for f in ("alp_host.cpp", "alp_host_selfcheck.cpp")]
-    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("alp_host.h", "alp_fold.h", "alp_plan.h", "alp_jacplan.h", "alp_lm.h")] + [os.path.join(INCLUDE, "alproj_hip.h"), os.path.abspath(__file__)]
+    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("alp_host.h", "alp_fold.h", "alp_plan.h", "alp_jacplan.h", "alp_lm.h", "alp_buffer.h")] + [os.path.join(INCLUDE, "alproj_hip.h"), os.path.abspath(__file__)]
     exe = os.path.join(HOST_SAN, f"alp_host_{kind}_{compiler}")
     if force or _stale(exe, deps):
         cmd = [cxx, "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", f"-I{INCLUDE}", f"-I{CSRC}"] + \

@@ -435,7 +435,7 @@ struct alp_cma {
     ExpandArgs ex{};
     std::vector<uint64_t> seeds;  // K: start k's sampler seed
     bool lens_free = false, shared_pose = false;
-    void *dev = nullptr;          // one allocation: K states, weights, X, candidates, losses, order, y_k, w_io, told losses
+    DeviceBuffer<> dev;           // one allocation: K states, weights, X, candidates, losses, order, y_k, w_io, told losses
     CmaState *st = nullptr;
     double *w = nullptr, *X = nullptr, *cand = nullptr, *loss = nullptr, *ys = nullptr, *wio = nullptr, *vals = nullptr;
     int *order = nullptr;
@@ -563,8 +563,7 @@ int alp_cma_create_starts(alp_points_t *pts, const double tmpl[ALP_NPARAM], cons
     const int64_t R = (int64_t)K * P;
     const size_t sz_state = round_up((int64_t)K * sizeof(CmaState), 256), sz_w = round_up(P * 8, 256), sz_p = round_up(R * 8, 256),
                  sz_pd = round_up(R * D * 8, 256), sz_cand = round_up(R * ALP_NPARAM * 8, 256), sz_ord = round_up(R * 4, 256);
-    int rc = ALP_OK;
-    if (hipMalloc(&h->dev, sz_state + sz_w + 3 * sz_p + 2 * sz_pd + sz_cand + sz_ord) != hipSuccess) rc = fail(ALP_EHIP, "alp_cma_create: hipMalloc failed");
+    int rc = h->dev.reserve(sz_state + sz_w + 3 * sz_p + 2 * sz_pd + sz_cand + sz_ord);
     if (!rc) {
         char *q = (char *)h->dev;
         h->st = (CmaState *)q; q += sz_state;
@@ -587,7 +586,6 @@ int alp_cma_create_starts(alp_points_t *pts, const double tmpl[ALP_NPARAM], cons
         rc = upload_states(h, 0, K, s.data());
     }
     if (rc) {
-        if (h->dev) hipFree(h->dev);
         delete h;
         return rc;
     }
@@ -614,7 +612,6 @@ int alp_cma_destroy(alp_cma_t *h) {
                 break;
             }
     }
-    if (h->dev) hipFree(h->dev);
     delete h;
     return ALP_OK;
 }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "host/alp_host.h"      // errors (set_error / fail / ALP_REQUIRE), pose record + fold_pose, RowDiv + launch planning, the HIP-free host helpers
+#include "host/alp_buffer.h"    // Buffer, reserve_all: how a handle owns memory
 
 namespace alp {
 
@@ -15,6 +16,48 @@ namespace alp {
             return ::alp::fail(ALP_EHIP, "%s failed: %s (%s:%d)", #expr,                  \
                                hipGetErrorString(e__), __FILE__, __LINE__);               \
     } while (0)
+
+// ------------------------------------------------------------------ ownership
+// A handle owns its device and pinned memory through these (host/alp_buffer.h) and its events through Event: `delete handle`
+// releases all of it, no list to keep.  Buffers that must be there together are reserved with reserve_all (all or none), and a
+// capacity that arithmetic or a kernel reads (cand_cap, qcap, park_cap[], the frame's w / h) is set to 0 before its group is
+// released and to its new value after the group is there.  What lives as long as the process (Context::scratch, the fetch
+// staging, the kernel-section timer) stays with plain pointers released in alp_shutdown: no static object may call HIP at exit.
+struct DeviceMemory {
+    static int alloc(void **p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        return e == hipSuccess ? ALP_OK : fail(ALP_EHIP, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    }
+    static void release(void *p) { hipFree(p); }
+};
+struct PinnedMemory {
+    static int alloc(void **p, size_t bytes) {
+        const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+        return e == hipSuccess ? ALP_OK : fail(ALP_EHIP, "hipHostMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    }
+    static void release(void *p) { hipHostFree(p); }
+};
+template <typename T = void> using DeviceBuffer = Buffer<DeviceMemory, T>;
+template <typename T = void> using PinnedBuffer = Buffer<PinnedMemory, T>;
+
+// a HIP event created on demand and destroyed with its owner
+struct Event {
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept {
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event() {
+        if (e) hipEventDestroy(e);
+    }
+    int ensure() {
+        if (!e && hipEventCreate(&e) != hipSuccess) return fail(ALP_EHIP, "hipEventCreate failed");
+        return ALP_OK;
+    }
+    operator hipEvent_t() const { return e; }
+    hipEvent_t e = nullptr;
+};
 
 // ------------------------------------------------------------------ global context
 struct Context {

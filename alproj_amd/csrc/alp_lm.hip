@@ -109,7 +109,7 @@ struct alp_lm {
     int loss = 0;
     double f_scale = 1.0;
     host::NormalGrid grid{0, 0};  // host::normal_batch_grid(n, K, cus): fixed for the life of the handle
-    void *dev = nullptr;          // one allocation: states, plans, sums, partials, list, running, count
+    DeviceBuffer<> dev;           // one allocation: states, plans, sums, partials, list, running, count
     LmState *st = nullptr;
     JacPlan *plans = nullptr;
     double *sums = nullptr, *partials = nullptr;
@@ -185,8 +185,7 @@ int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_
     const size_t sz_state = round_up((int64_t)K * sizeof(LmState), 256), sz_plan = round_up((int64_t)K * sizeof(JacPlan), 256),
                  sz_sums = round_up((int64_t)K * (T + 1) * 8, 256), sz_part = round_up((int64_t)K * h->grid.blocks * T * 8 + 8, 256),
                  sz_int = round_up((int64_t)K * 4, 256);
-    int rc = ALP_OK;
-    if (hipMalloc(&h->dev, sz_state + sz_plan + sz_sums + sz_part + 2 * sz_int + 256) != hipSuccess) rc = fail(ALP_EHIP, "alp_lm_create: hipMalloc failed");
+    int rc = h->dev.reserve(sz_state + sz_plan + sz_sums + sz_part + 2 * sz_int + 256);
     if (!rc) {
         char *q = (char *)h->dev;
         h->st = (LmState *)q; q += sz_state;
@@ -206,7 +205,6 @@ int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_
         if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(ALP_EHIP, "alp_lm_create: the first step failed");      // s (host) must outlive its copy
     }
     if (rc) {
-        if (h->dev) hipFree(h->dev);
         delete h;
         return rc;
     }
@@ -226,7 +224,6 @@ int alp_lm_destroy(alp_lm_t *h) {
                 break;
             }
     }
-    if (h->dev) hipFree(h->dev);
     delete h;
     return ALP_OK;
 }

@@ -110,21 +110,17 @@ int alp_mesh_set_value(alp_mesh_t *m, const void *value, int value_dtype) {
     if (int rc = require_init()) return rc;
     ALP_REQUIRE(m, "mesh handle is NULL");
     if (!value) {
-        if (m->value) {
-            ALP_HIP(hipStreamSynchronize(ctx().stream));      // a resolve that reads it may be in flight
-            hipFree(m->value);
-        }
-        m->value = nullptr;
+        if (m->value) ALP_HIP(hipStreamSynchronize(ctx().stream));      // a resolve that reads it may be in flight
+        m->value.reset();
         return ALP_OK;
     }
     ALP_REQUIRE(value_dtype == ALP_F32 || value_dtype == ALP_F64, "value_dtype must be ALP_F32 or ALP_F64");
     const bool fresh = !m->value;
-    if (fresh) ALP_HIP(hipMalloc((void **)&m->value, (size_t)m->n_vert * 12));
+    if (int rc = m->value.reserve((size_t)m->n_vert * 12)) return rc;
     const int rc = upload_f32(m->value, value, value_dtype, m->n_vert);    // stream-ordered behind any resolve in flight
     if (rc && fresh) {               // never leave an allocated, unwritten value buffer behind: it would render as colours
         hipStreamSynchronize(ctx().stream);
-        hipFree(m->value);
-        m->value = nullptr;
+        m->value.reset();
     }
     return rc;
 }
@@ -142,11 +138,10 @@ int alp_mesh_set_valid(alp_mesh_t *m, const uint8_t *valid) {
     m->vis_current = false;
     if (m->valid_derived) return apply_derived_mask(m, valid);   // filtered grid: its own mask stays in force
     if (!valid) {
-        if (m->valid) hipFree(m->valid);
-        m->valid = nullptr;
+        m->valid.reset();
         return ALP_OK;
     }
-    if (!m->valid) ALP_HIP(hipMalloc((void **)&m->valid, (size_t)m->n_vert));
+    if (int rc = m->valid.reserve((size_t)m->n_vert)) return rc;
     return upload_chunked(m->valid, valid, (size_t)m->n_vert);
 }
 
@@ -171,22 +166,19 @@ int alp_mesh_from_rasters(const void *dsm, int dsm_dtype, int64_t rows, int64_t 
     m->n_tri = 2 * (rows - 1) * (cols - 1);
     m->implicit = true;
     int rc = ALP_OK;
-    void *dsm_dev = nullptr, *aer_dev = nullptr;
-    unsigned char *nod_dev = nullptr;
-    unsigned long long *zmin_dev = nullptr;
+    DeviceBuffer<> dsm_dev, aer_dev;         // the rasters as uploaded: gone once the vertices are built
+    DeviceBuffer<unsigned char> nod_dev;
+    DeviceBuffer<unsigned long long> zmin_dev;
     auto bail = [&](int code) {
-        for (void *p : {dsm_dev, aer_dev, (void *)nod_dev, (void *)zmin_dev})
-            if (p) hipFree(p);
         alp_mesh_destroy(m);
         return code;
     };
     const size_t zsize = dsm_dtype == ALP_F32 ? 4 : 8;
     const size_t asize = aerial_dtype == ALP_U8 ? 1 : aerial_dtype == ALP_U16 ? 2 : 4;
-    if (hipMalloc(&dsm_dev, (size_t)n * zsize) != hipSuccess || hipMalloc(&aer_dev, (size_t)n * 3 * asize) != hipSuccess ||
-        hipMalloc((void **)&zmin_dev, 8) != hipSuccess || hipMalloc((void **)&m->vert, (size_t)n * 12) != hipSuccess ||
-        hipMalloc((void **)&m->value, (size_t)n * 12) != hipSuccess || hipMalloc((void **)&m->valid, (size_t)n) != hipSuccess ||
-        (nodata && hipMalloc((void **)&nod_dev, (size_t)n) != hipSuccess))
-        return bail(fail(ALP_EHIP, "alp_mesh_from_rasters: hipMalloc"));
+    if ((rc = reserve_all({(size_t)n * zsize, (size_t)n * 3 * asize, 8, (size_t)n * 12, (size_t)n * 12, (size_t)n},
+                          dsm_dev, aer_dev, zmin_dev, m->vert, m->value, m->valid)))
+        return bail(rc);
+    if (nodata && (rc = nod_dev.reserve((size_t)n))) return bail(rc);
     if ((rc = upload_chunked(dsm_dev, dsm, (size_t)n * zsize))) return bail(rc);
     if ((rc = upload_chunked(aer_dev, aerial, (size_t)n * 3 * asize))) return bail(rc);
     if (nodata && (rc = upload_chunked(nod_dev, nodata, (size_t)n))) return bail(rc);
@@ -239,18 +231,10 @@ int alp_mesh_from_rasters(const void *dsm, int dsm_dtype, int64_t rows, int64_t 
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return bail(fail(ALP_EHIP, "alp_mesh_from_rasters: %s", hipGetErrorString(e)));
-    if (!nodata) {                           // nothing masked: plain grid
-        hipFree(m->valid);
-        m->valid = nullptr;
-    }
-    for (void *p : {dsm_dev, aer_dev, (void *)nod_dev, (void *)zmin_dev})
-        if (p) hipFree(p);
-    dsm_dev = aer_dev = nullptr;
-    nod_dev = nullptr;
-    zmin_dev = nullptr;
-    if (hipMalloc((void **)&m->qcount_dev, QC_TOTAL * sizeof(unsigned)) != hipSuccess ||
-        hipHostMalloc((void **)&m->qcount_host, QC_TOTAL * sizeof(unsigned), hipHostMallocDefault) != hipSuccess)
-        return bail(fail(ALP_EHIP, "hipMalloc queue counter"));
+    if (!nodata) m->valid.reset();           // nothing masked: plain grid
+    reset_all(dsm_dev, aer_dev, nod_dev, zmin_dev);
+    const size_t counters = QC_TOTAL * sizeof(unsigned);
+    if ((rc = reserve_all({counters, counters}, m->qcount_dev, m->qcount_host))) return bail(rc);
     if ((rc = ensure_queue(m, initial_queue_cap()))) return bail(rc);
     if ((rc = ensure_gqueue(m, initial_queue_cap()))) return bail(rc);
     offsets_out[0] = ox;                     // X, Z, Y like `vert` (surface.py:189)

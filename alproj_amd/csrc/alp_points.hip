@@ -38,10 +38,10 @@ using alp::host::CONFIRM_MAX;
 namespace {
 
 // k planes of n_pad elements in ONE zeroed allocation (n_pad is a multiple of 1024 elements: every plane starts 4 KB-aligned)
-int alloc_planes(void **slab, int k, int64_t n_pad, size_t es, void **planes[]) {
-    ALP_HIP(hipMalloc(slab, (size_t)k * n_pad * es));
-    ALP_HIP(hipMemsetAsync(*slab, 0, (size_t)k * n_pad * es, ctx().stream));
-    for (int i = 0; i < k; ++i) *planes[i] = (char *)*slab + (size_t)i * n_pad * es;
+int alloc_planes(DeviceBuffer<> &slab, int k, int64_t n_pad, size_t es, void **planes[]) {
+    if (int rc = slab.reserve((size_t)k * n_pad * es)) return rc;
+    ALP_HIP(hipMemsetAsync(slab, 0, (size_t)k * n_pad * es, ctx().stream));
+    for (int i = 0; i < k; ++i) *planes[i] = (char *)slab + (size_t)i * n_pad * es;
     return ALP_OK;
 }
 
@@ -61,8 +61,8 @@ __global__ __launch_bounds__(256) void column_to_plane_kernel(const TIn *__restr
 template <typename TIn, typename Launch>
 int staged_upload(const void *const *srcs, int nsrc, int64_t n, int width, int64_t CH, Launch launch) {
     const int64_t ch = n < CH ? (n > 0 ? n : 1) : CH;
-    TIn *stage = nullptr;
-    ALP_HIP(hipMalloc((void **)&stage, (size_t)ch * width * sizeof(TIn)));
+    DeviceBuffer<TIn> stage;
+    if (int rc = stage.reserve((size_t)ch * width * sizeof(TIn))) return rc;
     int rc = ALP_OK;
     for (int c = 0; c < nsrc && !rc; ++c)
         for (int64_t off = 0; off < n; off += ch) {
@@ -75,8 +75,7 @@ int staged_upload(const void *const *srcs, int nsrc, int64_t n, int width, int64
             if (e != hipSuccess) { rc = fail(ALP_EHIP, "upload kernel: %s", hipGetErrorString(e)); break; }
         }
     if (hipStreamSynchronize(ctx().stream) != hipSuccess && !rc) rc = fail(ALP_EHIP, "upload: stream failed");
-    hipFree(stage);
-    return rc;
+    return rc;          // (`stage` is released here, behind the synchronisation)
 }
 
 // C planes from the C columns cols[] as they lie, or (cols == NULL) from `rows`, n x C row-major; o[0..3) = the origin
@@ -196,43 +195,24 @@ int launch_project(alp_points *p, const double params[ALP_NPARAM]) {
 int ensure_pop_scratch(alp_points *p, int64_t P, int nblk) {
     if (P > p->cand_cap) {
         const int64_t cap = round_up(P, 256);
-        if (p->cand_dev) hipFree(p->cand_dev);
-        if (p->cand_host) hipHostFree(p->cand_host);
-        if (p->sums_dev) hipFree(p->sums_dev);
-        if (p->sums_host) hipHostFree(p->sums_host);
-        p->cand_dev = p->cand_host = nullptr;
-        p->sums_dev = p->sums_host = nullptr;
         p->cand_cap = 0;
-        const size_t rec = POSE_WORDS * p->esize();
+        reset_all(p->cand_dev, p->cand_host, p->sums_dev, p->sums_host);
         // two records per candidate: the general one and, behind all of those, the lens-free one (enqueue_popeval)
-        ALP_HIP(hipMalloc(&p->cand_dev, (size_t)cap * rec * 2));
-        ALP_HIP(hipHostMalloc(&p->cand_host, (size_t)cap * rec * 2, hipHostMallocDefault));
-        ALP_HIP(hipMalloc((void **)&p->sums_dev, (size_t)(cap + 1) * sizeof(double)));
-        ALP_HIP(hipHostMalloc((void **)&p->sums_host, (size_t)(cap + 1) * sizeof(double), hipHostMallocDefault));
+        const size_t recs = (size_t)cap * POSE_WORDS * p->esize() * 2, sums = (size_t)(cap + 1) * sizeof(double);
+        if (int rc = reserve_all({recs, recs, sums, sums}, p->cand_dev, p->cand_host, p->sums_dev, p->sums_host)) return rc;
         p->cand_cap = cap;
     }
-    const int64_t need = (int64_t)nblk * P;
-    if (need > p->partials_cap) {
-        if (p->partials) hipFree(p->partials);
-        p->partials = nullptr;
-        p->partials_cap = 0;
-        ALP_HIP(hipMalloc((void **)&p->partials, (size_t)need * sizeof(double)));
-        p->partials_cap = need;
-    }
-    return ALP_OK;
+    const size_t need = (size_t)nblk * P * sizeof(double);
+    return need ? p->partials.reserve(need) : ALP_OK;
 }
 
 // the four timing events of a handle, all or none: a partial failure must not leave ev[1] .. ev[3] NULL for good
 int ensure_pop_events(alp_points *p) {
     if (p->ev[0]) return ALP_OK;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev[4];
     for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            for (auto &d : ev)
-                if (d) hipEventDestroy(d);
-            return fail(ALP_EHIP, "hipEventCreate failed");
-        }
-    for (int k = 0; k < 4; ++k) p->ev[k] = ev[k];
+        if (int rc = e.ensure()) return rc;
+    for (int k = 0; k < 4; ++k) p->ev[k] = std::move(ev[k]);
     return ALP_OK;
 }
 
@@ -244,15 +224,13 @@ PoseRec<double> *mend_recs(const alp_points *p) { return (PoseRec<double> *)(men
 
 int ensure_mend_scratch(alp_points *p) {
     if (!p->mend_cnt) {
-        ALP_HIP(hipMalloc(&p->mend_cnt, sizeof(MendCount)));
+        if (int rc = p->mend_cnt.reserve(sizeof(MendCount))) return rc;
         ALP_HIP(hipMemsetAsync(p->mend_cnt, 0, sizeof(MendCount), ctx().stream));
     }
     if (p->mend_cap >= p->cand_cap) return ALP_OK;
-    if (p->mend_dev) hipFree(p->mend_dev);
-    p->mend_dev = nullptr;
     p->mend_cap = 0;
     const int64_t cap = p->cand_cap;          // a multiple of 256
-    ALP_HIP(hipMalloc(&p->mend_dev, (size_t)round_up(cap * 4, 256) + (size_t)cap * (8 + sizeof(PoseRec<double>))));
+    if (int rc = p->mend_dev.reserve((size_t)round_up(cap * 4, 256) + (size_t)cap * (8 + sizeof(PoseRec<double>)))) return rc;
     p->mend_cap = cap;
     return ALP_OK;
 }
@@ -399,13 +377,8 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
     if (sizeof(T) == 4) p->cand_copy.assign(cand, cand + P * ALP_NPARAM);
     const double *params_dev = nullptr;
     if (sizeof(T) == 4 && p->mend) {
-        if (p->mend_params_cap < P) {
-            if (p->mend_params) hipFree(p->mend_params);
-            p->mend_params = nullptr;
-            p->mend_params_cap = 0;
-            ALP_HIP(hipMalloc((void **)&p->mend_params, (size_t)p->cand_cap * ALP_NPARAM * sizeof(double)));
-            p->mend_params_cap = p->cand_cap;
-        }
+        if (p->mend_params.capacity() < (size_t)P * ALP_NPARAM * sizeof(double))
+            if (int rc = p->mend_params.reserve((size_t)p->cand_cap * ALP_NPARAM * sizeof(double))) return rc;
         ALP_HIP(hipMemcpyAsync(p->mend_params, p->cand_copy.data(), (size_t)P * ALP_NPARAM * sizeof(double), hipMemcpyHostToDevice,
                                ctx().stream));
         params_dev = p->mend_params;
@@ -426,13 +399,8 @@ int confirm_losses(alp_points *p, const double *cand, const int64_t *which, int 
                    double *sums_out) {
     const int nblk = host::confirm_grid(p->n, ctx().cu_count);
     const size_t rec_bytes = (size_t)CONFIRM_MAX * sizeof(PoseRec<double>);
-    if (!p->conf_dev || p->conf_nblk < nblk) {
-        if (p->conf_dev) hipFree(p->conf_dev);
-        p->conf_dev = nullptr;
-        ALP_HIP(hipMalloc(&p->conf_dev, rec_bytes + (size_t)(nblk + 2) * CONFIRM_MAX * sizeof(double)));
-        p->conf_nblk = nblk;
-    }
-    if (!p->conf_host) ALP_HIP(hipHostMalloc((void **)&p->conf_host, (CONFIRM_MAX + 1) * sizeof(double), hipHostMallocDefault));
+    if (int rc = p->conf_dev.reserve(rec_bytes + (size_t)(nblk + 2) * CONFIRM_MAX * sizeof(double))) return rc;
+    if (int rc = p->conf_host.reserve((CONFIRM_MAX + 1) * sizeof(double))) return rc;
     PoseRec<double> recs[CONFIRM_MAX];
     for (int k = 0; k < K; ++k) fold_pose_t<double>(cand + which[k] * ALP_NPARAM, p->origin, &recs[k]);
     PoseRec<double> *recs_dev = (PoseRec<double> *)p->conf_dev;
@@ -755,14 +723,11 @@ int set_weights_t(alp_points *p, const void *w, int in_dtype) {
     if (int rc = in_dtype == ALP_F64 ? weights_stored<double, T>(w, p->n, stored, &sum) : weights_stored<float, T>(w, p->n, stored, &sum)) return rc;
     // (nothing of the set has changed so far: a refused call leaves the previous weights in force)
     if (!p->w) {
-        void *plane = nullptr;
-        ALP_HIP(hipMalloc(&plane, (size_t)p->n_pad * sizeof(T)));
+        DeviceBuffer<> plane;
+        if (int rc = plane.reserve((size_t)p->n_pad * sizeof(T))) return rc;
         hipError_t e = hipMemsetAsync(plane, 0, (size_t)p->n_pad * sizeof(T), ctx().stream);
-        if (e != hipSuccess) {
-            hipFree(plane);
-            return fail(ALP_EHIP, "alp_points_set_weights: %s", hipGetErrorString(e));
-        }
-        p->w = plane;
+        if (e != hipSuccess) return fail(ALP_EHIP, "alp_points_set_weights: %s", hipGetErrorString(e));
+        p->w = std::move(plane);
         p->w_sum = 0;           // until the copy below is through, the plane is all zeros
     }
     if (p->n > 0) ALP_HIP(hipMemcpyAsync(p->w, stored.data(), (size_t)p->n * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
@@ -792,7 +757,7 @@ static int points_create(const void *xyz, const void *const *cols, int in_dtype,
     p->precision = precision;
     memcpy(p->origin, origin, sizeof(p->origin));
     void **xyz_planes[3] = {&p->x, &p->y, &p->z};
-    int rc = alloc_planes(&p->slab_xyz, 3, p->n_pad, p->esize(), xyz_planes);
+    int rc = alloc_planes(p->slab_xyz, 3, p->n_pad, p->esize(), xyz_planes);
     if (!rc && n > 0) {
         void *const planes[3] = {p->x, p->y, p->z};
         rc = upload<3>(xyz, cols, in_dtype, n, origin, precision, planes);
@@ -826,16 +791,6 @@ int alp_points_destroy(alp_points_t *p) {
     for (alp_cma_t *h : p->loops) cma_points_gone(h);
     for (alp_lm_t *h : p->lm_loops) lm_points_gone(h);
     if (ctx().ready) hipStreamSynchronize(ctx().stream);
-    for (void *q : {p->slab_xyz, p->slab_obs, p->slab_uv, p->cand_dev, (void *)p->partials, (void *)p->sums_dev})
-        if (q) hipFree(q);
-    if (p->cand_host) hipHostFree(p->cand_host);
-    if (p->sums_host) hipHostFree(p->sums_host);
-    if (p->conf_dev) hipFree(p->conf_dev);
-    if (p->conf_host) hipHostFree(p->conf_host);
-    for (void *q : {p->mend_cnt, p->mend_dev, (void *)p->mend_params, p->w})
-        if (q) hipFree(q);
-    for (auto &e : p->ev)
-        if (e) hipEventDestroy(e);
     delete p;
     return ALP_OK;
 }
@@ -860,7 +815,7 @@ static int set_observed(alp_points_t *p, const void *uv, const void *const *cols
     ALP_REQUIRE(in_dtype == ALP_F32 || in_dtype == ALP_F64, "in_dtype must be ALP_F32 or ALP_F64");
     if (!p->uo) {
         void **obs_planes[2] = {&p->uo, &p->vo};
-        if (int rc = alloc_planes(&p->slab_obs, 2, p->n_pad, p->esize(), obs_planes)) return rc;
+        if (int rc = alloc_planes(p->slab_obs, 2, p->n_pad, p->esize(), obs_planes)) return rc;
     }
     const double zero[3] = {0, 0, 0};
     void *const planes[3] = {p->uo, p->vo, nullptr};
@@ -886,11 +841,8 @@ int alp_points_set_weights(alp_points_t *p, const void *w, int in_dtype) {
         if (lm_loop_pending(h))
             return fail(ALP_ESTATE, "alp_points_set_weights: a least-squares device loop on this point set has not been waited for");
     if (!w) {
-        if (p->w) {
-            ALP_HIP(hipStreamSynchronize(ctx().stream));
-            hipFree(p->w);
-        }
-        p->w = nullptr;
+        if (p->w) ALP_HIP(hipStreamSynchronize(ctx().stream));
+        p->w.reset();
         p->w_sum = 0;
         return ALP_OK;
     }
@@ -909,7 +861,7 @@ int alp_project(alp_points_t *p, const double params[ALP_NPARAM]) {
     ALP_REQUIRE(p && params, "NULL argument");
     if (!p->u) {
         void **uv_planes[2] = {&p->u, &p->v};
-        if (int rc = alloc_planes(&p->slab_uv, 2, p->n_pad, p->esize(), uv_planes)) return rc;
+        if (int rc = alloc_planes(p->slab_uv, 2, p->n_pad, p->esize(), uv_planes)) return rc;
     }
     p->projected = true;
     if (p->n == 0) return ALP_OK;

@@ -18,24 +18,23 @@ struct alp_points {
     // the planes live in at most three allocations (a hipMalloc / hipFree pair of this size costs ~1 ms: seven of them were a
     // third of what compute_residuals spent at 10 M points): coordinates at creation, observed pixels at alp_points_set_observed*,
     // projected pixels at the first alp_project
-    void *slab_xyz = nullptr, *slab_obs = nullptr, *slab_uv = nullptr;
+    alp::DeviceBuffer<> slab_xyz, slab_obs, slab_uv;
     void *x = nullptr, *y = nullptr, *z = nullptr;
     void *uo = nullptr, *vo = nullptr;
     void *u = nullptr, *v = nullptr;
     bool projected = false;
     // per-point frequency weights (alp_points_set_weights): one more plane of the set's element type, NULL = none set.  w_sum:
     // the float64 sum of the stored (rounded) weights in index order -- what the count slot of every reduction carries then
-    void *w = nullptr;
+    alp::DeviceBuffer<> w;
     double w_sum = 0;
     double count_slot() const { return w ? w_sum : (double)n; }
     // population-evaluation scratch
     int64_t cand_cap = 0;
-    void *cand_dev = nullptr;
-    void *cand_host = nullptr;     // pinned
-    double *partials = nullptr;
-    int64_t partials_cap = 0;
-    double *sums_dev = nullptr;    // cand_cap + 1
-    double *sums_host = nullptr;   // pinned, cand_cap + 1
+    alp::DeviceBuffer<> cand_dev;
+    alp::PinnedBuffer<> cand_host;
+    alp::DeviceBuffer<double> partials;
+    alp::DeviceBuffer<double> sums_dev;    // cand_cap + 1
+    alp::PinnedBuffer<double> sums_host;   // cand_cap + 1
     int64_t last_info[3] = {0, 0, 0};     // alp_eval_population_info: variant, stripes, tile columns of the last launch
     int64_t pending_P = 0;
     int pending_loss = 0;
@@ -43,18 +42,16 @@ struct alp_points {
     std::vector<double> cand_copy;   // the P x 25 parameter vectors of the pending call (argmin confirmation)
     // argmin confirmation (float32 sets): float64 records, partial sums and sums of up to CONFIRM_MAX candidates
     // last population evaluation: before the kernels, after them, after the all-reduce, after the mend pass
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    alp::Event ev[4];
     bool timed = false;
-    void *conf_dev = nullptr;
-    int conf_nblk = 0;
-    double *conf_host = nullptr;   // pinned, CONFIRM_MAX + 1
+    alp::DeviceBuffer<> conf_dev;
+    alp::PinnedBuffer<double> conf_host;   // CONFIRM_MAX + 1
     // the mend pass of a float32 set (alp_points_set_mend; alp_points.hip: mend_launch)
     bool mend = false;
-    void *mend_cnt = nullptr;      // MendCount: the last pass's count and the total since mend was enabled
-    void *mend_dev = nullptr;      // mend_cap x (index, mended sum, PoseRec<double>)
+    alp::DeviceBuffer<> mend_cnt;  // MendCount: the last pass's count and the total since mend was enabled
+    alp::DeviceBuffer<> mend_dev;  // mend_cap x (index, mended sum, PoseRec<double>)
     int64_t mend_cap = 0;
-    double *mend_params = nullptr; // the host path's P x 25 parameter rows (the device loop passes its own)
-    int64_t mend_params_cap = 0;
+    alp::DeviceBuffer<double> mend_params;   // the host path's cand_cap x 25 parameter rows (the device loop passes its own)
     bool mend_ran = false;         // the last population evaluation ran the pass
     int64_t mend_info[2] = {0, 0}; // its stripes and tile columns
     // device loops of the CMA-ES generation (alp_cma.hip) built on this set: told when it is destroyed; while one of them has

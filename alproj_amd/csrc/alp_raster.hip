@@ -117,9 +117,8 @@ static hipError_t staged_upload(const void *src, size_t esize, int64_t total, in
 
 int ensure_queue(alp_mesh *m, unsigned cap) {
     if (m->queue && m->qcap >= cap) return ALP_OK;
-    if (m->queue) hipFree(m->queue);
-    m->queue = nullptr;
-    ALP_HIP(hipMalloc((void **)&m->queue, (size_t)cap * sizeof(WorkItem)));
+    m->qcap = 0;
+    if (int rc = m->queue.reserve((size_t)cap * sizeof(WorkItem))) return rc;
     m->qcap = cap;
     return ALP_OK;
 }
@@ -131,14 +130,13 @@ unsigned initial_queue_cap() { return host::initial_queue_cap(getenv("ALP_QUEUE_
 // Queues of parked work: [first round | second round] per kind (small triangles, large triangles, cells), `cap` and `cap_b`
 // entries; the capacities are host::initial_park_caps' at the first grid frame and host::frame_verdict's after an overflow.
 static int alloc_park(alp_mesh *m, const unsigned cap[3], const unsigned cap_b[3]) {
-    if (m->park_small) hipFree(m->park_small);
-    if (m->park_cell) hipFree(m->park_cell);
-    m->park_small = nullptr;
+    for (int k = 0; k < 3; ++k) m->park_cap[k] = m->park_cap_b[k] = 0;
     m->park_large = nullptr;
-    m->park_cell = nullptr;
-    ALP_HIP(hipMalloc((void **)&m->park_small, ((size_t)cap[0] + cap_b[0] + cap[1] + cap_b[1]) * sizeof(Deferred)));
-    ALP_HIP(hipMalloc((void **)&m->park_cell, ((size_t)cap[2] + cap_b[2]) * sizeof(ParkedCell)));
-    m->park_large = (Deferred *)m->park_small + cap[0] + cap_b[0];
+    reset_all(m->park_small, m->park_cell);
+    const size_t triangles = ((size_t)cap[0] + cap_b[0] + cap[1] + cap_b[1]) * sizeof(Deferred);
+    const size_t cells = ((size_t)cap[2] + cap_b[2]) * sizeof(ParkedCell);
+    if (int rc = reserve_all({triangles, cells}, m->park_small, m->park_cell)) return rc;
+    m->park_large = m->park_small + cap[0] + cap_b[0];
     for (int k = 0; k < 3; ++k) {
         m->park_cap[k] = cap[k];
         m->park_cap_b[k] = cap_b[k];
@@ -153,7 +151,7 @@ int apply_derived_mask(alp_mesh *m, const unsigned char *user) {
         if (int rc = scratch_reserve((size_t)m->n_vert, (void **)&user_dev)) return rc;
         if (int rc = upload_chunked(user_dev, user, (size_t)m->n_vert)) return rc;
     }
-    if (!m->valid) ALP_HIP(hipMalloc((void **)&m->valid, (size_t)m->n_vert));
+    if (int rc = m->valid.reserve((size_t)m->n_vert)) return rc;
     hipLaunchKernelGGL(mask_and_kernel, dim3((unsigned)((m->n_vert + 255) / 256)), dim3(256), 0, st, m->valid_derived, user_dev,
                        (long long)m->n_vert, m->valid);
     ALP_HIP(hipGetLastError());
@@ -175,54 +173,50 @@ int try_subgrid(alp_mesh *m, const long long first[3]) {
     if (m->n_tri >= full || m->n_tri * 4 < full) return ALP_OK;
     hipStream_t st = ctx().stream;
     const long long words = (full + 31) / 32, blocks = (words + 255) / 256;
-    unsigned *block_dev = nullptr;
-    auto giveup = [&](int code) {
-        // (m->valid: the mesh is being created, a mask can only be this function's own, half-made one)
-        for (void *p : {(void *)m->valid_derived, (void *)m->tri_present, (void *)m->tri_rank, (void *)block_dev, (void *)m->valid})
-            if (p) hipFree(p);
-        m->valid_derived = m->valid = nullptr;
-        m->tri_present = m->tri_rank = nullptr;
-        return code;
-    };
-    if (hipMalloc((void **)&m->valid_derived, (size_t)m->n_vert) != hipSuccess ||
-        hipMalloc((void **)&m->tri_present, (size_t)words * 4) != hipSuccess ||
-        hipMalloc((void **)&m->tri_rank, (size_t)words * 4) != hipSuccess ||
-        hipMalloc((void **)&block_dev, (size_t)blocks * 4) != hipSuccess)
-        return giveup(fail(ALP_EHIP, "sub-grid check: hipMalloc"));
-    hipError_t e = hipMemsetAsync(m->valid_derived, 0, (size_t)m->n_vert, st);
-    if (e == hipSuccess) e = hipMemsetAsync(m->tri_present, 0, (size_t)words * 4, st);
+    // the mask, the triangle bits and their ranks stay this function's own until every check has passed
+    DeviceBuffer<unsigned char> derived;
+    DeviceBuffer<unsigned> present, rank, block_dev;
+    if (int rc = reserve_all({(size_t)m->n_vert, (size_t)words * 4, (size_t)words * 4, (size_t)blocks * 4},
+                             derived, present, rank, block_dev))
+        return rc;
+    hipError_t e = hipMemsetAsync(derived, 0, (size_t)m->n_vert, st);
+    if (e == hipSuccess) e = hipMemsetAsync(present, 0, (size_t)words * 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(m->qcount_dev, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return giveup(fail(ALP_EHIP, "sub-grid check: memset"));
+    if (e != hipSuccess) return fail(ALP_EHIP, "sub-grid check: memset");
     hipLaunchKernelGGL(subgrid_mark_kernel, dim3(ctx().cu_count * 8), dim3(256), 0, st, m->ind, (long long)m->n_tri, gw, gh,
-                       m->tri_present, m->valid_derived, m->qcount_dev);
-    hipLaunchKernelGGL(subgrid_absent_kernel, dim3(ctx().cu_count * 8), dim3(256), 0, st, full, gw, m->tri_present,
-                       m->valid_derived, m->qcount_dev);
-    hipLaunchKernelGGL(subgrid_blocksum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, m->tri_present, words, block_dev);
+                       present, derived, m->qcount_dev);
+    hipLaunchKernelGGL(subgrid_absent_kernel, dim3(ctx().cu_count * 8), dim3(256), 0, st, full, gw, present,
+                       derived, m->qcount_dev);
+    hipLaunchKernelGGL(subgrid_blocksum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, present, words, block_dev);
     std::vector<unsigned> sums((size_t)blocks);
     e = hipMemcpyAsync(m->qcount_host, m->qcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), block_dev, (size_t)blocks * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return giveup(fail(ALP_EHIP, "sub-grid check: %s", hipGetErrorString(e)));
-    if (*m->qcount_host != 0) return giveup(ALP_OK);                       // not a filtered grid: keep the index array
+    if (e != hipSuccess) return fail(ALP_EHIP, "sub-grid check: %s", hipGetErrorString(e));
+    if (*m->qcount_host != 0) return ALP_OK;                               // not a filtered grid: keep the index array
     unsigned long long run = 0;
     for (auto &s : sums) {
         const unsigned here = s;
         s = (unsigned)run;
         run += here;
     }
-    if ((long long)run != m->n_tri) return giveup(ALP_OK);                  // cannot happen after the order check; be safe
+    if ((long long)run != m->n_tri) return ALP_OK;                          // cannot happen after the order check; be safe
     e = hipMemcpyAsync(block_dev, sums.data(), (size_t)blocks * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(subgrid_rank_kernel, dim3((unsigned)blocks), dim3(256), 0, st, m->tri_present, words, block_dev,
-                           m->tri_rank);
+        hipLaunchKernelGGL(subgrid_rank_kernel, dim3((unsigned)blocks), dim3(256), 0, st, present, words, block_dev, rank);
         e = hipStreamSynchronize(st);
     }
-    if (e != hipSuccess) return giveup(fail(ALP_EHIP, "sub-grid ranks: %s", hipGetErrorString(e)));
-    hipFree(block_dev);
-    block_dev = nullptr;
-    if (int rc = apply_derived_mask(m, nullptr)) return giveup(rc);
-    hipFree(m->ind);
-    m->ind = nullptr;
+    if (e != hipSuccess) return fail(ALP_EHIP, "sub-grid ranks: %s", hipGetErrorString(e));
+    block_dev.reset();
+    m->valid_derived = std::move(derived);
+    if (int rc = apply_derived_mask(m, nullptr)) {
+        // (m->valid: the mesh is being created, a mask can only be this function's own, half-made one)
+        reset_all(m->valid_derived, m->valid);
+        return rc;
+    }
+    m->tri_present = std::move(present);
+    m->tri_rank = std::move(rank);
+    m->ind.reset();
     m->implicit = true;
     m->grid_h = gh;
     m->grid_w = gw;
@@ -232,9 +226,8 @@ int try_subgrid(alp_mesh *m, const long long first[3]) {
 
 int ensure_gqueue(alp_mesh *m, unsigned cap) {
     if (m->gqueue && m->gcap >= cap) return ALP_OK;
-    if (m->gqueue) hipFree(m->gqueue);
-    m->gqueue = nullptr;
-    ALP_HIP(hipMalloc((void **)&m->gqueue, (size_t)cap * sizeof(unsigned)));
+    m->gcap = 0;
+    if (int rc = m->gqueue.reserve((size_t)cap * sizeof(unsigned))) return rc;
     m->gcap = cap;
     return ALP_OK;
 }
@@ -250,14 +243,12 @@ int frame_valid_count(alp_mesh *m, int64_t *count) {
     const long long npix = (long long)m->w * m->h;
     const int chunks = (int)((npix + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
     if (chunks > m->compact_cap) {
-        if (m->compact_counts) hipFree(m->compact_counts);
-        if (m->compact_offsets) hipFree(m->compact_offsets);
-        m->compact_counts = nullptr;
-        m->compact_offsets = nullptr;
         m->compact_cap = 0;
+        reset_all(m->compact_counts, m->compact_offsets);
         // counts | the chunks' extents (four floats each);  offsets | the total | the frame's extent (four floats)
-        ALP_HIP(hipMalloc((void **)&m->compact_counts, (size_t)chunks * (sizeof(unsigned) + 4 * sizeof(float)) + 16));
-        ALP_HIP(hipMalloc((void **)&m->compact_offsets, (size_t)(chunks + 3) * sizeof(unsigned long long)));
+        const size_t counts = (size_t)chunks * (sizeof(unsigned) + 4 * sizeof(float)) + 16;
+        const size_t offsets = (size_t)(chunks + 3) * sizeof(unsigned long long);
+        if (int rc = reserve_all({counts, offsets}, m->compact_counts, m->compact_offsets)) return rc;
         m->compact_cap = chunks;
     }
     hipStream_t st = ctx().stream;
@@ -295,16 +286,14 @@ namespace {
 
 int ensure_frame(alp_mesh *m, int w, int h) {
     if (m->w == w && m->h == h && m->vis) return ALP_OK;
-    if (m->vis) hipFree(m->vis);
-    if (m->image) hipFree(m->image);
-    m->vis = nullptr;
-    m->image = nullptr;
+    m->w = m->h = 0;             // the new size is published last: a frame whose buffers are not all there has no pixels
     m->vis_current = false;
-    ALP_HIP(hipMalloc((void **)&m->vis, (size_t)w * h * sizeof(unsigned long long) + QC_TOTAL * sizeof(unsigned)));   // + the frame's counters
-    ALP_HIP(hipMalloc((void **)&m->image, (size_t)w * h * 3 * sizeof(float)));
-    if (m->hiz) hipFree(m->hiz);
-    m->hiz = nullptr;
-    ALP_HIP(hipMalloc((void **)&m->hiz, (size_t)hiz_total(w, h) * sizeof(unsigned)));
+    reset_all(m->vis, m->image);
+    if (int rc = reserve_all({(size_t)w * h * sizeof(unsigned long long) + QC_TOTAL * sizeof(unsigned),      // + the frame's counters
+                              (size_t)w * h * 3 * sizeof(float)}, m->vis, m->image))
+        return rc;
+    m->hiz.reset();
+    if (int rc = m->hiz.reserve((size_t)hiz_total(w, h) * sizeof(unsigned))) return rc;
     m->w = w;
     m->h = h;
     return ALP_OK;
@@ -356,22 +345,15 @@ int ensure_grid_plan(alp_mesh *m, const host::FramePlan &p) {
     if (m->tile_bounds) return ALP_OK;
     // published only when both allocations and the launch succeeded: a half-made plan must not
     // make the next frame skip this block and read uninitialised boxes
-    float *tb = nullptr;
-    unsigned *tl = nullptr;
-    hipError_t e = hipMalloc((void **)&tb, (size_t)p.tile_bounds_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&tl, (size_t)p.tile_lists_bytes);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(tile_bounds_kernel, dim3((unsigned)p.tiles), dim3(256), 0, ctx().stream, m->vert, (int)m->grid_h,
-                           (int)m->grid_w, p.tiles_x, tb);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) {
-        if (tb) hipFree(tb);
-        if (tl) hipFree(tl);
-        return fail(ALP_EHIP, "frame plan of the mesh: %s", hipGetErrorString(e));
-    }
-    m->tile_bounds = tb;
-    m->tile_lists = tl;
+    DeviceBuffer<float> tb;
+    DeviceBuffer<unsigned> tl;
+    if (int rc = reserve_all({(size_t)p.tile_bounds_bytes, (size_t)p.tile_lists_bytes}, tb, tl)) return rc;
+    hipLaunchKernelGGL(tile_bounds_kernel, dim3((unsigned)p.tiles), dim3(256), 0, ctx().stream, m->vert, (int)m->grid_h,
+                       (int)m->grid_w, p.tiles_x, tb);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ALP_EHIP, "frame plan of the mesh: %s", hipGetErrorString(e));
+    m->tile_bounds = std::move(tb);
+    m->tile_lists = std::move(tl);
     return ALP_OK;
 }
 
@@ -574,7 +556,7 @@ static int streamed_grid_check(alp_mesh *m, const void *ind, int ind_dtype, int6
 static int upload_indices(alp_mesh *m, const void *ind, int ind_dtype) {
     hipStream_t st = ctx().stream;
     const long long n_vert = m->n_vert;
-    if (hipMalloc((void **)&m->ind, (size_t)m->n_tri * 12) != hipSuccess) return fail(ALP_EHIP, "hipMalloc ind");
+    if (int rc = m->ind.reserve((size_t)m->n_tri * 12)) return rc;
     if (hipMemsetAsync(m->qcount_dev, 0, sizeof(unsigned), st) != hipSuccess) return fail(ALP_EHIP, "index check: memset");
     const int64_t total = m->n_tri * 3;
     hipError_t e = hipSuccess;
@@ -650,15 +632,14 @@ int alp_mesh_create(const void *vert, int vert_dtype, const void *value, int val
         const int T = host_check_threads(n_tri);
         if (T > 0) host_check.start(ind, ind_dtype, cand_gh, cand_gw, T);
     }
-    if (hipMalloc((void **)&m->vert, (size_t)n_vert * 12) != hipSuccess) return bail(fail(ALP_EHIP, "hipMalloc vert"));
+    if ((rc = m->vert.reserve((size_t)n_vert * 12))) return bail(rc);
     if ((rc = upload_f32(m->vert, vert, vert_dtype, n_vert))) return bail(rc);
     if (value) {
-        if (hipMalloc((void **)&m->value, (size_t)n_vert * 12) != hipSuccess) return bail(fail(ALP_EHIP, "hipMalloc value"));
+        if ((rc = m->value.reserve((size_t)n_vert * 12))) return bail(rc);
         if ((rc = upload_f32(m->value, value, value_dtype, n_vert))) return bail(rc);
     }
-    if (hipMalloc((void **)&m->qcount_dev, QC_TOTAL * sizeof(unsigned)) != hipSuccess ||
-        hipHostMalloc((void **)&m->qcount_host, QC_TOTAL * sizeof(unsigned), hipHostMallocDefault) != hipSuccess)
-        return bail(fail(ALP_EHIP, "hipMalloc queue counter"));
+    const size_t counters = QC_TOTAL * sizeof(unsigned);
+    if ((rc = reserve_all({counters, counters}, m->qcount_dev, m->qcount_host))) return bail(rc);
     // ... checked by the host threads started above while the vertices were uploaded -- then the array never crosses
     // PCIe -- or, where there are no threads to spare, WHILE IT STREAMS through the staging buffer; either way a full
     // grid is never stored: no 12 B/triangle buffer is allocated, nothing is narrowed or written, and the mesh is
@@ -703,15 +684,6 @@ int alp_mesh_info(alp_mesh_t *m, int64_t info[4]) {
 int alp_mesh_destroy(alp_mesh_t *m) {
     if (!m) return ALP_OK;
     if (ctx().ready) hipStreamSynchronize(ctx().stream);
-    for (void *p : {(void *)m->vert, (void *)m->value, (void *)m->ind, (void *)m->valid, (void *)m->valid_derived,
-                    (void *)m->tri_present, (void *)m->tri_rank, (void *)m->vis, (void *)m->image,
-                    (void *)m->queue, (void *)m->gqueue, (void *)m->qcount_dev, (void *)m->compact_counts, (void *)m->compact_offsets,
-                    (void *)m->tile_bounds, (void *)m->tile_lists, (void *)m->hiz, (void *)m->park_small, (void *)m->park_cell,
-                    (void *)m->rz_points, (void *)m->rz_work})
-        if (p) hipFree(p);
-    if (m->qcount_host) hipHostFree(m->qcount_host);
-    for (auto &e : m->ev_frame)
-        if (e) hipEventDestroy(e);
     delete m;
     return ALP_OK;
 }
@@ -728,14 +700,12 @@ int alp_render_enqueue(alp_mesh_t *m, const double params[ALP_NPARAM], const dou
     // same view as the frame whose visibility buffer is still there: the raster passes would rebuild it bit for bit
     const bool no_cache = getenv("ALP_NO_VIS_CACHE") != nullptr;      // tests, benchmarks: force the full frame
     const bool cached = m->vis_current && !no_cache && same_view(v, m->last_v);
-    if (!m->ev_frame[0]) {
-        hipEvent_t a = nullptr, b = nullptr;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
-            if (a) hipEventDestroy(a);
-            return fail(ALP_EHIP, "hipEventCreate failed");
-        }
-        m->ev_frame[0] = a;
-        m->ev_frame[1] = b;
+    if (!m->ev_frame[0]) {       // both or neither
+        Event a, b;
+        if (int e = a.ensure()) return e;
+        if (int e = b.ensure()) return e;
+        m->ev_frame[0] = std::move(a);
+        m->ev_frame[1] = std::move(b);
     }
     ALP_HIP(hipEventRecord(m->ev_frame[0], ctx().stream));
     const int e = render_impl(m, v, rc, min_distance, cached);
@@ -757,12 +727,8 @@ int alp_mesh_trim(alp_mesh_t *m) {
     if (int rc = require_init()) return rc;
     ALP_REQUIRE(m, "mesh handle is NULL");
     ALP_HIP(hipStreamSynchronize(ctx().stream));
-    if (m->rz_work) hipFree(m->rz_work);
-    m->rz_work = nullptr;
-    m->rz_work_cap = 0;
-    if (m->rz_points) hipFree(m->rz_points);
-    m->rz_points = nullptr;
-    m->rz_cap = 0;
+    m->rz_work.reset();
+    m->rz_points.reset();
     m->rz_n = -1;
     return ALP_OK;
 }

@@ -44,35 +44,36 @@ struct alignas(16) ParkedCell {
 struct alp_mesh {
     int64_t n_vert = 0, n_tri = 0, grid_h = 0, grid_w = 0;
     bool implicit = false;
-    float *vert = nullptr, *value = nullptr;
-    int *ind = nullptr;
-    unsigned char *valid = nullptr;    // optional, per vertex: 0 = nodata, its triangles are not drawn
+    alp::DeviceBuffer<float> vert, value;
+    alp::DeviceBuffer<int> ind;
+    alp::DeviceBuffer<unsigned char> valid;    // optional, per vertex: 0 = nodata, its triangles are not drawn
     // A filtered index array of the regular grid (surface.py:203-205: the triangles of nodata vertices removed)
     // recognised at creation: rendered as the implicit grid with the vertex mask it implies; these map the
     // grid's triangle ids back to positions in the caller's array (alp_render_fetch_visibility)
-    unsigned char *valid_derived = nullptr;   // the mask implied by the index array (valid = derived AND the caller's)
-    unsigned *tri_present = nullptr;          // bit per grid triangle: present in the caller's array
-    unsigned *tri_rank = nullptr;             // per 32-bit word of tri_present: number of present triangles before it
-    float *tile_bounds = nullptr;      // implicit grid: bounding box (centre, half extent) per raster_grid_kernel tile
-    unsigned *tile_lists = nullptr;    // implicit grid: near / far / surviving-far tile ids of the current frame + counters
-    unsigned *hiz = nullptr;           // depth pyramid of the current frame size (levels 8 .. 256 px)
+    alp::DeviceBuffer<unsigned char> valid_derived;   // the mask implied by the index array (valid = derived AND the caller's)
+    alp::DeviceBuffer<unsigned> tri_present;  // bit per grid triangle: present in the caller's array
+    alp::DeviceBuffer<unsigned> tri_rank;     // per 32-bit word of tri_present: number of present triangles before it
+    alp::DeviceBuffer<float> tile_bounds;      // implicit grid: bounding box (centre, half extent) per raster_grid_kernel tile
+    alp::DeviceBuffer<unsigned> tile_lists;    // implicit grid: near / far / surviving-far tile ids of the current frame + counters
+    alp::DeviceBuffer<unsigned> hiz;           // depth pyramid of the current frame size (levels 8 .. 256 px)
     bool coords_as_value = false;      // render the vertices themselves (reverse_proj) although values are stored
     // per-render state (sized on first use)
     int w = 0, h = 0;
-    unsigned long long *vis = nullptr;
-    float *image = nullptr;
-    alp::WorkItem *queue = nullptr;
+    alp::DeviceBuffer<unsigned long long> vis;
+    alp::DeviceBuffer<float> image;
+    alp::DeviceBuffer<alp::WorkItem> queue;
     unsigned qcap = 0;
-    unsigned *gqueue = nullptr;        // general queue: triangle ids set aside by raster_grid_kernel
+    alp::DeviceBuffer<unsigned> gqueue;        // general queue: triangle ids set aside by raster_grid_kernel
     unsigned gcap = 0;
-    alp::Deferred *park_small = nullptr, *park_large = nullptr;   // implicit grid: parked triangles (one allocation)
-    alp::ParkedCell *park_cell = nullptr;                         // implicit grid: parked cells
+    alp::DeviceBuffer<alp::Deferred> park_small;                  // implicit grid: parked triangles, small then large
+    alp::Deferred *park_large = nullptr;                          // (points into park_small's block)
+    alp::DeviceBuffer<alp::ParkedCell> park_cell;                 // implicit grid: parked cells
     unsigned park_cap[3] = {0, 0, 0};                             // small, large, cells: first round
     unsigned park_cap_b[3] = {0, 0, 0};                           // second round (its entries follow the first round's)
     // per round (2 rounds x QC_STRIDE) [0] work items, [1] general entries, [2] small parked, [3] large parked,
     // [4] parked cells; then the three tile-list lengths of the frame plan
-    unsigned *qcount_dev = nullptr;
-    unsigned *qcount_host = nullptr;   // pinned copy of the queue counters of the last frame
+    alp::DeviceBuffer<unsigned> qcount_dev;
+    alp::PinnedBuffer<unsigned> qcount_host;   // copy of the queue counters of the last frame
     bool unchecked = false;            // last frame enqueued, its queue counters not yet checked (finish_frame)
     alp::View last_v;
     alp::RemapCoef last_rc;
@@ -85,23 +86,21 @@ struct alp_mesh {
     bool vis_current = false;
     int64_t frames_full = 0, frames_resolve_only = 0;
     // reverse_proj compaction scratch
-    unsigned *compact_counts = nullptr;
-    unsigned long long *compact_offsets = nullptr;
+    alp::DeviceBuffer<unsigned> compact_counts;
+    alp::DeviceBuffer<unsigned long long> compact_offsets;
     int compact_cap = 0;
     float valid_span[4] = {0, 0, 0, 0};      // frame_valid_count: min / max of channel 0, min / max of channel 2 over the pixels that see the surface
     int64_t valid_total = -1;
     int64_t valid_total_planes = 0;     // plane length of the planar form of frame_valid_write
     // alp_render_rasterize_plan -> alp_render_rasterize: the compacted points of the current frame (device):
     // x[M] | y[M] float64, then the pixel index idx[M] uint32
-    char *rz_points = nullptr;
-    size_t rz_cap = 0;
+    alp::DeviceBuffer<char> rz_points;
     int64_t rz_n = -1;                 // -1: no plan for the current frame
     // work area of alp_render_rasterize (values, accumulators, raster, the caller's image): kept between calls, grow-only --
     // 5.3 GB for the 100 M-vertex frame at 1 m; allocating and freeing it per call cost 2 ms, and now and then 0.25-0.4 s
-    char *rz_work = nullptr;
-    size_t rz_work_cap = 0;
+    alp::DeviceBuffer<char> rz_work;
     // HIP events around the launches of the last alp_render_enqueue (alp_mesh_frame_ms); created on first use
-    hipEvent_t ev_frame[2] = {nullptr, nullptr};
+    alp::Event ev_frame[2];
 };
 
 namespace alp {

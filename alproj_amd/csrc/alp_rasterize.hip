@@ -345,13 +345,7 @@ extern "C" int alp_render_rasterize_plan(alp_mesh_t *m, const double *offsets, i
     bounds[0] = bounds[1] = bounds[2] = bounds[3] = NAN;
     if (M == 0) { m->rz_n = 0; return ALP_OK; }
     const size_t need = (size_t)M * (8 + 8 + 8 + 4) + 64;      // x | y | z planes (the compaction writes all three), then the pixel index
-    if (need > m->rz_cap) {
-        if (m->rz_points) hipFree(m->rz_points);
-        m->rz_points = nullptr;
-        m->rz_cap = 0;
-        ALP_HIP(hipMalloc((void **)&m->rz_points, need));
-        m->rz_cap = need;
-    }
+    if (int rc = m->rz_points.reserve(need)) return rc;
     double *x = (double *)m->rz_points;
     unsigned *idx = (unsigned *)(x + 3 * M);
     // the compaction writes planes directly (x = channel 0 + offset, y = channel 2 + offset: project.py:361, :370-373): no
@@ -392,13 +386,7 @@ extern "C" int alp_render_rasterize(alp_mesh_t *m, const void *array, int array_
     const size_t total = (size_t)width * height * nb;
     // values | raster a | raster b | out (u8) | band table | the caller's array   (the sort buffers: the library scratch)
     const size_t bytes = (size_t)n * nb * 8 + total * (4 + 4 + 1) + 64 * 4 + 256 + arr_bytes + 64;
-    if (bytes > m->rz_work_cap) {
-        if (m->rz_work) hipFree(m->rz_work);
-        m->rz_work = nullptr;
-        m->rz_work_cap = 0;
-        ALP_HIP(hipMalloc((void **)&m->rz_work, bytes));
-        m->rz_work_cap = bytes;
-    }
+    if (int rc = m->rz_work.reserve(bytes)) return rc;
     char *dev = m->rz_work;
     double *dv = (double *)dev;
     float *ra = (float *)(dv + (size_t)n * nb), *rb = ra + total;
@@ -465,13 +453,13 @@ static int rasterize_host_points(const char *who, const double *x, const double 
         for (int64_t b = 0; b < nb; ++b) ALP_REQUIRE(cols[b], "a band column is NULL");
     const size_t total = (size_t)width * height * nb;
     const size_t pts_bytes = (size_t)n * sizeof(double);
-    char *dev = nullptr;
+    DeviceBuffer<char> dev;          // released on every way out, behind the synchronisation below
     // x | y | values | raster a | raster b | out (u8) | flag words | sort buffers; the columns are staged in the sort buffers when
     // they fit (they are interleaved -- or, byte-valued, packed -- into `values` before the first sort), else behind them
     const size_t sort_bytes = rz_sort_bytes(n, nullptr);
     const bool stage_in_sort = cols && pts_bytes * nb <= sort_bytes;
     const size_t bytes = pts_bytes * (2 + nb) + total * (4 + 4 + 1) + 512 + 256 + sort_bytes + ((cols && !stage_in_sort) ? pts_bytes * nb + 64 : 0);
-    ALP_HIP(hipMalloc((void **)&dev, bytes));
+    if (int rc = dev.reserve(bytes)) return rc;
     double *dx = (double *)dev, *dy = dx + n, *dv = dy + n;
     float *ra = (float *)(dv + (size_t)n * nb), *rb = ra + total;
     unsigned char *out_dev = (unsigned char *)(rb + total);
@@ -514,7 +502,6 @@ static int rasterize_host_points(const char *who, const double *x, const double 
     }
     if (e == hipSuccess && rc == ALP_OK && !out_f32) e = hipMemcpyAsync(out, out_dev, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    hipFree(dev);
     if (rc) return rc;
     if (e != hipSuccess) return fail(ALP_EHIP, "%s: %s", who, hipGetErrorString(e));
     return ALP_OK;

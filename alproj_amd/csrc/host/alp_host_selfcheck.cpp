@@ -1,4 +1,4 @@
-// Self-checking driver of the HIP-free host code (host/alp_host.h, host/alp_host.cpp).  NOT part of libalproj_hip.so:
+// Self-checking driver of the HIP-free host code (host/alp_host.h, host/alp_host.cpp, host/alp_buffer.h).  NOT part of libalproj_hip.so:
 // alproj_amd/_build.py: build_host() links it with alp_host.cpp into build/host_san/alp_host_{plain,asan,tsan} and
 // tests/test_host_sanitized.py runs the three executables.  Every threaded helper is called with sizes that straddle
 // its thread thresholds (1, 70 001, one short of / exactly / one past a slice, two slices and a ragged rest), with
@@ -15,6 +15,7 @@
 #include <utility>
 
 #include "host/alp_host.h"
+#include "host/alp_buffer.h"
 
 using namespace alp;
 
@@ -809,6 +810,107 @@ int lm_mode() {
     return 0;
 }
 
+// ------------------------------------------------------------------ Buffer / reserve_all (host/alp_buffer.h)
+// The memory policy of this group: malloc and free (so a leak, a double free or a use after release is the sanitizers' to
+// report), counted, and told to fail the k-th allocation from now.  Only this group's thread touches it.
+struct CountedMemory {
+    static int live, peak, allocs, fail_at;      // blocks held now / at most since `peak` was reset; calls; the call to fail (0: none)
+    static int alloc(void **p, size_t bytes) {
+        if (++allocs == fail_at) return fail(ALP_EHIP, "counted allocation %d failed", allocs);
+        *p = malloc(bytes ? bytes : 1);
+        memset(*p, 0xA5, bytes);
+        ++live;
+        peak = std::max(peak, live);
+        return ALP_OK;
+    }
+    static void release(void *p) {
+        free(p);
+        --live;
+    }
+    static void fail_next(int k) { allocs = 0, fail_at = k; }
+};
+int CountedMemory::live = 0, CountedMemory::peak = 0, CountedMemory::allocs = 0, CountedMemory::fail_at = 0;
+
+void check_buffer() {
+    using Mem = CountedMemory;
+    using Bytes = Buffer<Mem, unsigned char>;
+    {
+        Bytes b;
+        CHECK(!b && b.get() == nullptr && b.capacity() == 0 && Mem::live == 0, "a new buffer is not empty");
+        CHECK(b.reserve(100) == ALP_OK && b && b.capacity() == 100 && Mem::live == 1, "first reserve");
+        unsigned char *first = b;
+        b[99] = 7;
+        // a reserve that fits keeps the block (and what is in it)
+        CHECK(b.reserve(100) == ALP_OK && b.reserve(1) == ALP_OK && b.get() == first && b.capacity() == 100 && b[99] == 7,
+              "a reserve that fits moved the block");
+        CHECK(Mem::live == 1, "a reserve that fits left %d blocks", Mem::live);
+        // a reserve that grows releases first: never more blocks live than before the call
+        Mem::peak = Mem::live;
+        CHECK(b.reserve(101) == ALP_OK && b.capacity() == 101 && Mem::live == 1 && Mem::peak == 1,
+              "growing held %d blocks at once", Mem::peak);
+        b[100] = 1;
+        // a failed reserve: empty, capacity 0, nothing live, the policy's code
+        Mem::fail_next(1);
+        CHECK(b.reserve(1000) == ALP_EHIP && !b && b.capacity() == 0 && Mem::live == 0,
+              "a failed reserve left %d block(s)", Mem::live);
+        CHECK(strstr(alp_last_error(), "counted allocation") != nullptr, "error text: %s", alp_last_error());
+        Mem::fail_next(0);
+        CHECK(b.reserve(8) == ALP_OK && b.capacity() == 8 && Mem::live == 1, "reserve after a failure");
+        b.reset();
+        CHECK(!b && b.capacity() == 0 && Mem::live == 0, "reset");
+        b.reset();                                  // (of an empty buffer: nothing to release)
+        CHECK(Mem::live == 0, "second reset");
+    }
+    {   // moves: the source comes out empty, a block the target held is released
+        Bytes a;
+        CHECK(a.reserve(16) == ALP_OK, "reserve");
+        unsigned char *pa = a;
+        Bytes b(std::move(a));
+        CHECK(!a && a.capacity() == 0 && b.get() == pa && b.capacity() == 16 && Mem::live == 1, "move construction");
+        Bytes c;
+        c = std::move(b);
+        CHECK(!b && c.get() == pa && c.capacity() == 16 && Mem::live == 1, "move assignment to an empty buffer");
+        Bytes d;
+        CHECK(d.reserve(32) == ALP_OK && Mem::live == 2, "reserve");
+        d = std::move(c);
+        CHECK(!c && d.get() == pa && d.capacity() == 16 && Mem::live == 1, "move assignment onto a block left %d live", Mem::live);
+        Bytes &self = d;
+        d = std::move(self);
+        CHECK(d.get() == pa && Mem::live == 1, "self-assignment");
+        Buffer<Mem> v;                              // the untyped form reads like a void *
+        CHECK(v.reserve(8) == ALP_OK && (const float *)v == (const float *)v.get() && (char *)v + 4 == (char *)v.get() + 4, "casts");
+    }
+    CHECK(Mem::live == 0, "%d block(s) outlived their buffers", Mem::live);
+    // groups of 2 and 3: whichever member fails, the whole group comes out empty -- the members that held a block before the
+    // call included -- and the next call succeeds
+    for (int size = 2; size <= 3; ++size)
+        for (int bad = 1; bad <= size; ++bad)
+            for (int held = 0; held < 2; ++held) {
+                Buffer<Mem, double> x;
+                Buffer<Mem> y;
+                Buffer<Mem, int> z;
+                auto group = [&](size_t n) {
+                    return size == 2 ? reserve_all({n, 2 * n}, x, y) : reserve_all({n, 2 * n, 3 * n}, x, y, z);
+                };
+                if (held) CHECK(group(8) == ALP_OK && Mem::live == size, "first group");
+                Mem::fail_next(bad);
+                CHECK(group(64) == ALP_EHIP && !x && !y && !z && x.capacity() + y.capacity() + z.capacity() == 0 && Mem::live == 0,
+                      "group of %d, member %d failed (held %d): %d block(s) live", size, bad, held, Mem::live);
+                Mem::fail_next(0);
+                CHECK(group(64) == ALP_OK && x && y && (size == 2 || z) && x.capacity() == 64 && y.capacity() == 128,
+                      "group of %d after a failure", size);
+                CHECK(Mem::live == size, "group of %d after a failure: %d blocks", size, Mem::live);
+                x[7] = 1.0;                         // (the last element each: the sanitizers hold the sizes to it)
+                ((char *)y)[127] = 1;
+                if (size == 3) z[47] = 1;
+                double *px = x;
+                CHECK(group(64) == ALP_OK && x.get() == px && Mem::live == size, "a group that fits moved");
+                reset_all(x, y, z);
+                CHECK(Mem::live == 0, "reset_all");
+            }
+    CHECK(Mem::live == 0, "%d block(s) live at the end", Mem::live);
+}
+
 int main(int argc, char **argv) {
     if (argc > 2 && !strcmp(argv[1], "--canary")) return canary(argv[2]);
     if (argc > 1 && !strcmp(argv[1], "--plan")) return plan(argc - 2, argv + 2);
@@ -816,7 +918,8 @@ int main(int argc, char **argv) {
     struct Group { const char *name; void (*fn)(); };
     const Group groups[] = {{"hash", check_hash},     {"minmax", check_minmax},   {"prefault", check_prefault}, {"fold_pose", check_fold_pose},
                             {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors},
-                            {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}, {"lm", check_lm}};
+                            {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}, {"lm", check_lm},
+                            {"buffer", check_buffer}};
     const bool concurrent = !(argc > 1 && !strcmp(argv[1], "--serial"));
     // every group on its own caller thread at once: the library promises that independent calls may overlap
     std::vector<std::thread> th;

@@ -236,10 +236,13 @@ def test_the_bindings_refuse_what_the_library_would_misread(L):
 
 
 def test_handles_give_their_device_memory_back(L):
-    """forty lives of a point set (float32 and float64, row-major and column uploads, observed pixels, projection, both fetches,
-    population evaluation with argmin confirmation, residuals) and of a mesh (grid and index array, render, visibility, the
-    visible-pixel table, rasterisation from the frame, a mesh from rasters): the free device memory hipMemGetInfo reports after
-    them is what it was after the first two (grow-only scratch areas reach their size in those)"""
+    """forty lives of a point set (float32 and float64, row-major and column uploads, observed pixels, weights set and cleared,
+    projection, both fetches, population evaluation with argmin confirmation and the mend pass, residuals; on a small set the
+    Jacobian, the normal equations alone and in a batch, and a CMA-ES and a least-squares device loop, closed before or after
+    their point set) and of a mesh (grid and index array, render at two frame sizes, values and a vertex mask set and dropped,
+    visibility, the visible-pixel table, rasterisation from the frame, trim, a mesh from rasters): the free device memory
+    hipMemGetInfo reports after them is what it was after the first two (grow-only scratch areas reach their size in those)"""
+    from alproj_amd.cma import CMA
     from alproj_amd import synthetic as syn
     hip = ctypes.CDLL("libamdhip64.so")
 
@@ -262,17 +265,51 @@ def test_handles_give_their_device_memory_back(L):
     dsm = (1500 + rng.normal(0, 20, (n, n))).astype(np.float32)
     aerial = rng.integers(0, 256, (3, n, n), dtype=np.uint8)
     img = rng.integers(0, 256, (320, 480, 3), dtype=np.uint8)
+    weights = rng.uniform(0.5, 2.0, len(xyz))
+    # the least-squares paths and the device loops: a small set of their own
+    small_xyz, small_uv = xyz[:3000], uv[:3000]
+    targets, D = syn.TARGETS_D9, 9
+    idx = np.array([L.PARAM_KEYS.index(t) for t in targets], dtype=np.int32)
+    b = orc.bounds_to_array(truth, targets)
+    lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+    X0 = np.stack([lo + 0.45 * (hi - lo), lo + 0.55 * (hi - lo)])
+    cam2 = dict(cam, w=400, h=240, cx=200.0, cy=120.0)
+    value = rng.uniform(0, 1, s["vert"].shape).astype(np.float32)
+    mask = rng.uniform(0, 1, len(s["vert"])) > 0.1
+
+    def small_life(k, prec):
+        q = L.Points(small_xyz, origin, prec)
+        q.set_observed(small_uv)
+        q.jacobian(cand[0], idx), q.normal_equations(cand[0], idx), q.normal_equations_batch(cand, idx)
+        host = CMA(mean=np.full(D, 0.5), sigma=0.3, bounds=np.column_stack([np.zeros(D), np.ones(D)]), population_size=8,
+                   n_max_resampling=100, seed=k, sampler=L.cma_sample)
+        cma_loop = L.CmaDevice(q, cand[0], idx, lo, hi, host, seeds=[k, k + 100])
+        cma_loop.run(2, L.LOSS_HUBER, 10.0)
+        cma_loop.wait()
+        lm_loop = L.LmDevice(q, cand[0], idx, lo, hi, X0)
+        lm_loop.run(2)
+        lm_loop.wait()
+        # the loops are told when their point set goes first (alp_points_destroy), and drop it from its list when they go first
+        for h in (q, cma_loop, lm_loop) if k % 2 else (cma_loop, lm_loop, q):
+            h.close()
 
     def one_life(k):
         prec = "f32" if k % 2 else "f64"
         pts = L.Points(xyz, origin, prec) if k % 3 else L.Points.from_columns(xyz[:, 0].copy(), xyz[:, 1].copy(), xyz[:, 2].copy(), origin, prec)
         with pts as p:
             p.set_observed(uv)
+            if k % 3 == 0:
+                p.set_weights(weights)
             p.project(cand[0])
             p.fetch(np.float64), p.fetch(np.float32), p.fetch_strided(0, 7, 1000)
+            if prec == "f32":
+                p.set_mend(True)
             p.eval_population(cand, L.LOSS_HUBER, 10.0)
+            if k % 3 == 0:
+                p.set_weights(None)
             if prec == "f64":
                 p.residuals(cand[0]), p.residuals_batch(cand)
+        small_life(k, prec)
         os.environ["ALP_NO_GRID_DETECT"] = "1" if k % 2 else "0"
         try:
             mesh = L.Mesh(s["vert"], None, ind if k % 2 else None, grid=None if k % 2 else (n, n))
@@ -280,10 +317,16 @@ def test_handles_give_their_device_memory_back(L):
             os.environ.pop("ALP_NO_GRID_DETECT", None)
         with mesh as m:
             m.render_enqueue(L.params_vector(cam), s["offsets"], coords=True)
+            m.render_enqueue(L.params_vector(cam2), s["offsets"], coords=True)         # another frame size, and back: the frame
+            m.set_value(value), m.set_valid(mask)                                      # buffers are replaced twice
+            m.render_enqueue(L.params_vector(cam), s["offsets"])
+            m.set_value(None), m.set_valid(None)
+            m.render_enqueue(L.params_vector(cam), s["offsets"], coords=True)
             m.fetch(), m.fetch_visibility(), m.fetch_valid(s["offsets"])
             cnt, (x0, y0, x1, y1) = m.rasterize_plan(s["offsets"])
             if cnt:
                 m.rasterize(img, [0, 1, 2], x0, y1, 2.0, int(np.ceil((x1 - x0) / 2.0)), int(np.ceil((y1 - y0) / 2.0)), 0, 1, 255)
+            m.trim()
         m2, _ = L.Mesh.from_rasters(dsm, (1.0, 0.0, 0.0, 0.0, -1.0, float(n)), 1600.0, aerial, 255.0, None)
         m2.close()
 

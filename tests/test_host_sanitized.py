@@ -70,7 +70,7 @@ def test_library_and_sanitized_build_share_their_sources():
     """what runs under the sanitizers is what ships: the library's source list names host/alp_host.cpp, and neither it nor
     the header it shares with the .hip units includes a HIP header"""
     assert "host/alp_host.cpp" in _build.SOURCES
-    for name in ("alp_host.h", "alp_host.cpp", "alp_fold.h", "alp_plan.h"):
+    for name in ("alp_host.h", "alp_host.cpp", "alp_fold.h", "alp_plan.h", "alp_buffer.h"):
         text = open(os.path.join(_build.HOST_DIR, name)).read()
         assert "hip_runtime" not in text and "#include <hip" not in text, name
     # the moved code is gone from the HIP units: one definition each
