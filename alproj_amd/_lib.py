@@ -18,6 +18,7 @@ LOSS_MEAN_DIST, LOSS_HUBER = 0, 1
 # alp_normal_equations: scipy.optimize.least_squares' losses of one scalar residual (enum alp_normal_loss)
 NORMAL_LOSSES = {"linear": 0, "soft_l1": 1, "huber": 2, "cauchy": 3}
 NORMAL_BATCH_MAX = 1024         # alp_normal_equations_batch: poses per call
+WEIGHT_TABLE_MAX_BYTES = 1 << 30  # ALP_WEIGHT_TABLE_MAX_BYTES: the stored size of a weight table (a guard, not a tuned number)
 NPARAM = 25
 UNIQUE_ID_BYTES = 128
 
@@ -214,6 +215,11 @@ _SIGNATURES = {
     "alp_points_set_mend": [_c_void_p, _c_int],
     "alp_points_set_weights": [_c_void_p, _c_void_p, _c_int],
     "alp_points_weight_sum": [_c_void_p, ctypes.POINTER(ctypes.c_double)],
+    "alp_points_set_weight_table": [_c_void_p, _c_void_p, _c_int, _c_int],
+    "alp_points_weight_table_sums": [_c_void_p, _c_dp],
+    "alp_normal_equations_batch_rows": [_c_void_p, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _c_int,
+                                        _c_int, _c_double, _c_dp],
+    "alp_residuals_assigned": [_c_void_p, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_dp],
     "alp_eval_population_mended": [_c_void_p, ctypes.POINTER(_c_i64)],
     "alp_loss_uv": [_c_dp, _c_dp, _c_i64, _c_int, _c_double, _c_dp],
     "alp_loss_uv_columns": [_c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_int, _c_double, _c_dp],
@@ -230,6 +236,8 @@ _SIGNATURES = {
     "alp_cma_fetch_last": [_c_void_p, _c_dp, _c_dp, _c_dp],
     "alp_lm_create": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_dp, _c_dp, _c_dp, _c_int, _c_int, _c_double, _c_double,
                       _c_double, _c_double, _c_i64, ctypes.POINTER(_c_void_p)],
+    "alp_lm_create_rows": [_c_void_p, _c_dp, ctypes.POINTER(ctypes.c_int32), _c_int, _c_dp, _c_dp, _c_dp, _c_int, _c_int, _c_double,
+                           _c_double, _c_double, _c_double, _c_i64, ctypes.POINTER(_c_void_p)],
     "alp_lm_destroy": [_c_void_p],
     "alp_lm_run": [_c_void_p, _c_i64],
     "alp_lm_wait": [_c_void_p, ctypes.POINTER(_c_i64)],
@@ -554,6 +562,86 @@ class Points:
         W = ctypes.c_double()
         check(self._lib.alp_points_weight_sum(self._h, ctypes.byref(W)))
         return float(W.value)
+
+    def set_weight_table(self, table):
+        """A table of R weight rows (alp_points_set_weight_table): ``table`` (R, N) holds finite values >= 0, 1 <= R <=
+        NORMAL_BATCH_MAX, at most WEIGHT_TABLE_MAX_BYTES once stored in the set's element type (a float32 set rounds);
+        ``None`` drops it.  ``normal_equations_batch_rows`` and ``LmDevice(weight_rows=True)`` evaluate a pose under the row
+        they name for it; every other call ignores the table, and the rows' users ignore ``set_weights``' plane.  The row
+        sums are formed on the device (``weight_table_sums``).  ValueError -- the previous table stays in force -- for
+        another shape, a negative, NaN or infinite weight or a table over the cap."""
+        if table is None:
+            check(self._lib.alp_points_set_weight_table(self._h, None, 0, ALP_F64))
+            self._table_rows = 0
+            return
+        t = np.asarray(table)
+        if t.dtype not in (np.float32, np.float64):
+            t = t.astype(np.float64)
+        t = np.ascontiguousarray(t)
+        if t.ndim != 2 or t.shape[1] != self.n or not 1 <= t.shape[0] <= NORMAL_BATCH_MAX:
+            raise ValueError(f"a weight table must have shape (R, {self.n}) with 1 <= R <= {NORMAL_BATCH_MAX}")
+        if t.shape[0] * self.n * (4 if self.precision == ALP_F32 else 8) > WEIGHT_TABLE_MAX_BYTES:
+            raise ValueError(f"the stored weight table would exceed {WEIGHT_TABLE_MAX_BYTES} bytes")
+        if not np.isfinite(t).all() or (t < 0).any():
+            raise ValueError("weights must be finite and >= 0")
+        if self.precision == ALP_F32:
+            with np.errstate(over="ignore"):
+                if not np.isfinite(t.astype(np.float32)).all():
+                    raise ValueError("a weight does not fit float32")
+        check(self._lib.alp_points_set_weight_table(self._h, t.ctypes.data_as(_c_void_p), t.shape[0], dtype_code(t)))
+        self._table_rows = int(t.shape[0])
+
+    def weight_table_sums(self):
+        """(R,) float64: this rank's sum of every stored row of the weight table, as the device formed them -- in an order
+        that depends on N alone, no atomics (alp_points_weight_table_sums)"""
+        out = np.empty(int(getattr(self, "_table_rows", 0)), dtype=np.float64)
+        check(self._lib.alp_points_weight_table_sums(self._h, as_dp(out)))
+        return out
+
+    def normal_equations_batch_rows(self, cand, row_of_pose, target_idx, loss="linear", f_scale=1.0):
+        """-> (G (B, D, D), g (B, D), cost (B,), W (B,)): ``normal_equations_batch`` with pose b evaluated under row
+        ``row_of_pose[b]`` of the weight table (``set_weight_table``; repeats allowed, B need not be R), in one launch
+        (alp_normal_equations_batch_rows).  Row b has the bits ``set_weights(table[row_of_pose[b]])`` +
+        ``normal_equations_batch(cand)`` give for the same B; W[b] is that row's sum of weights (over the ranks).  ValueError,
+        before the library is called, for what ``normal_equations_batch`` refuses and a row index outside the table."""
+        idx = normal_targets_check(target_idx)
+        kind, fs = normal_loss_check(loss, f_scale)
+        cand = np.ascontiguousarray(cand, dtype=np.float64)
+        if cand.ndim != 2 or cand.shape[1] != NPARAM or not 1 <= cand.shape[0] <= NORMAL_BATCH_MAX:
+            raise ValueError(f"cand must have shape (B, 25) with 1 <= B <= {NORMAL_BATCH_MAX}")
+        b, d = cand.shape[0], len(idx)
+        rows = np.ascontiguousarray(np.asarray(row_of_pose).reshape(-1), dtype=np.int32)
+        if rows.shape != (b,) or ((rows < 0) | (rows >= int(getattr(self, "_table_rows", 0)))).any():
+            raise ValueError("row_of_pose must hold one row index of the weight table per pose")
+        tri = d * (d + 1) // 2
+        out = np.empty((b, tri + d + 2), dtype=np.float64)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        check(self._lib.alp_normal_equations_batch_rows(self._h, as_dp(cand), b, rows.ctypes.data_as(i32), idx.ctypes.data_as(i32), d,
+                                                        kind, fs, as_dp(out)))
+        iu = np.triu_indices(d)
+        G = np.zeros((b, d, d), dtype=np.float64)
+        G[:, iu[0], iu[1]] = out[:, :tri]
+        G = G + np.triu(G, 1).transpose(0, 2, 1)
+        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], out[:, tri + d + 1].copy()
+
+    def residuals_assigned(self, cand, assign):
+        """(B, 25) parameter vectors and (N,) int assignments -> (2N,) residuals in ``residuals``' order: point i under
+        ``cand[assign[i]]``, a NaN pair where ``assign[i] < 0`` -- one launch (alp_residuals_assigned).  Float64 arithmetic on
+        either set; on a float64 set the pair of point i has the bits of row ``assign[i]`` of ``residuals_batch(cand)``.
+        ValueError for another shape or an assignment >= B."""
+        cand = np.ascontiguousarray(cand, dtype=np.float64)
+        if cand.ndim != 2 or cand.shape[1] != NPARAM or not 1 <= cand.shape[0] <= 4096:
+            raise ValueError("cand must have shape (B, 25) with 1 <= B <= 4096")
+        a = np.asarray(assign)
+        if a.shape != (self.n,) or a.dtype.kind not in "iu":
+            raise ValueError(f"assign must hold {self.n} integers")
+        if (a >= cand.shape[0]).any():
+            raise ValueError("an assignment names a pose past the last one")
+        a = np.ascontiguousarray(np.where(a < 0, -1, a), dtype=np.int32)
+        out = result_empty(2 * self.n, np.float64)
+        check(self._lib.alp_residuals_assigned(self._h, as_dp(cand), cand.shape[0], a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                               as_dp(out)))
+        return out
 
     def _count(self, slot):
         """the count slot of a normal-equation result: the point count, or W (a float) on a weighted set"""
@@ -1165,10 +1253,12 @@ class LmDevice:
     trial points, step, selection) without the host in between, ``wait()`` synchronises and returns how many starts still run.
     ``points``: the Points (with observed uv) the sums are formed on; ``template``: the 25-vector of params_init; ``targets``:
     ABI indices of the targets (normal_targets_check's rule); ``lower`` / ``upper``: the box; ``X0`` (K, D): the starts;
-    ``loss`` / ``f_scale`` as for ``Points.normal_equations``; tolerances and ``max_nfev`` (None: 100 D) as for normal_lm."""
+    ``loss`` / ``f_scale`` as for ``Points.normal_equations``; tolerances and ``max_nfev`` (None: 100 D) as for normal_lm.
+    ``weight_rows=True`` (alp_lm_create_rows): start k is evaluated under row k of the set's weight table
+    (``Points.set_weight_table``), which must have exactly K rows, instead of under the weight plane."""
 
     def __init__(self, points, template, targets, lower, upper, X0, loss="linear", f_scale=1.0, ftol=1e-10, xtol=1e-10, gtol=1e-10,
-                 max_nfev=None):
+                 max_nfev=None, weight_rows=False):
         l = lib()
         idx = normal_targets_check(targets)
         kind, fs = normal_loss_check(loss, f_scale)
@@ -1181,9 +1271,10 @@ class LmDevice:
             raise ValueError("template must have 25 entries, lower / upper D and X0 the shape (K, D)")
         self.K = int(X0.shape[0])
         h = _c_void_p()
-        check(l.alp_lm_create(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo), as_dp(hi),
-                              as_dp(X0), self.K, kind, fs, float(ftol), float(xtol), float(gtol),
-                              100 * self.D if max_nfev is None else max(1, int(max_nfev)), ctypes.byref(h)))
+        create = l.alp_lm_create_rows if weight_rows else l.alp_lm_create
+        check(create(points._h, as_dp(tmpl), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.D, as_dp(lo), as_dp(hi),
+                     as_dp(X0), self.K, kind, fs, float(ftol), float(xtol), float(gtol),
+                     100 * self.D if max_nfev is None else max(1, int(max_nfev)), ctypes.byref(h)))
         self._h = h
         self._lib = l
         self.points = points
@@ -1290,6 +1381,13 @@ def comm_info():
     r, w = _c_int(), _c_int()
     check(lib().alp_comm_info(ctypes.byref(r), ctypes.byref(w)))
     return r.value, w.value
+
+
+def comm_world():
+    """the number of ranks, 1 without a communicator; unlike ``comm_info`` it initialises nothing: the GPU is not touched"""
+    world = _c_int()
+    check(load().alp_comm_info(None, ctypes.byref(world)))
+    return int(world.value)
 
 
 def comm_bcast(array, root=0):

@@ -116,6 +116,7 @@ struct alp_lm {
     int *list = nullptr, *running = nullptr;
     long long *count = nullptr;
     bool pending = false;         // rounds enqueued, alp_lm_wait not yet called
+    bool weight_rows = false;     // alp_lm_create_rows: start k under row k of the set's weight table
     int T() const { return a.cfg.D * (a.cfg.D + 1) / 2 + a.cfg.D + 1; }
 };
 
@@ -142,13 +143,10 @@ int launch_step_select(alp_lm *h, int consume) {
     return ALP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
-                  const double *upper, const double *X0, int K, int loss, double f_scale, double ftol, double xtol, double gtol,
-                  int64_t max_nfev, alp_lm_t **out) {
+// alp_lm_create and, with `weight_rows`, alp_lm_create_rows
+int lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+              const double *upper, const double *X0, int K, int loss, double f_scale, double ftol, double xtol, double gtol,
+              int64_t max_nfev, bool weight_rows, alp_lm_t **out) {
     if (int rc = require_init()) return rc;
     ALP_REQUIRE(out, "out is NULL");
     *out = nullptr;
@@ -161,8 +159,12 @@ int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_
     ALP_REQUIRE(!(ftol != ftol) && !(xtol != xtol) && !(gtol != gtol), "a tolerance is NaN");
     for (int i = 0; i < D; ++i) ALP_REQUIRE(!(lower[i] != lower[i]) && !(upper[i] != upper[i]) && lower[i] <= upper[i], "bounds must satisfy lower <= upper");
     if (!pts->uo) return fail(ALP_ESTATE, "alp_lm_create: observed uv not set");
+    if (weight_rows && !pts->wt) return fail(ALP_ESTATE, "alp_lm_create_rows: no weight table set");
+    if (weight_rows && pts->wt_rows != K)
+        return fail(ALP_EINVAL, "alp_lm_create_rows: the weight table has %d rows, the loop %d starts: start k runs under row k", pts->wt_rows, K);
     alp_lm *h = new alp_lm();
     h->pts = pts;
+    h->weight_rows = weight_rows;
     h->loss = loss;
     h->f_scale = f_scale;
     memset(&h->a, 0, sizeof(h->a));
@@ -213,6 +215,22 @@ int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_
     return ALP_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                  const double *upper, const double *X0, int K, int loss, double f_scale, double ftol, double xtol, double gtol,
+                  int64_t max_nfev, alp_lm_t **out) {
+    return lm_create(pts, tmpl, target_idx, D, lower, upper, X0, K, loss, f_scale, ftol, xtol, gtol, max_nfev, false, out);
+}
+
+int alp_lm_create_rows(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                       const double *upper, const double *X0, int K, int loss, double f_scale, double ftol, double xtol, double gtol,
+                       int64_t max_nfev, alp_lm_t **out) {
+    return lm_create(pts, tmpl, target_idx, D, lower, upper, X0, K, loss, f_scale, ftol, xtol, gtol, max_nfev, true, out);
+}
+
 int alp_lm_destroy(alp_lm_t *h) {
     if (!h) return ALP_OK;
     if (ctx().ready) hipStreamSynchronize(ctx().stream);
@@ -233,11 +251,13 @@ int alp_lm_run(alp_lm_t *h, int64_t rounds) {
     ALP_REQUIRE(rounds >= 0, "rounds is negative");
     alp_points *p = h->pts;
     if (!p) return fail(ALP_ESTATE, "alp_lm_run: the point set of this device loop has been destroyed");
+    if (h->weight_rows && p->wt_rows != h->a.K)
+        return fail(ALP_ESTATE, "alp_lm_run: the weight table of the point set no longer has the loop's %d rows", (int)h->a.K);
     if (rounds == 0) return ALP_OK;
     h->pending = true;                   // from the first launch on: a failure below still needs alp_lm_wait
     for (int64_t r = 0; r < rounds; ++r) {
         if (int rc = normal_listed_launch(p, h->plans, h->list, h->count, h->running, h->a.K, h->a.cfg.D, h->grid, h->loss, h->f_scale,
-                                          h->partials, h->sums))
+                                          h->partials, h->sums, h->weight_rows))
             return rc;
         if (int rc = launch_step_select(h, 1)) return rc;
     }

@@ -953,6 +953,130 @@ __global__ __launch_bounds__(256) void reduce_normal_listed_kernel(const double 
     if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = n_local;
 }
 
+// ------------------------------------------------------------------ K3n under the rows of a weight table
+// alp_points_set_weight_table: R rows of n weights of the set's element type, row r at table + r * n.  The kernels below are
+// normal_batch_kernel and normal_batch_listed_kernel with the weight plane replaced by the pose's row: the same grid, the same
+// stripes, normal_body<TS, LOSS, true> on the row -- a result row depends on its pose, its weight row and the stripes alone
+// and has the bits alp_points_set_weights(row) + the unlisted kernel give.  The row index is the same in every lane (it comes
+// in by a scalar load, like the plan).
+template <typename TS, int LOSS>
+__global__ __launch_bounds__(256) void normal_batch_rows_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+                                                                const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
+                                                                int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
+                                                                int pose_in_x, double *__restrict__ partials, const TS *__restrict__ table,
+                                                                const int *__restrict__ row_of_pose) {
+    const int pose = pose_in_x ? blockIdx.x : blockIdx.y, stripe = pose_in_x ? blockIdx.y : blockIdx.x;
+    const int stripes = pose_in_x ? gridDim.y : gridDim.x;
+    normal_body<TS, LOSS, true>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
+                                (int64_t)pose * stripes + stripe, table + (int64_t)row_of_pose[pose] * n);
+}
+
+// the device loop's form (alp_lm_create_rows): start k runs under row k of a table of K rows
+template <typename TS, int LOSS>
+__global__ __launch_bounds__(256) void normal_batch_listed_rows_kernel(const TS *__restrict__ x, const TS *__restrict__ y,
+                                                                       const TS *__restrict__ z, const TS *__restrict__ uo,
+                                                                       const TS *__restrict__ vo, int64_t n, int64_t groups_per,
+                                                                       double inv_f_scale, const JacPlan *__restrict__ plans,
+                                                                       const int *__restrict__ list, const long long *__restrict__ count,
+                                                                       double *__restrict__ partials, const TS *__restrict__ table) {
+    if ((long long)blockIdx.x >= *count) return;
+    const int pose = list[blockIdx.x], stripe = blockIdx.y, stripes = gridDim.y;
+    normal_body<TS, LOSS, true>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
+                                (int64_t)pose * stripes + stripe, table + (int64_t)pose * n);
+}
+
+// reduce_normal_batch_kernel (running == NULL) and reduce_normal_listed_kernel (running[q] != 0: start q still runs) for those
+// two: the same order of additions, and the count slot of row q is the local sum of ITS weight row,
+// row_sums[row_of_pose ? row_of_pose[q] : q], instead of one scalar for every row.
+__global__ __launch_bounds__(256) void reduce_normal_rows_kernel(const double *__restrict__ partials, int stripes, int T,
+                                                                 const double *__restrict__ row_sums, const int *__restrict__ row_of_pose,
+                                                                 const int *__restrict__ running, double *__restrict__ sums) {
+    __shared__ double s[8][32];
+    const int cl = threadIdx.x & 31;
+    const int g = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cl;
+    const double *rows = partials + (int64_t)blockIdx.y * stripes * T;
+    double *out = sums + (int64_t)blockIdx.y * (T + 1);
+    const bool live = running ? running[blockIdx.y] != 0 : true;        // the same in every lane
+    double acc = 0.0;
+    if (c < T && live)
+        for (int b = g; b < stripes; b += 8) acc += rows[(int64_t)b * T + c];
+    s[g][cl] = acc;
+    __syncthreads();
+    if (g == 0 && c < T) {
+        double t = s[0][cl];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) t += s[k][cl];
+        out[c] = t;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = row_sums[row_of_pose ? row_of_pose[blockIdx.y] : (int)blockIdx.y];
+}
+
+// W[r] = the float64 sum of row r of a weight table, without atomics and in an order that depends on the row length alone.
+// Workgroup (c, r) adds the values [c * chunk, min((c + 1) * chunk, len)) of row r of `src` (rows `row_stride` apart): lane t takes
+// every 256th value from t on in index order, then the 256 lane sums fold pairwise (t += t + 128, t + 64, .. t + 1) -> out[r * gridDim.x + c].
+// A table is summed in two launches: chunks of WT_SUM_CHUNK weights into partial sums (TIn = the set's element type), then the
+// partial sums of a row as ONE chunk (TIn = double); a row of at most one chunk needs the first alone.
+constexpr int64_t WT_SUM_CHUNK = 16384;
+template <typename TIn>
+__global__ __launch_bounds__(256) void weight_table_sums_kernel(const TIn *__restrict__ src, int64_t row_stride, int64_t len, int64_t chunk,
+                                                                double *__restrict__ out) {
+    __shared__ double s[256];
+    const int tid = threadIdx.x;
+    const int64_t beg = (int64_t)blockIdx.x * chunk;
+    const int64_t end = beg + chunk < len ? beg + chunk : len;
+    const TIn *row = src + (int64_t)blockIdx.y * row_stride;
+    double acc = 0.0;
+    for (int64_t i = beg + tid; i < end; i += 256) acc += (double)row[i];
+    s[tid] = acc;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if (tid < m) s[tid] += s[tid + m];
+        __syncthreads();
+    }
+    if (tid == 0) out[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
+}
+
+// ------------------------------------------------------------------ K3a: held-out residuals, one pose per POINT
+// out[i] = (uo_i - u, vo_i - v) of point i under poses[assign[i]], a NaN pair where assign[i] < 0 (alp_residuals_assigned: the
+// residual of every point under the model that was fitted without it).  K3's float64 arithmetic -- project_norm / to_pixels on
+// the pose record, the planes widened on load -- so that on a float64 set the pair has the bits of row assign[i] of
+// residual_batch_kernel's output.  The pose differs from lane to lane: the record comes in by vector loads, from LDS when
+// the B records fit (B <= RA_LDS_POSES = 128: 33 KB, two workgroups a CU and more), from global memory otherwise.  In LDS a
+// record takes RA_STRIDE = 33 doubles = 66 dwords: lanes that read the same word of different poses start 2 banks apart per
+// pose (a stride of 32 doubles would put every pose on the same banks).  Lane t of a pass takes point base + t: the loads of
+// the planes and of `assign` and the 16-byte stores are contiguous across the wave.  The host has checked assign[i] < B.
+constexpr int RA_LDS_POSES = 128;
+constexpr int RA_STRIDE = POSE_WORDS + 1;
+template <typename TS, bool IN_LDS>
+__global__ __launch_bounds__(256) void residuals_assigned_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+                                                                 const TS *__restrict__ uo, const TS *__restrict__ vo,
+                                                                 const int *__restrict__ assign, double2 *__restrict__ out, int64_t n,
+                                                                 const PoseRec<double> *__restrict__ poses, int B) {
+    __shared__ double s_rec[IN_LDS ? RA_LDS_POSES * RA_STRIDE : 1];
+    if constexpr (IN_LDS) {
+        for (int t = threadIdx.x; t < B * POSE_WORDS; t += blockDim.x)
+            s_rec[(t / POSE_WORDS) * RA_STRIDE + (t % POSE_WORDS)] = poses[t / POSE_WORDS].v[t % POSE_WORDS];
+        __syncthreads();
+    }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int a = assign[i];
+        double du = __builtin_nan(""), dv = du;
+        if (a >= 0) {
+            const double *r;
+            if constexpr (IN_LDS) r = s_rec + a * RA_STRIDE;
+            else r = poses[a].v;
+            double xd, yd, u, v;
+            project_norm<double>(r, (double)x[i], (double)y[i], (double)z[i], xd, yd);
+            to_pixels<double>(r, xd, yd, u, v);
+            du = (double)uo[i] - u;
+            dv = (double)vo[i] - v;
+        }
+        Num<double>::nt_store(make_double2(du, dv), out + i);
+    }
+}
+
 // TS = element type of the planes in HBM, T = arithmetic type (TS = float with T = double is the
 // float64 re-evaluation of a float32 point set: alp_eval_population's argmin confirmation)
 // WEIGHTED: the weight plane `wts` is read beside uo / vo, at the same index (the masked lanes' stand-in index included, whose

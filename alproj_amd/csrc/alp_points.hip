@@ -6,6 +6,8 @@
 //   jacobian_kernel  d projected / d parameters for one pose, exact (least-squares path)
 //   normal_kernel    the same rows contracted to J^T J, J^T r and the cost where they are made (f64 MFMA; least-squares path)
 //   normal_batch_kernel  the same for B poses in one launch, one workgroup per (stripe, pose) pair
+//   normal_batch_rows_kernel  the same with every pose under a row of the set's weight table (alp_points_set_weight_table)
+//   residuals_assigned_kernel  observed - projected with the pose chosen per point (held-out residuals of a cross-validation)
 //
 // Reference arithmetic: src/alproj/optimize.py  project :122-155, _distort :98-120,
 // rmse :157-178, huber_loss :181-212, compute_residuals :215-237, and the generation loop
@@ -469,6 +471,32 @@ int residuals_impl(alp_points *p, const double *cand, int64_t B, double *out) {
     });
 }
 
+// alp_residuals_assigned: float64 records of the B poses, then per chunk of points the assignments in and the pairs out
+template <typename TS>
+int residuals_assigned_impl(alp_points *p, const double *cand, int64_t B, const int32_t *assign, double *out) {
+    const size_t rec_bytes = round_up((int64_t)(B * sizeof(PoseRec<double>)), 256);
+    const int64_t chunk = host::stage_chunk_points(p->n, 1);
+    const size_t idx_bytes = round_up(chunk * 4, 256);
+    char *dev = nullptr;
+    if (int rc = scratch_reserve(rec_bytes + idx_bytes + (size_t)chunk * sizeof(double2), (void **)&dev)) return rc;
+    PoseRec<double> *poses_dev = (PoseRec<double> *)dev;
+    int *assign_dev = (int *)(dev + rec_bytes);
+    double2 *res_dev = (double2 *)(dev + rec_bytes + idx_bytes);
+    std::vector<PoseRec<double>> poses((size_t)B);
+    for (int64_t b = 0; b < B; ++b) fold_pose_t<double>(cand + b * ALP_NPARAM, p->origin, &poses[b]);
+    hipStream_t st = ctx().stream;
+    ALP_HIP(hipMemcpyAsync(poses_dev, poses.data(), (size_t)B * sizeof(PoseRec<double>), hipMemcpyHostToDevice, st));
+    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, const int *, double2 *, int64_t, const PoseRec<double> *, int);
+    const Kernel kernel = B <= RA_LDS_POSES ? residuals_assigned_kernel<TS, true> : residuals_assigned_kernel<TS, false>;
+    return staged_chunks(p->n, chunk, [&](int64_t off, int64_t cnt) {
+        if (hipMemcpyAsync(assign_dev, assign + off, (size_t)cnt * 4, hipMemcpyHostToDevice, st) != hipSuccess) return;      // (hipGetLastError reports it)
+        hipLaunchKernelGGL(kernel, dim3(stream_grid(cnt)), dim3(256), 0, st, (const TS *)p->x + off, (const TS *)p->y + off, (const TS *)p->z + off, (const TS *)p->uo + off,
+                           (const TS *)p->vo + off, (const int *)assign_dev, res_dev, cnt, (const PoseRec<double> *)poses_dev, (int)B);
+    }, [&](int64_t off, int64_t cnt) {
+        return hipMemcpyAsync(out + 2 * off, res_dev, (size_t)cnt * sizeof(double2), hipMemcpyDeviceToHost, st);
+    });
+}
+
 // alp_jacobian: chunks of whole points (a chunk's rows are one contiguous block of the output: one copy each)
 template <typename TS>
 int jacobian_impl(alp_points *p, const JacPlan &plan, double *out) {
@@ -530,9 +558,14 @@ int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, do
 // and the sums.  ALP_NORMAL_BATCH_ORDER = "stripe" | "pose" (a development switch, tools/probe_normal_batch.py) names the grid
 // index that runs fastest; the sums do not depend on it.
 template <typename TS>
-int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss, double f_scale, double *out) {
+int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss, double f_scale, double *out,
+                      const int32_t *row_of_pose = nullptr) {
     using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, int, double *,
                             const TS *);
+    using RowsKernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, int,
+                                double *, const TS *, const int *);
+    static const RowsKernel rows_kernels[4] = {normal_batch_rows_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_rows_kernel<TS, ALP_NORMAL_SOFT_L1>,
+                                               normal_batch_rows_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_rows_kernel<TS, ALP_NORMAL_CAUCHY>};
     static const Kernel kernels[2][4] = {{normal_batch_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1>,
                                           normal_batch_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_kernel<TS, ALP_NORMAL_CAUCHY>},
                                          {normal_batch_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
@@ -540,10 +573,12 @@ int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss
     const int64_t B = (int64_t)plans.size();
     const int D = plans[0].D, T = D * (D + 1) / 2 + D + 1;
     const host::NormalGrid g = host::normal_batch_grid(p->n, B, ctx().cu_count);
-    const size_t plan_bytes = round_up((int64_t)(B * sizeof(JacPlan)), 256);
+    // (behind the plans, on the row path: the B row indices)
+    const size_t plan_bytes = round_up((int64_t)(B * sizeof(JacPlan)), 256) + (row_of_pose ? round_up(B * 4, 256) : 0);
     char *dev = nullptr;
     if (int rc = scratch_reserve(plan_bytes + ((size_t)B * g.blocks * T + (size_t)B * (T + 1)) * sizeof(double), (void **)&dev)) return rc;
     JacPlan *plans_dev = (JacPlan *)dev;
+    int *rows_dev = (int *)(dev + round_up((int64_t)(B * sizeof(JacPlan)), 256));
     double *partials = (double *)(dev + plan_bytes), *sums = partials + (size_t)B * g.blocks * T;
     hipStream_t st = ctx().stream;
     if (g.blocks > 0) {
@@ -551,15 +586,24 @@ int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss
         const int pose_in_x = order ? !strcmp(order, "pose") : NORMAL_BATCH_POSE_IN_X;
         const dim3 grid = pose_in_x ? dim3((unsigned)B, (unsigned)g.blocks) : dim3((unsigned)g.blocks, (unsigned)B);
         ALP_HIP(hipMemcpyAsync(plans_dev, plans.data(), (size_t)B * sizeof(JacPlan), hipMemcpyHostToDevice, st));
+        if (row_of_pose) ALP_HIP(hipMemcpyAsync(rows_dev, row_of_pose, (size_t)B * 4, hipMemcpyHostToDevice, st));
         ktime_begin();
-        hipLaunchKernelGGL(kernels[p->w != nullptr][loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
-                           (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials, (const TS *)p->w);
-        hipLaunchKernelGGL(reduce_normal_batch_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)B), dim3(256), 0, st, partials, g.blocks, T,
-                           p->count_slot(), sums);
+        if (row_of_pose) {
+            hipLaunchKernelGGL(rows_kernels[loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
+                               (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials,
+                               (const TS *)p->wt, (const int *)rows_dev);
+            hipLaunchKernelGGL(reduce_normal_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)B), dim3(256), 0, st, (const double *)partials,
+                               g.blocks, T, (const double *)p->wt_sums, (const int *)rows_dev, (const int *)nullptr, sums);
+        } else {
+            hipLaunchKernelGGL(kernels[p->w != nullptr][loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
+                               (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials, (const TS *)p->w);
+            hipLaunchKernelGGL(reduce_normal_batch_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)B), dim3(256), 0, st, partials, g.blocks, T,
+                               p->count_slot(), sums);
+        }
         ktime_end();
         ALP_HIP(hipGetLastError());
     } else {
-        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)B * (T + 1) * sizeof(double), st));   // an empty shard still joins the all-reduce
+        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)B * (T + 1) * sizeof(double), st));   // an empty shard still joins the all-reduce (a row of no weights sums to 0)
     }
     if (int rc = comm_allreduce_sum_f64(sums, B * (T + 1))) return rc;
     ALP_HIP(hipMemcpyAsync(out, sums, (size_t)B * (T + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -571,7 +615,12 @@ int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss
 // starts, reduce_normal_listed_kernel, one all-reduce of K (T + 1) doubles.  Enqueue only; the buffers are the loop's own.
 template <typename TS>
 int normal_listed_impl(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
-                       const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums) {
+                       const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums, bool weight_rows) {
+    using RowsKernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, const int *,
+                                const long long *, double *, const TS *);
+    static const RowsKernel rows_kernels[4] = {
+        normal_batch_listed_rows_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_listed_rows_kernel<TS, ALP_NORMAL_SOFT_L1>,
+        normal_batch_listed_rows_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_listed_rows_kernel<TS, ALP_NORMAL_CAUCHY>};
     using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, const int *,
                             const long long *, double *, const TS *);
     static const Kernel kernels[2][4] = {
@@ -581,7 +630,14 @@ int normal_listed_impl(alp_points *p, const JacPlan *plans, const int *list, con
          normal_batch_listed_kernel<TS, ALP_NORMAL_HUBER, true>, normal_batch_listed_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
     const int T = D * (D + 1) / 2 + D + 1;
     hipStream_t st = ctx().stream;
-    if (g.blocks > 0) {
+    if (g.blocks > 0 && weight_rows) {
+        hipLaunchKernelGGL(rows_kernels[loss], dim3((unsigned)K, (unsigned)g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
+                           (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, list, count, partials,
+                           (const TS *)p->wt);
+        hipLaunchKernelGGL(reduce_normal_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)K), dim3(256), 0, st, (const double *)partials,
+                           g.blocks, T, (const double *)p->wt_sums, (const int *)nullptr, running, sums);
+        ALP_HIP(hipGetLastError());
+    } else if (g.blocks > 0) {
         hipLaunchKernelGGL(kernels[p->w != nullptr][loss], dim3((unsigned)K, (unsigned)g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
                            (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, list, count, partials,
                            (const TS *)p->w);
@@ -598,9 +654,9 @@ int normal_listed_impl(alp_points *p, const JacPlan *plans, const int *list, con
 
 namespace alp {
 int normal_listed_launch(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
-                         const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums) {
-    return p->precision == ALP_F64 ? normal_listed_impl<double>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums)
-                                   : normal_listed_impl<float>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums);
+                         const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums, bool weight_rows) {
+    return p->precision == ALP_F64 ? normal_listed_impl<double>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums, weight_rows)
+                                   : normal_listed_impl<float>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums, weight_rows);
 }
 int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched,
                    const double *params_dev) {
@@ -736,6 +792,63 @@ int set_weights_t(alp_points *p, const void *w, int in_dtype) {
     return ALP_OK;
 }
 
+// alp_points_set_weight_table: validate everything (nothing of the set has changed until then), build the new table beside
+// the old one -- the rows rounded to T in chunks of at most WT_STAGE values on the host, the row sums by
+// weight_table_sums_kernel -- and only then let it take the old one's place.
+constexpr int64_t WT_STAGE = (int64_t)8 << 20;
+
+template <typename T>
+int weight_table_sums_launch(const T *table, int64_t n, int R, double *sums) {
+    hipStream_t st = ctx().stream;
+    if (n == 0) {
+        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)R * sizeof(double), st));
+        return ALP_OK;
+    }
+    const int64_t C = (n + WT_SUM_CHUNK - 1) / WT_SUM_CHUNK;
+    double *partials = sums;
+    if (C > 1)
+        if (int rc = scratch_reserve((size_t)R * C * sizeof(double), (void **)&partials)) return rc;
+    hipLaunchKernelGGL(weight_table_sums_kernel<T>, dim3((unsigned)C, (unsigned)R), dim3(256), 0, st, table, n, n, WT_SUM_CHUNK, partials);
+    if (C > 1)
+        hipLaunchKernelGGL(weight_table_sums_kernel<double>, dim3(1, (unsigned)R), dim3(256), 0, st, (const double *)partials, C, C, C, sums);
+    ALP_HIP(hipGetLastError());
+    return ALP_OK;
+}
+
+template <typename TIn, typename T>
+int set_weight_table_t(alp_points *p, const void *w, int R) {
+    const TIn *src = (const TIn *)w;
+    const int64_t n = p->n, total = (int64_t)R * n;
+    for (int64_t i = 0; i < total; ++i) {
+        const double v = (double)src[i];
+        if (!(v >= 0.0) || !std::isfinite(v))
+            return fail(ALP_EINVAL, "alp_points_set_weight_table: weight %lld of row %lld is negative, NaN or infinite", (long long)(i % n),
+                        (long long)(i / n));
+        if (!std::isfinite((double)(T)v))
+            return fail(ALP_EINVAL, "alp_points_set_weight_table: weight %lld of row %lld does not fit the set's element type", (long long)(i % n),
+                        (long long)(i / n));
+    }
+    const size_t table_bytes = (size_t)round_up((total > 0 ? total : 1) * (int64_t)sizeof(T), 256);
+    DeviceBuffer<> fresh;
+    if (int rc = fresh.reserve(table_bytes + (size_t)R * sizeof(double))) return rc;
+    T *table = (T *)fresh;
+    double *sums = (double *)((char *)table + table_bytes);
+    hipStream_t st = ctx().stream;
+    std::vector<T> stage((size_t)(total < WT_STAGE ? total : WT_STAGE));
+    for (int64_t off = 0; off < total; off += WT_STAGE) {
+        const int64_t cnt = total - off < WT_STAGE ? total - off : WT_STAGE;
+        for (int64_t i = 0; i < cnt; ++i) stage[(size_t)i] = (T)(double)src[off + i];
+        ALP_HIP(hipMemcpyAsync(table + off, stage.data(), (size_t)cnt * sizeof(T), hipMemcpyHostToDevice, st));
+        ALP_HIP(hipStreamSynchronize(st));      // `stage` is rewritten by the next chunk
+    }
+    if (int rc = weight_table_sums_launch<T>(table, n, R, sums)) return rc;
+    ALP_HIP(hipStreamSynchronize(st));          // nothing enqueued reads the old table any more either
+    p->wt = std::move(fresh);
+    p->wt_rows = R;
+    p->wt_sums = sums;
+    return ALP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -856,6 +969,39 @@ int alp_points_weight_sum(const alp_points_t *p, double *W) {
     return ALP_OK;
 }
 
+int alp_points_set_weight_table(alp_points_t *p, const void *w, int R, int in_dtype) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p, "points handle is NULL");
+    if (p->pending_P > 0 || p->loop_pending)
+        return fail(ALP_ESTATE, "alp_points_set_weight_table: an evaluation or a device loop on this point set has not been waited for");
+    for (alp_lm_t *h : p->lm_loops)
+        if (lm_loop_pending(h))
+            return fail(ALP_ESTATE, "alp_points_set_weight_table: a least-squares device loop on this point set has not been waited for");
+    if (!w) {
+        if (p->wt) ALP_HIP(hipStreamSynchronize(ctx().stream));
+        p->wt.reset();
+        p->wt_rows = 0;
+        p->wt_sums = nullptr;
+        return ALP_OK;
+    }
+    ALP_REQUIRE(in_dtype == ALP_F32 || in_dtype == ALP_F64, "in_dtype must be ALP_F32 or ALP_F64");
+    ALP_REQUIRE(R >= 1 && R <= host::NORMAL_BATCH_MAX, "R must be 1..1024");
+    if ((int64_t)R * p->n * (int64_t)p->esize() > ALP_WEIGHT_TABLE_MAX_BYTES)
+        return fail(ALP_EINVAL, "alp_points_set_weight_table: %d rows of %lld weights exceed ALP_WEIGHT_TABLE_MAX_BYTES", R, (long long)p->n);
+    if (p->precision == ALP_F64)
+        return in_dtype == ALP_F64 ? set_weight_table_t<double, double>(p, w, R) : set_weight_table_t<float, double>(p, w, R);
+    return in_dtype == ALP_F64 ? set_weight_table_t<double, float>(p, w, R) : set_weight_table_t<float, float>(p, w, R);
+}
+
+int alp_points_weight_table_sums(alp_points_t *p, double *out) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p && out, "NULL argument");
+    if (!p->wt) return fail(ALP_ESTATE, "alp_points_weight_table_sums: no weight table set");
+    ALP_HIP(hipMemcpyAsync(out, p->wt_sums, (size_t)p->wt_rows * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
+    ALP_HIP(hipStreamSynchronize(ctx().stream));
+    return ALP_OK;
+}
+
 int alp_project(alp_points_t *p, const double params[ALP_NPARAM]) {
     if (int rc = require_init()) return rc;
     ALP_REQUIRE(p && params, "NULL argument");
@@ -929,6 +1075,19 @@ int alp_residuals_batch(alp_points_t *p, const double *cand, int64_t B, double *
     return p->precision == ALP_F64 ? residuals_impl<double>(p, cand, B, out) : residuals_impl<float>(p, cand, B, out);
 }
 
+int alp_residuals_assigned(alp_points_t *p, const double *cand, int64_t B, const int32_t *assign, double *out) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p && cand, "NULL argument");
+    ALP_REQUIRE(B >= 1 && B <= 4096, "B out of range");
+    if (!p->uo) return fail(ALP_ESTATE, "alp_residuals_assigned: observed uv not set");
+    if (p->n == 0) return ALP_OK;
+    ALP_REQUIRE(assign && out, "NULL argument");
+    for (int64_t i = 0; i < p->n; ++i)          // before the launch: the kernel indexes the records with it
+        if (assign[i] >= B) return fail(ALP_EINVAL, "alp_residuals_assigned: assign[%lld] = %d names no pose of the %lld", (long long)i, (int)assign[i], (long long)B);
+    return p->precision == ALP_F64 ? residuals_assigned_impl<double>(p, cand, B, assign, out)
+                                   : residuals_assigned_impl<float>(p, cand, B, assign, out);
+}
+
 int alp_jacobian(alp_points_t *p, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int of_residuals,
                  double *out) {
     if (int rc = require_init()) return rc;
@@ -965,6 +1124,26 @@ int alp_normal_equations_batch(alp_points_t *p, const double *params, int64_t B,
     if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations_batch: observed uv not set");
     return p->precision == ALP_F64 ? normal_batch_impl<double>(p, plans, loss, f_scale, out)
                                    : normal_batch_impl<float>(p, plans, loss, f_scale, out);
+}
+
+int alp_normal_equations_batch_rows(alp_points_t *p, const double *params, int64_t B, const int32_t *row_of_pose, const int32_t *target_idx,
+                                    int D, int loss, double f_scale, double *out) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(p && params && out && row_of_pose, "NULL argument");
+    ALP_REQUIRE(B >= 1 && B <= host::NORMAL_BATCH_MAX, "B must be 1..1024");
+    ALP_REQUIRE(loss >= ALP_NORMAL_LINEAR && loss <= ALP_NORMAL_CAUCHY, "unknown loss");
+    ALP_REQUIRE(f_scale > 0 && std::isfinite(f_scale), "f_scale must be a positive finite number");
+    std::vector<JacPlan> plans((size_t)B);
+    for (int64_t b = 0; b < B; ++b)
+        if (int rc = jacobian_plan(params + b * ALP_NPARAM, p->origin, target_idx, D, 1, &plans[(size_t)b])) return rc;
+    if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations_batch_rows: observed uv not set");
+    if (!p->wt) return fail(ALP_ESTATE, "alp_normal_equations_batch_rows: no weight table set");
+    for (int64_t b = 0; b < B; ++b)             // before the launch: the kernel indexes the table with it
+        if (row_of_pose[b] < 0 || row_of_pose[b] >= p->wt_rows)
+            return fail(ALP_EINVAL, "alp_normal_equations_batch_rows: row_of_pose[%lld] = %d is no row of the table of %d", (long long)b,
+                        (int)row_of_pose[b], p->wt_rows);
+    return p->precision == ALP_F64 ? normal_batch_impl<double>(p, plans, loss, f_scale, out, row_of_pose)
+                                   : normal_batch_impl<float>(p, plans, loss, f_scale, out, row_of_pose);
 }
 
 // obs_b / prj_b NULL: that array is interleaved (n x 2 row-major); else a = the u column, b = the v column

@@ -28,6 +28,12 @@ struct alp_points {
     alp::DeviceBuffer<> w;
     double w_sum = 0;
     double count_slot() const { return w ? w_sum : (double)n; }
+    // the weight table (alp_points_set_weight_table): wt_rows rows of n weights of the set's element type, row r at r * n, and
+    // behind them (256-byte aligned) the wt_rows float64 row sums the device formed -- one allocation, NULL = no table.
+    // Independent of the plane above: a call that names table rows ignores `w`, every other call ignores the table.
+    alp::DeviceBuffer<> wt;
+    int wt_rows = 0;
+    double *wt_sums = nullptr;
     // population-evaluation scratch
     int64_t cand_cap = 0;
     alp::DeviceBuffer<> cand_dev;
@@ -88,7 +94,9 @@ bool lm_loop_pending(const alp_lm_t *h);
 // ascending order; running[k] != 0 for exactly those) under plans[k], over the fixed grid `g` = host::normal_batch_grid(n, K, cus):
 // sums = K rows of T + 1 doubles in alp_normal_equations_batch's layout, zeros (and the point count) for a start that is not
 // listed; all-reduced when a communicator exists.  partials: K * g.blocks * T doubles.  Enqueue only.
+// `weight_rows` (alp_lm_create_rows): start k under row k of the set's weight table (the caller has checked that it has K rows),
+// the count slot of row k = that row's sum.
 int normal_listed_launch(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
-                         const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums);
+                         const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums, bool weight_rows = false);
 
 }  // namespace alp

@@ -12,6 +12,7 @@ here                          reference                                device en
 ``bounds_to_array``           optimize.py:249-276                      (host, D <= 21 scalars)
 ``CMAOptimizer.optimize``     optimize.py:359-439                      alp_eval_population, alp_cma_*
 ``LsqOptimizer.optimize``     optimize.py:467-539                      alp_residuals; method="normal": alp_normal_equations(_batch)
+``LsqOptimizer.cross_validate`` / ``.bootstrap``  (none: held-out error, parameter spread)  alp_normal_equations_batch_rows, alp_residuals_assigned
 ``parameter_covariance``      (none: standard errors of a fit)         alp_jacobian, alp_residuals; "normal": alp_normal_equations
 ``intrinsic_mat`` etc.        optimize.py:8-96                         (host, 3x3 / 4x4)
 ============================  =======================================  ======================
@@ -33,7 +34,7 @@ import pandas as pd
 from scipy.optimize import least_squares
 from tqdm import tqdm
 
-from . import _lib
+from . import _lib, resample
 from .cma import CMA
 
 __all__ = ["intrinsic_mat", "extrinsic_mat", "project", "rmse", "huber_loss",
@@ -664,12 +665,14 @@ def normal_lm(fun, x0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfe
         return stop.value
 
 
-def normal_lm_batch(fun, X0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None):
+def normal_lm_batch(fun, X0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None, indexed=False):
     """K runs of ``normal_lm`` in lockstep.  ``fun(X (k, D)) -> (G (k, D, D), g (k, D), cost (k,))``, row by row what
     ``normal_lm``'s ``fun`` returns -- ``Points.normal_equations_batch`` on the device.  ``X0`` (K, D): the starts; bounds,
     tolerances and ``max_nfev`` (per start) as for ``normal_lm``.  A round: every start that has not stopped advances to its
     next trial point, and all of them go to ``fun`` in one call, in start order; a start that has stopped drops out of the
-    later calls.  Every start does the arithmetic of ``normal_lm`` run alone on its rows.  Returns the K result dicts in start
+    later calls.  Every start does the arithmetic of ``normal_lm`` run alone on its rows.  ``indexed=True``: ``fun`` is called
+    as ``fun(X, starts)`` with the (k,) indices of the starts whose trial points the rows of X are -- for a ``fun`` whose
+    problem differs from start to start (``Points.normal_equations_batch_rows``).  Returns the K result dicts in start
     order."""
     X0 = np.asarray(X0, dtype=np.float64)
     if X0.ndim != 2:
@@ -679,7 +682,8 @@ def normal_lm_batch(fun, X0, lower, upper, ftol=1e-10, xtol=1e-10, gtol=1e-10, m
     pending = {k: next(run) for k, run in enumerate(runs)}        # the first yield needs no input and always comes
     while pending:
         order = sorted(pending)
-        G, g, cost = fun(np.array([pending[k] for k in order], dtype=np.float64))
+        X = np.array([pending[k] for k in order], dtype=np.float64)
+        G, g, cost = fun(X, np.array(order, dtype=np.int32)) if indexed else fun(X)
         for row, k in enumerate(order):
             try:
                 pending[k] = runs[k].send((G[row], g[row], cost[row]))
@@ -874,6 +878,172 @@ class LsqOptimizer(BaseOptimizer):
         b = best_start([r["cost"] for r in runs])
         self.result_ = dict(self.start_results[b][2], start=b)
         return self.start_results[b][0], self.start_results[b][1]
+
+    # -- K fits under K weight rows: cross-validation and bootstrap ---------------------------
+    _RESULT_KEYS = ("cost", "iterations", "evaluations", "status", "grad_norm")
+
+    def _resample_checks(self, loss, f_scale, device_loop, check_every):
+        """the refusals cross_validate and bootstrap share with optimize(method="normal"): host arithmetic"""
+        if device_loop and (isinstance(check_every, (bool, np.bool_)) or not isinstance(check_every, (int, np.integer)) or check_every < 1):
+            raise ValueError("check_every must be a positive integer")
+        _lib.normal_loss_check(loss, f_scale)
+        return _jacobian_targets(self.target_params)
+
+    def _shard(self, world, seed):
+        """(lo, hi, n_global, seed): this rank's columns [lo, hi) of the global index range -- the shards lie in rank order,
+        their sizes come from one comm_allgather -- and the seed every rank uses: rank 0's (its own entropy for None)"""
+        n = len(self.obj_points)
+        if world == 1:
+            return 0, n, n, seed
+        rank, _ = _lib.comm_info()
+        sizes = _lib.comm_allgather(np.array([n], dtype=np.int64))
+        s = np.array([np.random.SeedSequence().entropy % (1 << 63) if seed is None else int(seed)], dtype=np.uint64)
+        _lib.comm_bcast(s, root=0)
+        lo = int(sizes[:rank].sum())
+        return lo, lo + n, int(sizes.sum()), int(s[0])
+
+    def _global_weights(self, lo, hi, n_global):
+        """(n_global,) float64: the constructor's weights (ones without) in this rank's columns, zeros elsewhere"""
+        w = np.zeros(n_global, dtype=np.float64)
+        w[lo:hi] = 1.0 if self.weights is None else self.weights
+        return w
+
+    def _fit_rows(self, pts, table, cols, bounds, world, loss, f_scale, ftol, xtol, gtol, max_nfev, device_loop, check_every):
+        """K = len(table) fits from params_init in one lockstep, fit b under row b of ``table`` (uploaded here as the set's
+        weight table) -> (the K result dicts of normal_lm, finals (K, D)).  The host lockstep (normal_lm_batch on
+        Points.normal_equations_batch_rows) or, ``device_loop``, LmDevice(weight_rows=True)."""
+        K = len(table)
+        pts.set_weight_table(table)
+        X0 = np.ascontiguousarray(np.tile(np.clip(np.asarray(self.target_params_init, dtype=np.float64), bounds[:, 0], bounds[:, 1]), (K, 1)))
+        if device_loop:
+            with _lib.LmDevice(pts, _lib.params_vector(self.params_init), cols, bounds[:, 0], bounds[:, 1], X0, loss, f_scale, ftol, xtol,
+                               gtol, max_nfev, weight_rows=True) as loop:
+                pending = K
+                while pending:
+                    loop.run(int(check_every))
+                    pending = loop.wait()
+                rec = loop.get()
+            runs = [dict(x=rec["x"][k], cost=float(rec["cost"][k]), grad_norm=float(rec["grad_norm"][k]), iterations=int(rec["iterations"][k]),
+                         evaluations=int(rec["evaluations"][k]), status=int(rec["status"][k])) for k in range(K)]
+        else:
+            def sums_rows(X, starts):
+                return pts.normal_equations_batch_rows(self._candidate_matrix(X), starts, cols, loss, f_scale)[:3]
+
+            runs = normal_lm_batch(sums_rows, X0, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol, max_nfev=max_nfev, indexed=True)
+        finals = np.ascontiguousarray([r["x"] for r in runs], dtype=np.float64)
+        if world > 1:
+            _lib.comm_bcast(finals, root=0)
+        return runs, finals
+
+    def cross_validate(self, folds=5, seed=None, bound_widths=None, loss="linear", f_scale=1.0, ftol=1e-10, xtol=1e-10, gtol=1e-10,
+                       max_nfev=None, precision=None, device_loop=False, check_every=8):
+        """k-fold cross-validation of the ``method="normal"`` fit: how large is the reprojection error on points the fit has
+        not seen -- the held-out check-point accuracy -- and which point disagrees with the model fitted without it.
+
+        ``folds``: an integer k (2 <= k <= min(N, 1024): a permutation from ``np.random.default_rng(seed)`` dealt round-robin,
+        fold sizes differ by at most 1), ``"loo"`` (every point its own fold, at most 1024 points) or N explicit integer
+        labels (``resample.fold_labels``; with several ranks the labels of ALL points, in rank order).  The k fits start
+        from ``params_init`` and run in ONE lockstep: fit b sees the weights ``w_i [label_i != b]`` as row b of a weight
+        table on the device (``Points.set_weight_table``), and every round is one alp_normal_equations_batch_rows launch
+        over the folds that have not stopped -- or, ``device_loop=True``, the device loop of optimize(method="normal") with a
+        row per start.  The points are uploaded once.  Then one more such launch at the k optima under the held-out rows
+        ``w_i [label_i == b]`` with the linear loss gives every fold's held-out error, and one alp_residuals_assigned launch
+        every point's residual under the parameters fitted WITHOUT its fold.  ``bound_widths``, ``loss`` / ``f_scale``, the
+        tolerances, ``max_nfev``, ``precision``, ``device_loop`` and ``check_every`` as for optimize(method="normal"); the
+        constructor's ``weights`` multiply both tables.
+
+        Returns -- and keeps as ``self.cv_`` -- a dict: ``labels`` (N,) of this rank's points; ``fold_params`` (k parameter
+        dicts); ``fold_results`` (k dicts: cost, iterations, evaluations, status, grad_norm of the training fit, as in
+        ``start_results``); ``fold_rmse`` (k,): sqrt(sum w_i d_i^2 / sum w_i) over fold b's own points under fit b, from the
+        device's sums as sqrt(2 cost_b / W_b); ``rmse``: the same pooled over all points, sqrt(sum_b 2 cost_b / sum_b W_b);
+        ``residuals`` (N, 2) and ``distance`` (N,): the held-out residual pair (observed - projected) and its length for
+        this rank's points.  With several ranks the sums arrive all-reduced and rank 0's seed is everybody's.
+
+        ValueError, before the device is touched (with several ranks: before anything but the exchange of the shard sizes),
+        for ``folds`` out of range, a table above ``resample.WEIGHT_TABLE_MAX_BYTES``, targets w / h, an unknown loss, and
+        -- without a communicator -- a fold whose training weights are all zero."""
+        cols = self._resample_checks(loss, f_scale, device_loop, check_every)
+        bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
+        world = _lib.comm_world()
+        lo, hi, n_global, seed = self._shard(world, seed)
+        labels = resample.fold_labels(n_global, folds, seed)
+        k = int(labels.max()) + 1
+        precision = default_precision(hi - lo, precision)
+        resample.table_check(k, hi - lo, 4 if precision == "f32" else 8)                   # before the tables exist: they are O(k N)
+        train, held = resample.fold_tables(labels, self._global_weights(lo, hi, n_global), lo, hi)
+        resample.table_check(k, hi - lo, 4 if precision == "f32" else 8, train.sum(axis=1) if world == 1 else None)
+        pts = self._device_points(precision)
+        try:
+            runs, finals = self._fit_rows(pts, train, cols, bounds, world, loss, f_scale, ftol, xtol, gtol, max_nfev, device_loop, check_every)
+            cand = self._candidate_matrix(finals)
+            pts.set_weight_table(held)
+            _, _, cost, W = pts.normal_equations_batch_rows(cand, np.arange(k, dtype=np.int32), cols, "linear", 1.0)
+            res = pts.residuals_assigned(cand, labels[lo:hi]).reshape(-1, 2)
+        finally:
+            pts.close()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            fold_rmse = np.sqrt(2.0 * cost / W)
+            pooled = float(np.sqrt(2.0 * cost.sum() / W.sum()))
+        self.cv_ = dict(labels=labels[lo:hi].copy(), fold_params=[self._result_params(x) for x in finals],
+                        fold_results=[{key: r[key] for key in self._RESULT_KEYS} for r in runs], fold_rmse=fold_rmse, rmse=pooled,
+                        residuals=res, distance=np.hypot(res[:, 0], res[:, 1]))
+        return self.cv_
+
+    def bootstrap(self, n_boot=200, seed=None, bound_widths=None, loss="linear", f_scale=1.0, ftol=1e-10, xtol=1e-10, gtol=1e-10,
+                  max_nfev=None, precision=None, device_loop=False, check_every=8):
+        """Bootstrap of the ``method="normal"`` fit: how uncertain are the fitted parameters -- the answer that, unlike the
+        linearised ``parameter_covariance``, survives a robust loss and active bounds.
+
+        ``n_boot`` (1 .. 1024) resamples of the N points, N draws with replacement each from ONE
+        ``np.random.default_rng(seed)`` (``resample.bootstrap_table``); resample b is fitted from ``params_init`` under the
+        weights ``count_b[i] w_i`` -- row b of a weight table on the device -- and all fits run in ONE lockstep, as in
+        ``cross_validate`` (same arguments, same two loops).  The points are uploaded once.
+
+        Returns -- and keeps as ``self.boot_`` -- a dict: ``samples`` (n_boot, D): the fitted values in ``target_params``
+        order; ``results`` (n_boot dicts: cost, iterations, evaluations, status, grad_norm); ``counts`` (n_boot, N): how often
+        each of this rank's points was drawn; ``kept`` (n_boot,) bool: the fits with status > 0 and a finite cost, over which
+        the statistics run; ``dropped``: how many were left out; ``mean`` (D,), ``std`` (D,; ddof = 1) and ``cov`` (D, D;
+        ``np.cov``) of the kept samples (NaN with fewer than two); ``interval``: a function, ``interval(level=0.95)`` ->
+        (lower (D,), upper (D,)), the percentiles 50 (1 -+ level) of the kept samples.
+
+        ValueError, before the device is touched, for ``n_boot`` out of range, a table above
+        ``resample.WEIGHT_TABLE_MAX_BYTES``, targets w / h, an unknown loss, and -- without a communicator -- a resample
+        whose weights are all zero (every point it drew has weight 0)."""
+        cols = self._resample_checks(loss, f_scale, device_loop, check_every)
+        bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
+        world = _lib.comm_world()
+        lo, hi, n_global, seed = self._shard(world, seed)
+        precision = default_precision(hi - lo, precision)
+        if isinstance(n_boot, (int, np.integer)) and not isinstance(n_boot, (bool, np.bool_)):
+            resample.table_check(n_boot, hi - lo, 4 if precision == "f32" else 8)        # before the draws: they are O(n_boot N)
+        counts = resample.bootstrap_table(n_global, n_boot, seed, None, lo, hi)
+        table = counts if self.weights is None else counts * self.weights[None, :]
+        resample.table_check(len(table), hi - lo, 4 if precision == "f32" else 8, table.sum(axis=1) if world == 1 else None)
+        pts = self._device_points(precision)
+        try:
+            runs, finals = self._fit_rows(pts, table, cols, bounds, world, loss, f_scale, ftol, xtol, gtol, max_nfev, device_loop, check_every)
+        finally:
+            pts.close()
+        kept = np.array([r["status"] > 0 and bool(np.isfinite(r["cost"])) for r in runs], dtype=bool)
+        good = finals[kept]
+        d = finals.shape[1]
+        if len(good) >= 2:
+            mean, std, cov = good.mean(axis=0), good.std(axis=0, ddof=1), np.atleast_2d(np.cov(good, rowvar=False))
+        else:
+            mean = good.mean(axis=0) if len(good) else np.full(d, np.nan)
+            std, cov = np.full(d, np.nan), np.full((d, d), np.nan)
+
+        def interval(level=0.95):
+            if not 0 < level < 1:
+                raise ValueError("level must lie in (0, 1)")
+            if not len(good):
+                return np.full(d, np.nan), np.full(d, np.nan)
+            q = np.percentile(good, [50.0 * (1.0 - level), 50.0 * (1.0 + level)], axis=0)
+            return q[0], q[1]
+
+        self.boot_ = dict(samples=finals, results=[{key: r[key] for key in self._RESULT_KEYS} for r in runs], counts=counts, kept=kept,
+                          dropped=int((~kept).sum()), mean=mean, std=std, cov=cov, interval=interval)
+        return self.boot_
 
     def optimize(self, method="trf", bound_widths=None, loss="linear", f_scale=1.0, **kwargs):
         """scipy.optimize.least_squares on the device residuals.  ``jac``: "batched" (the default for trf and dogbox: 2-point

@@ -243,6 +243,24 @@ int alp_normal_equations(alp_points_t *pts, const double params[ALP_NPARAM], con
  * B > 1024. */
 int alp_normal_equations_batch(alp_points_t *pts, const double *params, int64_t B, const int32_t *target_idx, int D, int loss,
                                double f_scale, double *out);
+/* alp_normal_equations_batch with every pose under a weight row of its own: pose b is evaluated under row row_of_pose[b]
+ * (0 .. R-1, repeats allowed, B need not be R) of the table of alp_points_set_weight_table instead of under the weight plane --
+ * the K folds of a cross-validation or the resamples of a bootstrap of the solve of src/alproj/optimize.py:442-539 in the
+ * launch the K starts take.  out as for alp_normal_equations_batch, except that the count slot of row b carries the sum of
+ * ITS weight row (over the ranks, through the same all-reduce).  Grid, stripes and the order of every addition are
+ * alp_normal_equations_batch's for the same B: row b has, bit for bit, the values alp_points_set_weights(row row_of_pose[b])
+ * followed by alp_normal_equations_batch gives, and depends on no other row of the call; a row whose weights are all 0 gives
+ * exact zeros and count 0.  Errors as for alp_normal_equations_batch, ALP_ESTATE when no table is set, ALP_EINVAL for a row
+ * index outside the table (checked on the host before the launch). */
+int alp_normal_equations_batch_rows(alp_points_t *pts, const double *params, int64_t B, const int32_t *row_of_pose,
+                                    const int32_t *target_idx, int D, int loss, double f_scale, double *out);
+/* Residuals with the pose chosen per POINT, in one launch: point i is evaluated under params row assign[i] (cand: B x 25
+ * row-major, 1 <= B <= 4096; assign: n values in -1 .. B-1).  out: 2n doubles in alp_residuals' order (the residual vector of
+ * src/alproj/optimize.py:215-237), a NaN pair where assign[i] < 0.  With assign = the fold of every point and cand = the optima
+ * fitted without that fold, these are the held-out residuals of a cross-validation.  Float64 arithmetic on either set; on a
+ * float64 set the pair of point i has the bits of row assign[i] of alp_residuals_batch.  Needs observed uv (ALP_ESTATE);
+ * ALP_EINVAL for NULL, B out of range or an assign[i] >= B (checked on the host before the launch).  n = 0: nothing happens. */
+int alp_residuals_assigned(alp_points_t *pts, const double *cand, int64_t B, const int32_t *assign, double *out);
 
 /* Population-wide reprojection error: replaces the inner loop of CMAOptimizer.optimize,
  * src/alproj/optimize.py:420-423, i.e. P calls of _proj_error (:347-356) = project +
@@ -346,6 +364,22 @@ int alp_points_set_weights(alp_points_t *pts, const void *w, int in_dtype);
 /* *W = the float64 sum of this rank's stored (rounded) weights, added in index order; n when no weights are set. */
 int alp_points_weight_sum(const alp_points_t *pts, double *W);
 
+/* A TABLE of weights: R rows of n weights each, row-major (w: R x n host values of in_dtype), for the calls that evaluate
+ * every pose under a row of its own -- alp_normal_equations_batch_rows and the device loop of alp_lm_create_rows.  Values,
+ * storage (the set's element type: a float32 set rounds) and the meaning of a weight are alp_points_set_weights'; so are the
+ * rules: everything is validated on the host before anything changes (ALP_EINVAL for a negative, NaN or infinite weight or
+ * one that does not fit the element type: the previous table stays in force), w = NULL drops the table, ALP_ESTATE while an
+ * evaluation is enqueued or a device loop on the set is pending.  1 <= R <= 1024, and the stored table holds at most
+ * ALP_WEIGHT_TABLE_MAX_BYTES (R n element sizes; ALP_EINVAL above) -- a guard, not a tuned number.  The table and the
+ * plane of alp_points_set_weights are independent: a call that names table rows ignores the plane, every other call ignores the
+ * table and runs the kernels it ran before.  The sum of every stored row is formed on the device when the table is set, in
+ * float64, without atomics and in an order that depends on n alone, and kept beside the table: the count slots come from
+ * there.  With a communicator every rank sets the columns of its own shard. */
+#define ALP_WEIGHT_TABLE_MAX_BYTES ((int64_t)1 << 30)
+int alp_points_set_weight_table(alp_points_t *pts, const void *w, int R, int in_dtype);
+/* out[0 .. R) = this rank's row sums as the device formed them; ALP_ESTATE when no table is set. */
+int alp_points_weight_table_sums(alp_points_t *pts, double *out);
+
 /* The candidate sampler of the CMA-ES loop on the device: replaces the `population_size` calls of
  * `optimizer.ask()` per generation, src/alproj/optimize.py:420-421 (third-party cmaes==0.12.0,
  * requirements.txt:14; bounds handling documented at optimize.py:381-384).  Candidate c of generation g:
@@ -443,6 +477,13 @@ typedef struct alp_lm alp_lm_t;
 int alp_lm_create(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
                   const double *upper, const double *X0, int K, int loss, double f_scale, double ftol, double xtol, double gtol,
                   int64_t max_nfev, alp_lm_t **out);
+/* alp_lm_create with start k evaluated under row k of the table of alp_points_set_weight_table (which must have exactly K rows:
+ * ALP_EINVAL otherwise, ALP_ESTATE without a table) instead of under the weight plane: K fits of K resamples in one loop.  The
+ * evaluation is alp_normal_equations_batch_rows' for row_of_pose = 0 .. K-1; everything else is alp_lm_create's.  Replacing the
+ * table by one of another height makes alp_lm_run return ALP_ESTATE. */
+int alp_lm_create_rows(alp_points_t *pts, const double tmpl[ALP_NPARAM], const int32_t *target_idx, int D, const double *lower,
+                       const double *upper, const double *X0, int K, int loss, double f_scale, double ftol, double xtol, double gtol,
+                       int64_t max_nfev, alp_lm_t **out);
 int alp_lm_destroy(alp_lm_t *h);
 /* Enqueue `rounds` rounds (enqueue only; alp_lm_wait synchronises).  A second run before the wait: ALP_ESTATE.  Rounds after
  * the last start has stopped do nothing. */
