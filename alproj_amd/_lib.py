@@ -604,25 +604,8 @@ class Points:
         (alp_normal_equations_batch_rows).  Row b has the bits ``set_weights(table[row_of_pose[b]])`` +
         ``normal_equations_batch(cand)`` give for the same B; W[b] is that row's sum of weights (over the ranks).  ValueError,
         before the library is called, for what ``normal_equations_batch`` refuses and a row index outside the table."""
-        idx = normal_targets_check(target_idx)
-        kind, fs = normal_loss_check(loss, f_scale)
-        cand = np.ascontiguousarray(cand, dtype=np.float64)
-        if cand.ndim != 2 or cand.shape[1] != NPARAM or not 1 <= cand.shape[0] <= NORMAL_BATCH_MAX:
-            raise ValueError(f"cand must have shape (B, 25) with 1 <= B <= {NORMAL_BATCH_MAX}")
-        b, d = cand.shape[0], len(idx)
-        rows = np.ascontiguousarray(np.asarray(row_of_pose).reshape(-1), dtype=np.int32)
-        if rows.shape != (b,) or ((rows < 0) | (rows >= int(getattr(self, "_table_rows", 0)))).any():
-            raise ValueError("row_of_pose must hold one row index of the weight table per pose")
-        tri = d * (d + 1) // 2
-        out = np.empty((b, tri + d + 2), dtype=np.float64)
-        i32 = ctypes.POINTER(ctypes.c_int32)
-        check(self._lib.alp_normal_equations_batch_rows(self._h, as_dp(cand), b, rows.ctypes.data_as(i32), idx.ctypes.data_as(i32), d,
-                                                        kind, fs, as_dp(out)))
-        iu = np.triu_indices(d)
-        G = np.zeros((b, d, d), dtype=np.float64)
-        G[:, iu[0], iu[1]] = out[:, :tri]
-        G = G + np.triu(G, 1).transpose(0, 2, 1)
-        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], out[:, tri + d + 1].copy()
+        G, g, cost, slots = Points._normal_batch(self, cand, row_of_pose, target_idx, loss, f_scale)
+        return G, g, cost, slots.copy()
 
     def residuals_assigned(self, cand, assign):
         """(B, 25) parameter vectors and (N,) int assignments -> (2N,) residuals in ``residuals``' order: point i under
@@ -721,6 +704,12 @@ class Points:
         the rows.  Row b is what ``normal_equations(cand[b], ...)`` returns, to the order of the additions (bit for bit up to
         256 points), and does not depend on the other rows.  ValueError, before the library is called, for what
         ``normal_equations`` refuses and for a ``cand`` of another shape."""
+        G, g, cost, slots = Points._normal_batch(self, cand, None, target_idx, loss, f_scale)
+        return G, g, cost, self._count(slots[0])
+
+    def _normal_batch(self, cand, row_of_pose, target_idx, loss, f_scale):
+        """``normal_equations_batch`` (``row_of_pose`` None) and ``normal_equations_batch_rows``: the checks, the call and
+        -> (G, g, cost, the count slot of every row)"""
         idx = normal_targets_check(target_idx)
         kind, fs = normal_loss_check(loss, f_scale)
         cand = np.ascontiguousarray(cand, dtype=np.float64)
@@ -729,13 +718,20 @@ class Points:
         b, d = cand.shape[0], len(idx)
         tri = d * (d + 1) // 2
         out = np.empty((b, tri + d + 2), dtype=np.float64)
-        check(self._lib.alp_normal_equations_batch(self._h, as_dp(cand), b, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), d, kind,
-                                                   fs, as_dp(out)))
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        if row_of_pose is None:
+            check(self._lib.alp_normal_equations_batch(self._h, as_dp(cand), b, idx.ctypes.data_as(i32), d, kind, fs, as_dp(out)))
+        else:
+            rows = np.ascontiguousarray(np.asarray(row_of_pose).reshape(-1), dtype=np.int32)
+            if rows.shape != (b,) or ((rows < 0) | (rows >= int(getattr(self, "_table_rows", 0)))).any():
+                raise ValueError("row_of_pose must hold one row index of the weight table per pose")
+            check(self._lib.alp_normal_equations_batch_rows(self._h, as_dp(cand), b, rows.ctypes.data_as(i32), idx.ctypes.data_as(i32), d,
+                                                            kind, fs, as_dp(out)))
         iu = np.triu_indices(d)
         G = np.zeros((b, d, d), dtype=np.float64)
         G[:, iu[0], iu[1]] = out[:, :tri]
         G = G + np.triu(G, 1).transpose(0, 2, 1)
-        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], self._count(out[0, tri + d + 1])
+        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], out[:, tri + d + 1]
 
     def eval_population(self, cand, loss_kind, f_scale=10.0, want_argmin=True):
         """-> (losses (P,), argmin).  ``want_argmin=False``: losses only -- the library then skips the float64 confirmation

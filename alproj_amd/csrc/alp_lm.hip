@@ -5,7 +5,7 @@
 // two launches, a copy back, a synchronisation and K numpy state-machine steps with a Cholesky each; at GCP size the kernels
 // are tens of microseconds of that.  Here the state of the K runs (host/alp_lm.h: LmState) lives on the device and a round is
 // enqueued on the library stream with no copy and no synchronisation in between:
-//   1. normal_batch_listed_kernel + reduce_normal_listed_kernel (alp_points.hip: normal_listed_launch), + the all-reduce of the
+//   1. normal_poses_kernel + reduce_normal_poses_kernel on the list (alp_points.hip: normal_listed_launch), + the all-reduce of the
 //      K (T + 1) sums when a communicator exists: the sums at the trial points of the starts that still run
 //   2. lm_step_kernel     one workgroup of one wave per start: the two transitions of host/alp_lm.h on the start's sums, then --
 //                         for a start that goes on -- the 25-parameter row (optimize.py _candidate_matrix) and its plan

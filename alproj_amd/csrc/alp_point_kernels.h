@@ -755,7 +755,7 @@ __device__ __forceinline__ double normal_rho(double z, double &s, double &w) {
     return rho;
 }
 
-// The body of normal_kernel and normal_batch_kernel: the workgroup's stripe `stripe` of `groups_per` groups under `plan`, its
+// The body of normal_kernel and normal_poses_kernel: the workgroup's stripe `stripe` of `groups_per` groups under `plan`, its
 // sums to row `out_row` of `partials` (T doubles each).  `stripe`, `plan` and `out_row` are the same in every lane (the plan comes in by
 // scalar loads).
 // WEIGHTED (alp_points_set_weights): both rows of point i count w_i times -- the row scalings s and w are multiplied by
@@ -869,128 +869,46 @@ __global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, c
     normal_body<TS, LOSS, WEIGHTED>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plan, (int64_t)blockIdx.x, partials, (int64_t)blockIdx.x, wts);
 }
 
-// K3n for B poses over the same points (alp_normal_equations_batch): one workgroup per (stripe, pose) pair of
-// host::normal_batch_grid, under plans[pose]; its row of partials is row `stripe` of pose `pose`:
-// partials[(pose * stripes + stripe) * T ..).  Which grid index carries the pose is the launch's choice (`pose_in_x`: the
-// workgroups of one stripe under all poses are dispatched next to each other, so that the stripe's points are fetched from HBM
-// once and found in the cache by the other poses); the sums do not depend on it.
+// K3n for a batch of poses over the same points (alp_normal_equations_batch, alp_normal_equations_batch_rows and the device
+// loop of alp_lm.hip): one workgroup per (stripe, slot) pair of host::normal_batch_grid.  Which grid index carries the slot is
+// the launch's choice (`pose_in_x`: the workgroups of one stripe under all poses are dispatched next to each other, so that the
+// stripe's points are fetched from HBM once and found in the cache by the other poses); the sums do not depend on it.
+//   the pose   `list` NULL: pose = slot.  Else (the device loop: the grid is the one for ALL K starts) pose = list[slot], `list`
+//              holding the *count running starts in ascending order, and a workgroup with slot >= *count returns at once.
+//   the plan   plans[pose]; the row of partials is row `stripe` of pose `pose`, partials[(pose * stripes + stripe) * T ..) --
+//              a start's stripes and the order of its additions do not depend on which other starts still run.
+//   WEIGHTED   the weights are wts + row * row_stride, row = row_of_pose ? row_of_pose[pose] : pose.  row_stride = 0: the
+//              set's weight plane (alp_points_set_weights) for every pose; row_stride = n: row `row` of the set's weight table
+//              (alp_points_set_weight_table: R rows of n weights of the set's element type).
+// A result row depends on its pose, its weight row and the stripes alone (tests/test_gpu_weight_table.py): it has the bits
+// alp_points_set_weights(row) + the unlisted launch give.  slot, pose and row are the same in every lane: they, like the plan,
+// come in by scalar loads.
 constexpr int NORMAL_BATCH_POSE_IN_X = 1;
 template <typename TS, int LOSS, bool WEIGHTED = false>
-__global__ __launch_bounds__(256) void normal_batch_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
+__global__ __launch_bounds__(256) void normal_poses_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
                                                            const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
                                                            int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
-                                                           int pose_in_x, double *__restrict__ partials, const TS *__restrict__ wts) {
-    const int pose = pose_in_x ? blockIdx.x : blockIdx.y, stripe = pose_in_x ? blockIdx.y : blockIdx.x;
+                                                           const int *__restrict__ list, const long long *__restrict__ count,
+                                                           int pose_in_x, double *__restrict__ partials, const TS *__restrict__ wts,
+                                                           int64_t row_stride, const int *__restrict__ row_of_pose) {
+    const int slot = pose_in_x ? blockIdx.x : blockIdx.y, stripe = pose_in_x ? blockIdx.y : blockIdx.x;
     const int stripes = pose_in_x ? gridDim.y : gridDim.x;
+    if (count && (long long)slot >= *count) return;
+    const int pose = list ? list[slot] : slot;
+    if constexpr (WEIGHTED) wts += (int64_t)(row_of_pose ? row_of_pose[pose] : pose) * row_stride;
     normal_body<TS, LOSS, WEIGHTED>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
                                     (int64_t)pose * stripes + stripe, wts);
 }
 
 // sums[q * (T + 1) + c] = sum over the stripes of pose q's partial rows (reduce_partials_kernel's order: 8 row-groups, each
-// over every 8th stripe, then the 8 in order), sums[q * (T + 1) + T] = n_local, the local point count or, on a weighted set, the local sum of the weights: row q has
-// alp_normal_equations' layout.  blockIdx.y = the pose; one workgroup handles 32 sums x 8 row-groups.
-__global__ __launch_bounds__(256) void reduce_normal_batch_kernel(const double *__restrict__ partials, int stripes, int T, double n_local,
-                                                                  double *__restrict__ sums) {
-    __shared__ double s[8][32];
-    const int cl = threadIdx.x & 31;
-    const int g = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    const double *rows = partials + (int64_t)blockIdx.y * stripes * T;
-    double *out = sums + (int64_t)blockIdx.y * (T + 1);
-    double acc = 0.0;
-    if (c < T)
-        for (int b = g; b < stripes; b += 8) acc += rows[(int64_t)b * T + c];
-    s[g][cl] = acc;
-    __syncthreads();
-    if (g == 0 && c < T) {
-        double t = s[0][cl];
-#pragma unroll
-        for (int k = 1; k < 8; ++k) t += s[k][cl];
-        out[c] = t;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = n_local;
-}
-
-// K3n for the starts a device loop still runs (alp_lm.hip): the grid is normal_batch_kernel's for ALL K starts, pose index
-// fastest, and workgroup (b, stripe) takes start list[b] under plans[list[b]] -- `list` holds the *count running starts in
-// ascending order; a workgroup with b >= *count returns at once.  The partial row is the one normal_batch_kernel would write for
-// pose list[b] of K, so a start's stripes and the order of its additions do not depend on which other starts still run.
-// list[b] is the same in every lane: the plan still comes in by scalar loads.
-template <typename TS, int LOSS, bool WEIGHTED = false>
-__global__ __launch_bounds__(256) void normal_batch_listed_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
-                                                                  const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
-                                                                  int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
-                                                                  const int *__restrict__ list, const long long *__restrict__ count,
-                                                                  double *__restrict__ partials, const TS *__restrict__ wts) {
-    if ((long long)blockIdx.x >= *count) return;
-    const int pose = list[blockIdx.x], stripe = blockIdx.y, stripes = gridDim.y;
-    normal_body<TS, LOSS, WEIGHTED>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
-                                    (int64_t)pose * stripes + stripe, wts);
-}
-
-// reduce_normal_batch_kernel for those starts: row q of `sums` for a running start (running[q] != 0) in the same order of
-// additions, zeros for a stopped one (its partial rows are stale); sums[q * (T + 1) + T] = the local point count in every row.
-__global__ __launch_bounds__(256) void reduce_normal_listed_kernel(const double *__restrict__ partials, int stripes, int T, double n_local,
-                                                                   const int *__restrict__ running, double *__restrict__ sums) {
-    __shared__ double s[8][32];
-    const int cl = threadIdx.x & 31;
-    const int g = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    const double *rows = partials + (int64_t)blockIdx.y * stripes * T;
-    double *out = sums + (int64_t)blockIdx.y * (T + 1);
-    const bool live = running[blockIdx.y] != 0;        // the same in every lane
-    double acc = 0.0;
-    if (c < T && live)
-        for (int b = g; b < stripes; b += 8) acc += rows[(int64_t)b * T + c];
-    s[g][cl] = acc;
-    __syncthreads();
-    if (g == 0 && c < T) {
-        double t = s[0][cl];
-#pragma unroll
-        for (int k = 1; k < 8; ++k) t += s[k][cl];
-        out[c] = t;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = n_local;
-}
-
-// ------------------------------------------------------------------ K3n under the rows of a weight table
-// alp_points_set_weight_table: R rows of n weights of the set's element type, row r at table + r * n.  The kernels below are
-// normal_batch_kernel and normal_batch_listed_kernel with the weight plane replaced by the pose's row: the same grid, the same
-// stripes, normal_body<TS, LOSS, true> on the row -- a result row depends on its pose, its weight row and the stripes alone
-// and has the bits alp_points_set_weights(row) + the unlisted kernel give.  The row index is the same in every lane (it comes
-// in by a scalar load, like the plan).
-template <typename TS, int LOSS>
-__global__ __launch_bounds__(256) void normal_batch_rows_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
-                                                                const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
-                                                                int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plans,
-                                                                int pose_in_x, double *__restrict__ partials, const TS *__restrict__ table,
-                                                                const int *__restrict__ row_of_pose) {
-    const int pose = pose_in_x ? blockIdx.x : blockIdx.y, stripe = pose_in_x ? blockIdx.y : blockIdx.x;
-    const int stripes = pose_in_x ? gridDim.y : gridDim.x;
-    normal_body<TS, LOSS, true>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
-                                (int64_t)pose * stripes + stripe, table + (int64_t)row_of_pose[pose] * n);
-}
-
-// the device loop's form (alp_lm_create_rows): start k runs under row k of a table of K rows
-template <typename TS, int LOSS>
-__global__ __launch_bounds__(256) void normal_batch_listed_rows_kernel(const TS *__restrict__ x, const TS *__restrict__ y,
-                                                                       const TS *__restrict__ z, const TS *__restrict__ uo,
-                                                                       const TS *__restrict__ vo, int64_t n, int64_t groups_per,
-                                                                       double inv_f_scale, const JacPlan *__restrict__ plans,
-                                                                       const int *__restrict__ list, const long long *__restrict__ count,
-                                                                       double *__restrict__ partials, const TS *__restrict__ table) {
-    if ((long long)blockIdx.x >= *count) return;
-    const int pose = list[blockIdx.x], stripe = blockIdx.y, stripes = gridDim.y;
-    normal_body<TS, LOSS, true>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plans + pose, (int64_t)stripe, partials,
-                                (int64_t)pose * stripes + stripe, table + (int64_t)pose * n);
-}
-
-// reduce_normal_batch_kernel (running == NULL) and reduce_normal_listed_kernel (running[q] != 0: start q still runs) for those
-// two: the same order of additions, and the count slot of row q is the local sum of ITS weight row,
-// row_sums[row_of_pose ? row_of_pose[q] : q], instead of one scalar for every row.
-__global__ __launch_bounds__(256) void reduce_normal_rows_kernel(const double *__restrict__ partials, int stripes, int T,
-                                                                 const double *__restrict__ row_sums, const int *__restrict__ row_of_pose,
-                                                                 const int *__restrict__ running, double *__restrict__ sums) {
+// over every 8th stripe, then the 8 in order): row q has alp_normal_equations' layout.  blockIdx.y = the pose; one workgroup
+// handles 32 sums x 8 row-groups.  `running` (the device loop): zeros for a start that has stopped (running[q] == 0: its
+// partial rows are stale).  The count slot sums[q * (T + 1) + T], in every row: n_local -- the local point count or, on a
+// weighted set, the local sum of the weights -- or, under a weight table (`row_sums`), the local sum of ITS row,
+// row_sums[row_of_pose ? row_of_pose[q] : q].
+__global__ __launch_bounds__(256) void reduce_normal_poses_kernel(const double *__restrict__ partials, int stripes, int T, double n_local,
+                                                                  const double *__restrict__ row_sums, const int *__restrict__ row_of_pose,
+                                                                  const int *__restrict__ running, double *__restrict__ sums) {
     __shared__ double s[8][32];
     const int cl = threadIdx.x & 31;
     const int g = threadIdx.x >> 5;
@@ -1009,8 +927,9 @@ __global__ __launch_bounds__(256) void reduce_normal_rows_kernel(const double *_
         for (int k = 1; k < 8; ++k) t += s[k][cl];
         out[c] = t;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = row_sums[row_of_pose ? row_of_pose[blockIdx.y] : (int)blockIdx.y];
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[T] = row_sums ? row_sums[row_of_pose ? row_of_pose[blockIdx.y] : (int)blockIdx.y] : n_local;
 }
+
 
 // W[r] = the float64 sum of row r of a weight table, without atomics and in an order that depends on the row length alone.
 // Workgroup (c, r) adds the values [c * chunk, min((c + 1) * chunk, len)) of row r of `src` (rows `row_stride` apart): lane t takes

@@ -5,8 +5,8 @@
 //   residual_batch_kernel  observed - projected for B poses, interleaved (least-squares path)
 //   jacobian_kernel  d projected / d parameters for one pose, exact (least-squares path)
 //   normal_kernel    the same rows contracted to J^T J, J^T r and the cost where they are made (f64 MFMA; least-squares path)
-//   normal_batch_kernel  the same for B poses in one launch, one workgroup per (stripe, pose) pair
-//   normal_batch_rows_kernel  the same with every pose under a row of the set's weight table (alp_points_set_weight_table)
+//   normal_poses_kernel  the same for B poses in one launch, one workgroup per (stripe, pose) pair: every pose under the set's
+//                    weights or under a row of its weight table (alp_points_set_weight_table), all B or the listed ones (alp_lm.hip)
 //   residuals_assigned_kernel  observed - projected with the pose chosen per point (held-out residuals of a cross-validation)
 //
 // Reference arithmetic: src/alproj/optimize.py  project :122-155, _distort :98-120,
@@ -553,110 +553,100 @@ int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, do
     return ALP_OK;
 }
 
-// alp_normal_equations_batch: normal_batch_kernel over host::normal_batch_grid's stripes x the B poses, reduce_normal_batch_kernel
-// over each pose's rows, one all-reduce and one copy of the B x (T + 1) sums.  The scratch holds the B plans, the partial rows
-// and the sums.  ALP_NORMAL_BATCH_ORDER = "stripe" | "pose" (a development switch, tools/probe_normal_batch.py) names the grid
-// index that runs fastest; the sums do not depend on it.
+// The kernel of the multi-pose K3n for a loss and a weighted / unweighted launch
 template <typename TS>
-int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss, double f_scale, double *out,
-                      const int32_t *row_of_pose = nullptr) {
-    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, int, double *,
-                            const TS *);
-    using RowsKernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, int,
-                                double *, const TS *, const int *);
-    static const RowsKernel rows_kernels[4] = {normal_batch_rows_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_rows_kernel<TS, ALP_NORMAL_SOFT_L1>,
-                                               normal_batch_rows_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_rows_kernel<TS, ALP_NORMAL_CAUCHY>};
-    static const Kernel kernels[2][4] = {{normal_batch_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1>,
-                                          normal_batch_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_kernel<TS, ALP_NORMAL_CAUCHY>},
-                                         {normal_batch_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_batch_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
-                                          normal_batch_kernel<TS, ALP_NORMAL_HUBER, true>, normal_batch_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
+using NormalPosesKernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *,
+                                   const int *, const long long *, int, double *, const TS *, int64_t, const int *);
+template <typename TS>
+NormalPosesKernel<TS> normal_poses_kernel_for(int loss, bool weighted) {
+    static const NormalPosesKernel<TS> kernels[2][4] = {
+        {normal_poses_kernel<TS, ALP_NORMAL_LINEAR>, normal_poses_kernel<TS, ALP_NORMAL_SOFT_L1>,
+         normal_poses_kernel<TS, ALP_NORMAL_HUBER>, normal_poses_kernel<TS, ALP_NORMAL_CAUCHY>},
+        {normal_poses_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_poses_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
+         normal_poses_kernel<TS, ALP_NORMAL_HUBER, true>, normal_poses_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
+    return kernels[weighted][loss];
+}
+
+// What varies between the launches of the multi-pose K3n (device pointers; alp_point_kernels.h: normal_poses_kernel):
+struct NormalPosesLaunch {
+    const int *list = nullptr;           // the device loop: the running starts, their count and a flag per start
+    const long long *count = nullptr;
+    const int *running = nullptr;
+    int pose_in_x = NORMAL_BATCH_POSE_IN_X;
+    bool table = false;                  // the poses run under rows of the set's weight table, not under its weight plane
+    const int *row_of_pose = nullptr;    // with `table`: the row of each pose; NULL: pose k under row k
+    bool timed = false;                  // the two launches are a kernel section (alp_kernel_timing)
+};
+
+// normal_poses_kernel over the stripes of `g` x the K poses under plans[], reduce_normal_poses_kernel over each pose's rows (or
+// zeros for an empty shard, which still joins the all-reduce: a row of no weights sums to 0), one all-reduce of the K x (T + 1)
+// sums.  Enqueue only.  partials: K * g.blocks * T doubles.
+template <typename TS>
+int normal_poses_enqueue(alp_points *p, const JacPlan *plans, int K, int D, const host::NormalGrid &g, int loss, double f_scale,
+                         const NormalPosesLaunch &l, double *partials, double *sums) {
+    const int T = D * (D + 1) / 2 + D + 1;
+    hipStream_t st = ctx().stream;
+    if (g.blocks > 0) {
+        const TS *wts = (const TS *)(l.table ? p->wt : p->w);
+        const dim3 grid = l.pose_in_x ? dim3((unsigned)K, (unsigned)g.blocks) : dim3((unsigned)g.blocks, (unsigned)K);
+        if (l.timed) ktime_begin();
+        hipLaunchKernelGGL(normal_poses_kernel_for<TS>(loss, wts != nullptr), grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
+                           (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, l.list, l.count,
+                           l.pose_in_x, partials, wts, l.table ? p->n : (int64_t)0, l.row_of_pose);
+        hipLaunchKernelGGL(reduce_normal_poses_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)K), dim3(256), 0, st, (const double *)partials,
+                           g.blocks, T, p->count_slot(), l.table ? (const double *)p->wt_sums : nullptr, l.row_of_pose, l.running, sums);
+        if (l.timed) ktime_end();
+        ALP_HIP(hipGetLastError());
+    } else {
+        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)K * (T + 1) * sizeof(double), st));
+    }
+    return comm_allreduce_sum_f64(sums, (int64_t)K * (T + 1));
+}
+
+// alp_normal_equations_batch (row_of_pose NULL) and alp_normal_equations_batch_rows: the scratch holds the B plans, on the row
+// path the B row indices, the partial rows and the sums; one copy of the B x (T + 1) sums comes back.
+// ALP_NORMAL_BATCH_ORDER = "stripe" | "pose" (a development switch, tools/probe_normal_batch.py) names the grid index that runs
+// fastest; the sums do not depend on it.
+template <typename TS>
+int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss, double f_scale, double *out, const int32_t *row_of_pose) {
     const int64_t B = (int64_t)plans.size();
     const int D = plans[0].D, T = D * (D + 1) / 2 + D + 1;
     const host::NormalGrid g = host::normal_batch_grid(p->n, B, ctx().cu_count);
-    // (behind the plans, on the row path: the B row indices)
-    const size_t plan_bytes = round_up((int64_t)(B * sizeof(JacPlan)), 256) + (row_of_pose ? round_up(B * 4, 256) : 0);
+    const size_t plans_bytes = round_up((int64_t)(B * sizeof(JacPlan)), 256), rows_bytes = row_of_pose ? round_up(B * 4, 256) : 0;
     char *dev = nullptr;
-    if (int rc = scratch_reserve(plan_bytes + ((size_t)B * g.blocks * T + (size_t)B * (T + 1)) * sizeof(double), (void **)&dev)) return rc;
+    if (int rc = scratch_reserve(plans_bytes + rows_bytes + ((size_t)B * g.blocks * T + (size_t)B * (T + 1)) * sizeof(double), (void **)&dev)) return rc;
     JacPlan *plans_dev = (JacPlan *)dev;
-    int *rows_dev = (int *)(dev + round_up((int64_t)(B * sizeof(JacPlan)), 256));
-    double *partials = (double *)(dev + plan_bytes), *sums = partials + (size_t)B * g.blocks * T;
+    int *rows_dev = (int *)(dev + plans_bytes);
+    double *partials = (double *)(dev + plans_bytes + rows_bytes), *sums = partials + (size_t)B * g.blocks * T;
     hipStream_t st = ctx().stream;
+    NormalPosesLaunch l;
+    l.timed = true;
     if (g.blocks > 0) {
         const char *order = getenv("ALP_NORMAL_BATCH_ORDER");
-        const int pose_in_x = order ? !strcmp(order, "pose") : NORMAL_BATCH_POSE_IN_X;
-        const dim3 grid = pose_in_x ? dim3((unsigned)B, (unsigned)g.blocks) : dim3((unsigned)g.blocks, (unsigned)B);
+        if (order) l.pose_in_x = !strcmp(order, "pose");
         ALP_HIP(hipMemcpyAsync(plans_dev, plans.data(), (size_t)B * sizeof(JacPlan), hipMemcpyHostToDevice, st));
-        if (row_of_pose) ALP_HIP(hipMemcpyAsync(rows_dev, row_of_pose, (size_t)B * 4, hipMemcpyHostToDevice, st));
-        ktime_begin();
         if (row_of_pose) {
-            hipLaunchKernelGGL(rows_kernels[loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
-                               (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials,
-                               (const TS *)p->wt, (const int *)rows_dev);
-            hipLaunchKernelGGL(reduce_normal_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)B), dim3(256), 0, st, (const double *)partials,
-                               g.blocks, T, (const double *)p->wt_sums, (const int *)rows_dev, (const int *)nullptr, sums);
-        } else {
-            hipLaunchKernelGGL(kernels[p->w != nullptr][loss], grid, dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z, (const TS *)p->uo,
-                               (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plans_dev, pose_in_x, partials, (const TS *)p->w);
-            hipLaunchKernelGGL(reduce_normal_batch_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)B), dim3(256), 0, st, partials, g.blocks, T,
-                               p->count_slot(), sums);
+            ALP_HIP(hipMemcpyAsync(rows_dev, row_of_pose, (size_t)B * 4, hipMemcpyHostToDevice, st));
+            l.table = true;
+            l.row_of_pose = rows_dev;
         }
-        ktime_end();
-        ALP_HIP(hipGetLastError());
-    } else {
-        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)B * (T + 1) * sizeof(double), st));   // an empty shard still joins the all-reduce (a row of no weights sums to 0)
     }
-    if (int rc = comm_allreduce_sum_f64(sums, B * (T + 1))) return rc;
+    if (int rc = normal_poses_enqueue<TS>(p, plans_dev, (int)B, D, g, loss, f_scale, l, partials, sums)) return rc;
     ALP_HIP(hipMemcpyAsync(out, sums, (size_t)B * (T + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
     ALP_HIP(hipStreamSynchronize(st));           // the plans must outlive their copy too
     return ALP_OK;
 }
 
-// The evaluation of a round of the least-squares device loop (alp_lm.hip): normal_batch_listed_kernel over the grid of all K
-// starts, reduce_normal_listed_kernel, one all-reduce of K (T + 1) doubles.  Enqueue only; the buffers are the loop's own.
-template <typename TS>
-int normal_listed_impl(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
-                       const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums, bool weight_rows) {
-    using RowsKernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, const int *,
-                                const long long *, double *, const TS *);
-    static const RowsKernel rows_kernels[4] = {
-        normal_batch_listed_rows_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_listed_rows_kernel<TS, ALP_NORMAL_SOFT_L1>,
-        normal_batch_listed_rows_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_listed_rows_kernel<TS, ALP_NORMAL_CAUCHY>};
-    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, const int *,
-                            const long long *, double *, const TS *);
-    static const Kernel kernels[2][4] = {
-        {normal_batch_listed_kernel<TS, ALP_NORMAL_LINEAR>, normal_batch_listed_kernel<TS, ALP_NORMAL_SOFT_L1>,
-         normal_batch_listed_kernel<TS, ALP_NORMAL_HUBER>, normal_batch_listed_kernel<TS, ALP_NORMAL_CAUCHY>},
-        {normal_batch_listed_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_batch_listed_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
-         normal_batch_listed_kernel<TS, ALP_NORMAL_HUBER, true>, normal_batch_listed_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
-    const int T = D * (D + 1) / 2 + D + 1;
-    hipStream_t st = ctx().stream;
-    if (g.blocks > 0 && weight_rows) {
-        hipLaunchKernelGGL(rows_kernels[loss], dim3((unsigned)K, (unsigned)g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
-                           (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, list, count, partials,
-                           (const TS *)p->wt);
-        hipLaunchKernelGGL(reduce_normal_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)K), dim3(256), 0, st, (const double *)partials,
-                           g.blocks, T, (const double *)p->wt_sums, (const int *)nullptr, running, sums);
-        ALP_HIP(hipGetLastError());
-    } else if (g.blocks > 0) {
-        hipLaunchKernelGGL(kernels[p->w != nullptr][loss], dim3((unsigned)K, (unsigned)g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y,
-                           (const TS *)p->z, (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, plans, list, count, partials,
-                           (const TS *)p->w);
-        hipLaunchKernelGGL(reduce_normal_listed_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)K), dim3(256), 0, st, (const double *)partials,
-                           g.blocks, T, p->count_slot(), running, sums);
-        ALP_HIP(hipGetLastError());
-    } else {
-        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)K * (T + 1) * sizeof(double), st));       // an empty shard still joins the all-reduce
-    }
-    return comm_allreduce_sum_f64(sums, (int64_t)K * (T + 1));
-}
-
 }  // namespace
 
 namespace alp {
+// The evaluation of a round of the least-squares device loop (alp_lm.hip), over the grid of all K starts; the buffers are the loop's own.
 int normal_listed_launch(alp_points *p, const JacPlan *plans, const int *list, const long long *count, const int *running, int K, int D,
                          const host::NormalGrid &g, int loss, double f_scale, double *partials, double *sums, bool weight_rows) {
-    return p->precision == ALP_F64 ? normal_listed_impl<double>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums, weight_rows)
-                                   : normal_listed_impl<float>(p, plans, list, count, running, K, D, g, loss, f_scale, partials, sums, weight_rows);
+    NormalPosesLaunch l;
+    l.list = list, l.count = count, l.running = running, l.pose_in_x = 1, l.table = weight_rows;
+    return p->precision == ALP_F64 ? normal_poses_enqueue<double>(p, plans, K, D, g, loss, f_scale, l, partials, sums)
+                                   : normal_poses_enqueue<float>(p, plans, K, D, g, loss, f_scale, l, partials, sums);
 }
 int popeval_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, bool lens_free, bool shared_pose, bool batched,
                    const double *params_dev) {
@@ -1111,39 +1101,37 @@ int alp_normal_equations(alp_points_t *p, const double params[ALP_NPARAM], const
     return p->precision == ALP_F64 ? normal_impl<double>(p, plan, loss, f_scale, out) : normal_impl<float>(p, plan, loss, f_scale, out);
 }
 
-int alp_normal_equations_batch(alp_points_t *p, const double *params, int64_t B, const int32_t *target_idx, int D, int loss,
-                               double f_scale, double *out) {
+// alp_normal_equations_batch (rows = false) and alp_normal_equations_batch_rows under their own names
+static int normal_equations_batch_entry(const char *name, alp_points_t *p, const double *params, int64_t B, bool rows, const int32_t *row_of_pose,
+                                        const int32_t *target_idx, int D, int loss, double f_scale, double *out) {
     if (int rc = require_init()) return rc;
-    ALP_REQUIRE(p && params && out, "NULL argument");
-    ALP_REQUIRE(B >= 1 && B <= host::NORMAL_BATCH_MAX, "B must be 1..1024");
-    ALP_REQUIRE(loss >= ALP_NORMAL_LINEAR && loss <= ALP_NORMAL_CAUCHY, "unknown loss");
-    ALP_REQUIRE(f_scale > 0 && std::isfinite(f_scale), "f_scale must be a positive finite number");
+    const auto refuse = [&](bool ok, const char *msg) { return ok ? ALP_OK : fail(ALP_EINVAL, "%s: %s", name, msg); };
+    if (int rc = refuse(p && params && out && (row_of_pose || !rows), "NULL argument")) return rc;
+    if (int rc = refuse(B >= 1 && B <= host::NORMAL_BATCH_MAX, "B must be 1..1024")) return rc;
+    if (int rc = refuse(loss >= ALP_NORMAL_LINEAR && loss <= ALP_NORMAL_CAUCHY, "unknown loss")) return rc;
+    if (int rc = refuse(f_scale > 0 && std::isfinite(f_scale), "f_scale must be a positive finite number")) return rc;
     std::vector<JacPlan> plans((size_t)B);
     for (int64_t b = 0; b < B; ++b)
         if (int rc = jacobian_plan(params + b * ALP_NPARAM, p->origin, target_idx, D, 1, &plans[(size_t)b])) return rc;
-    if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations_batch: observed uv not set");
-    return p->precision == ALP_F64 ? normal_batch_impl<double>(p, plans, loss, f_scale, out)
-                                   : normal_batch_impl<float>(p, plans, loss, f_scale, out);
+    if (!p->uo) return fail(ALP_ESTATE, "%s: observed uv not set", name);
+    if (rows) {
+        if (!p->wt) return fail(ALP_ESTATE, "%s: no weight table set", name);
+        for (int64_t b = 0; b < B; ++b)             // before the launch: the kernel indexes the table with it
+            if (row_of_pose[b] < 0 || row_of_pose[b] >= p->wt_rows)
+                return fail(ALP_EINVAL, "%s: row_of_pose[%lld] = %d is no row of the table of %d", name, (long long)b, (int)row_of_pose[b], p->wt_rows);
+    }
+    return p->precision == ALP_F64 ? normal_batch_impl<double>(p, plans, loss, f_scale, out, row_of_pose)
+                                   : normal_batch_impl<float>(p, plans, loss, f_scale, out, row_of_pose);
+}
+
+int alp_normal_equations_batch(alp_points_t *p, const double *params, int64_t B, const int32_t *target_idx, int D, int loss,
+                               double f_scale, double *out) {
+    return normal_equations_batch_entry(__func__, p, params, B, false, nullptr, target_idx, D, loss, f_scale, out);
 }
 
 int alp_normal_equations_batch_rows(alp_points_t *p, const double *params, int64_t B, const int32_t *row_of_pose, const int32_t *target_idx,
                                     int D, int loss, double f_scale, double *out) {
-    if (int rc = require_init()) return rc;
-    ALP_REQUIRE(p && params && out && row_of_pose, "NULL argument");
-    ALP_REQUIRE(B >= 1 && B <= host::NORMAL_BATCH_MAX, "B must be 1..1024");
-    ALP_REQUIRE(loss >= ALP_NORMAL_LINEAR && loss <= ALP_NORMAL_CAUCHY, "unknown loss");
-    ALP_REQUIRE(f_scale > 0 && std::isfinite(f_scale), "f_scale must be a positive finite number");
-    std::vector<JacPlan> plans((size_t)B);
-    for (int64_t b = 0; b < B; ++b)
-        if (int rc = jacobian_plan(params + b * ALP_NPARAM, p->origin, target_idx, D, 1, &plans[(size_t)b])) return rc;
-    if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations_batch_rows: observed uv not set");
-    if (!p->wt) return fail(ALP_ESTATE, "alp_normal_equations_batch_rows: no weight table set");
-    for (int64_t b = 0; b < B; ++b)             // before the launch: the kernel indexes the table with it
-        if (row_of_pose[b] < 0 || row_of_pose[b] >= p->wt_rows)
-            return fail(ALP_EINVAL, "alp_normal_equations_batch_rows: row_of_pose[%lld] = %d is no row of the table of %d", (long long)b,
-                        (int)row_of_pose[b], p->wt_rows);
-    return p->precision == ALP_F64 ? normal_batch_impl<double>(p, plans, loss, f_scale, out, row_of_pose)
-                                   : normal_batch_impl<float>(p, plans, loss, f_scale, out, row_of_pose);
+    return normal_equations_batch_entry(__func__, p, params, B, true, row_of_pose, target_idx, D, loss, f_scale, out);
 }
 
 // obs_b / prj_b NULL: that array is interleaved (n x 2 row-major); else a = the u column, b = the v column

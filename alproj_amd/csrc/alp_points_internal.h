@@ -90,7 +90,8 @@ void lm_points_gone(alp_lm_t *h);
 // rounds of a least-squares device loop are enqueued and not yet waited for (they read the set's planes, the weights included)
 bool lm_loop_pending(const alp_lm_t *h);
 
-// One evaluation of the least-squares device loop (alp_lm.hip): the normal equations of the starts in `list` (*count of them, in
+// One evaluation of the least-squares device loop (alp_lm.hip), normal_poses_kernel + reduce_normal_poses_kernel given the list:
+// the normal equations of the starts in `list` (*count of them, in
 // ascending order; running[k] != 0 for exactly those) under plans[k], over the fixed grid `g` = host::normal_batch_grid(n, K, cus):
 // sums = K rows of T + 1 doubles in alp_normal_equations_batch's layout, zeros (and the point count) for a start that is not
 // listed; all-reduced when a communicator exists.  partials: K * g.blocks * T doubles.  Enqueue only.

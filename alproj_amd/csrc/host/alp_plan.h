@@ -161,7 +161,7 @@ inline NormalGrid normal_grid(int64_t n, int cu_count) {
     return {(int)((groups + per - 1) / per), per};
 }
 
-// The grid of normal_batch_kernel (alp_normal_equations_batch): B poses over the same points, one workgroup per (stripe, pose)
+// The grid of normal_poses_kernel (alp_normal_equations_batch, its _rows form and the rounds of alp_lm.hip): B poses over the same points, one workgroup per (stripe, pose)
 // pair, `blocks` stripes per pose -- blocks x B workgroups, each writing ONE row of partial sums.  The workgroups normal_grid
 // aims at are shared out among the poses: a pose gets ceil(want / B) stripes, at least one, at most one per group; the stripes
 // are then made as long as they must be and those left without a group are dropped, as in normal_grid.  B = 1 is normal_grid

@@ -1,4 +1,4 @@
-"""GPU: the normal equations of B poses in one launch (alp_normal_equations_batch / normal_batch_kernel) and
+"""GPU: the normal equations of B poses in one launch (alp_normal_equations_batch / normal_poses_kernel) and
 LsqOptimizer.optimize(method="normal", starts=...).
 
 A row of the batch against the single call (alp_normal_equations) at the same pose: the per-point arithmetic is the same code,

@@ -341,6 +341,92 @@ def test_the_listed_kernel_of_the_device_loop_under_table_rows(L, n):
             assert e.value.code == ESTATE
 
 
+# A pose whose plan the host and the device fold to the same bits.  The loop folds a start's plan on the device, the library
+# call on the host, and the two differ by the device's sin / cos / tan alone (tests/test_gpu_lm_device.py), so a comparison of
+# the two bit for bit needs a pose where those agree: pan = roll = 0 and tilt = -90 (a camera looking straight down) make
+# every angle of host/alp_fold.h a zero, whose sine and cosine are exact everywhere, and at fov = 52 on the 5616 x 3744 image
+# both tangents of the fold (of 0.4537.. and 0.3025..) lie within 0.06 ulp of a double, which every tangent good to 0.9 ulp
+# returns.  None of the four is a target below, so they stay what they are in every round.
+NADIR_FOV = 52.0
+NADIR_TARGETS = ["x", "y", "z", "a1", "a2", "k1", "k2"]
+NADIR_WIDTH = np.array([40.0, 40.0, 40.0, 0.1, 0.1, 0.05, 0.02])
+
+
+@functools.lru_cache(maxsize=None)
+def nadir_problem(n):
+    from alproj_amd import synthetic as syn
+    p = dict(syn.truth_params(316), pan=0.0, tilt=-90.0, roll=0.0, fov=NADIR_FOV)
+    xyz = syn.gcp_points(n, p, seed=7)
+    uv = orc.project_points(xyz, p) + np.random.default_rng(7).normal(0, 1.0, (n, 2))
+    centre = np.array([float(p[t]) for t in NADIR_TARGETS])
+    X0 = centre + np.random.default_rng(8).uniform(-0.25, 0.25, (3, len(NADIR_TARGETS))) * NADIR_WIDTH
+    return p, xyz, uv, X0, centre - NADIR_WIDTH, centre + NADIR_WIDTH
+
+
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+@pytest.mark.parametrize("n", [64, 257])
+def test_the_listed_kernel_under_table_rows_after_a_start_has_ended(L, n, precision):
+    """A listed launch under table rows in which list[b] != b.  Three device loops of K = 3 starts under a 3-row table; start 0
+    of `ended` and `twin` has a NaN coordinate (np.clip keeps it), so it ends at its first evaluation and the two rounds after
+    it run list = [1, 2]: workgroup slot b takes start b + 1, its plan, its weight row and its partial rows (257 points: two
+    stripes, the second group ragged; 64: one).
+      ended  runs its rounds on the device;
+      twin   is stepped (alp_lm_step_host) on alp_normal_equations_batch_rows' sums of the trial points of starts 1 and 2 under
+             row_of_pose = [1, 2]; the row of start 0: NaN in the first round (what the evaluation at a NaN pose gives), then
+             zeros, its own row's weight sum in the count slot;
+      whole  is `ended` with a finite start 0: all three starts run, list = [0, 1, 2].
+    In every round the records of starts 1 and 2 are the same BIT FOR BIT in all three.  The loop's sums cannot be read back,
+    but lm_step_kernel is the same code on the three handles, and one differing bit in G, g or the cost of a round shows in
+    cost, x, mu or the next trial point (nadir_problem's pose: the host-built plan of the library call has the bits of the
+    device-built one).  The row of sums of the ended start cannot be read either; what it stands for is held: status -1 after
+    one evaluation, and a record that never moves again."""
+    p, xyz, uv, X0, lower, upper = nadir_problem(n)
+    K = 3
+    X0_nan = X0.copy()
+    X0_nan[0, 0] = np.nan
+    targets = t_normal.idx(NADIR_TARGETS)
+    tp = np.array(targets, dtype=np.int32)
+    rows = np.array([1, 2], dtype=np.int32)
+    D = len(targets)
+    tmpl = L.params_vector(p)
+    with t_w.points(L, xyz, uv, [p["x"], p["y"], p["z"]], precision) as pts:
+        pts.set_weight_table(table_of(pts.n, K, seed=9))
+        pts.set_weights(np.full(pts.n, 7.0))                    # the plane is ignored under table rows
+        sums = pts.weight_table_sums()
+        assert len(set(sums.tolist())) == K                     # three rows, three problems
+        loop = lambda starts: L.LmDevice(pts, tmpl, targets, lower, upper, starts, weight_rows=True)
+        with loop(X0_nan) as ended, loop(X0_nan) as twin, loop(X0) as whole:
+            for rnd in range(3):
+                rec = twin.get()
+                assert (rec["status"][1:] == lc.RUNNING).all() and (rec["status"][0] == lc.RUNNING) == (rnd == 0)
+                cand = np.tile(tmpl, (2, 1))
+                cand[:, targets] = rec["trial"][1:]
+                raw = np.zeros((K, D * (D + 1) // 2 + D + 2))
+                assert L.lib().alp_normal_equations_batch_rows(pts._h, L.as_dp(cand), 2, rows.ctypes.data_as(I32), tp.ctypes.data_as(I32), D, 0,
+                                                               1.0, L.as_dp(raw[1:])) == 0
+                assert np.array_equal(raw[1:, -1], sums[1:])
+                if rnd == 0:
+                    raw[0] = np.nan
+                raw[0, -1] = sums[0]
+                ended.run(1)
+                assert ended.wait() == 2
+                whole.run(1)
+                assert whole.wait() == 3
+                twin.step_host(raw)
+                r_end, rt, rw = ended.get(), twin.get(), whole.get()
+                dev = float(np.max(np.abs(r_end["trial"][1:] - rt["trial"][1:]) / (upper - lower)))
+                print("round %d: trial deviation of the twin %.3g of the width, cost rel %.3g" %
+                      (rnd, dev, float(np.max(np.abs(r_end["cost"][1:] - rt["cost"][1:]) / np.abs(rt["cost"][1:])))))
+                assert r_end["status"][0] == -1 and r_end["evaluations"][0] == 1 and not np.isfinite(r_end["cost"][0])
+                if rnd == 0:
+                    first = r_end
+                t_lm.same_bits(r_end, first, rows=(0, 0))
+                for k in (1, 2):
+                    t_lm.same_bits(r_end, rw, rows=(k, k))
+                    t_lm.same_bits(r_end, rt, rows=(k, k))
+            assert (r_end["evaluations"][1:] == 3).all() and r_end["cost"][1] != r_end["cost"][2]
+
+
 def lsq(prob, n=None, weights=None):
     from alproj_amd import optimize as aopt
     sub = dict(prob, xyz=prob["xyz"][:n], uv=prob["uv"][:n])

@@ -423,7 +423,7 @@ def test_normal_equations_launch_shapes(L, n, D):
 @pytest.mark.parametrize("n", [None, 257])
 def test_the_listed_kernel_of_the_device_loop_on_a_weighted_set(L, n):
     """tests/test_gpu_lm_device.py::test_the_evaluation_inside_the_loop_is_the_batch_call on a weighted set: one handle runs a
-    round (normal_batch_listed_kernel), its twin is stepped on alp_normal_equations_batch's sums at the same trial points"""
+    round (normal_poses_kernel given the list), its twin is stepped on alp_normal_equations_batch's sums at the same trial points"""
     from tests import test_gpu_lm_device as t_lm
     prob = t_lm.problem("trf_linear_d7")
     K = 3

@@ -11,7 +11,7 @@ One JSON line per configuration:
          evaluation dominates, the loop must cost nothing.
 
 Which number is compared with which: the device loop against the host lockstep in the same run.  No ratio is fixed in advance.
-Kernel time per round by kernel (lm_step_kernel, lm_select_kernel, normal_batch_listed_kernel, reduce_normal_listed_kernel):
+Kernel time per round by kernel (lm_step_kernel, lm_select_kernel, normal_poses_kernel, reduce_normal_poses_kernel):
 from a separate kernel-trace run of `--steps trace` (the device loop alone, K = 64, check_every = 8) under the profiler.
 
   python tools/probe_lm_device.py [--steps small,large] [--reps 15] [--out profiles/lm_device_probe.jsonl]

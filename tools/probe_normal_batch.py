@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""alp_normal_equations_batch (normal_batch_kernel: the normal equations of B poses in one launch) against B single calls, and
-the single entry point against the parent commit's.  One process, one JSON line per step:
+"""alp_normal_equations_batch (normal_poses_kernel: the normal equations of B poses in one launch) against B single calls, and
+the normal-equation entry points against the parent commit's.  One process, one JSON line per step:
 
   small  (a) the GCP size: n = 1127 float64 points, D = 9, B = 64.  One batch call against 64 sequential
              Points.normal_equations calls on the same handle: the median whole-call wall time of --reps repetitions after a
@@ -10,10 +10,13 @@ the single entry point against the parent commit's.  One process, one JSON line 
              single call's, alternated round by round in one process, for BOTH workgroup orders (ALP_NORMAL_BATCH_ORDER =
              stripe | pose: which grid index runs fastest).  Condition, for the order the library ships: the batch's median per
              pose is not above the single call's median by more than the single call's own spread, (max - min) / median.
-  single (c) --parent-lib PATH: the parent's library (loaded twice, as tools/probe_mend.py does) and this one in one process,
-             alternated, alp_normal_equations at both sizes: the results bit for bit, and this library's median kernel time
-             inside the spread of the two parent instances.  normal_kernel's body moved into a device function both kernels
-             call; its launch did not change.
+  single (c) --parent-lib PATH: the parent's library (loaded twice, as tools/probe_mend.py does) and this one in one process.
+             Bits: alp_normal_equations_batch (B = 1, 8, 64; unweighted and weighted), alp_normal_equations_batch_rows (repeated
+             and permuted rows) and one round of the device loop with and without weight rows, read back through alp_lm_get, at
+             n = 257 and 100 003, float64 and float32, linear and huber: no bit may differ between the three.  Time, alternated
+             round by round: the whole call and the kernel section of alp_normal_equations and alp_normal_equations_batch at the
+             GCP size, a round of the device loop with K = 64 there, and the kernel sections of the single, the batch and the
+             rows call at --points; this library's median must lie inside the spread of the two parent instances' values.
   solve  (d) recorded only: LsqOptimizer.optimize(method="normal", starts=64, seed=1) on the g14 problem trf_linear_d7 against
              64 single-start runs from the same starts: wall time, kernel time, and the rest split into library calls and host
              solve.
@@ -146,29 +149,177 @@ class RawLib:
         if rc:
             raise RuntimeError(f"rc {rc}: {(self.lib.alp_last_error() or b'').decode(errors='replace')}")
 
-    def points(self, xyz, origin, uv):
+    def points(self, xyz, origin, uv, precision=L.ALP_F64):
         h = ctypes.c_void_p()
         xyz, uv = np.ascontiguousarray(xyz), np.ascontiguousarray(uv)
         o = np.ascontiguousarray(origin, dtype=np.float64)
-        self.ok(self.lib.alp_points_create(xyz.ctypes.data_as(ctypes.c_void_p), L.dtype_code(xyz), len(xyz), L.as_dp(o), L.ALP_F64,
+        self.ok(self.lib.alp_points_create(xyz.ctypes.data_as(ctypes.c_void_p), L.dtype_code(xyz), len(xyz), L.as_dp(o), precision,
                                            ctypes.byref(h)))
         self.ok(self.lib.alp_points_set_observed(h, uv.ctypes.data_as(ctypes.c_void_p), L.dtype_code(uv)))
         return h
 
-    def normal(self, h, pv, cols, reps):
-        """(mean kernel ms of `reps` calls after one more, the sums)"""
+    def set_weights(self, h, w):
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim == 1:
+            self.ok(self.lib.alp_points_set_weights(h, w.ctypes.data_as(ctypes.c_void_p), L.ALP_F64))
+        else:
+            self.ok(self.lib.alp_points_set_weight_table(h, w.ctypes.data_as(ctypes.c_void_p), len(w), L.ALP_F64))
+
+    def normal(self, h, pv, cols, loss=0, rows=None):
+        """the raw sums of alp_normal_equations (pv (25,)), alp_normal_equations_batch (pv (B, 25)) or, with `rows`, of
+        alp_normal_equations_batch_rows"""
         idx = np.ascontiguousarray(cols, dtype=np.int32)
         d = len(idx)
-        out = np.empty(d * (d + 1) // 2 + d + 2)
+        pv = np.ascontiguousarray(pv, dtype=np.float64)
+        out = np.empty(pv.shape[:-1] + (d * (d + 1) // 2 + d + 2,))
+        if pv.ndim == 1:
+            self.ok(self.lib.alp_normal_equations(h, L.as_dp(pv), idx.ctypes.data_as(I32), d, loss, 1.0, L.as_dp(out)))
+        elif rows is None:
+            self.ok(self.lib.alp_normal_equations_batch(h, L.as_dp(pv), len(pv), idx.ctypes.data_as(I32), d, loss, 1.0, L.as_dp(out)))
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.int32)
+            self.ok(self.lib.alp_normal_equations_batch_rows(h, L.as_dp(pv), len(pv), r.ctypes.data_as(I32), idx.ctypes.data_as(I32), d, loss, 1.0,
+                                                             L.as_dp(out)))
+        return out
+
+    def timed(self, fn, reps):
+        """(median wall ms of a call, mean kernel ms of a call) over `reps` calls of fn after one more"""
         ms, cnt = ctypes.c_float(), ctypes.c_int()
         self.ok(self.lib.alp_kernel_timing(1))
-        self.ok(self.lib.alp_normal_equations(h, L.as_dp(pv), idx.ctypes.data_as(I32), d, 0, 1.0, L.as_dp(out)))
+        fn()
         self.ok(self.lib.alp_kernel_time_ms(ctypes.byref(ms), ctypes.byref(cnt)))
+        wall = []
         for _ in range(reps):
-            self.ok(self.lib.alp_normal_equations(h, L.as_dp(pv), idx.ctypes.data_as(I32), d, 0, 1.0, L.as_dp(out)))
+            t0 = time.perf_counter()
+            fn()
+            wall.append((time.perf_counter() - t0) * 1e3)
         self.ok(self.lib.alp_kernel_time_ms(ctypes.byref(ms), ctypes.byref(cnt)))
         self.ok(self.lib.alp_kernel_timing(0))
-        return ms.value / reps, out
+        return float(np.median(wall)), ms.value / reps
+
+    def lm_rounds(self, h, pv, cols, X0, rounds, loss=0, weight_rows=False):
+        """a device loop from the starts X0 (K, D), unbounded: (wall ms per round of `rounds` rounds, enqueue to the end of the
+        wait; the records read back through alp_lm_get, as one array)"""
+        idx = np.ascontiguousarray(cols, dtype=np.int32)
+        X0 = np.ascontiguousarray(X0, dtype=np.float64)
+        K, D = X0.shape
+        lo, hi = np.full(D, -np.inf), np.full(D, np.inf)
+        loop = ctypes.c_void_p()
+        create = self.lib.alp_lm_create_rows if weight_rows else self.lib.alp_lm_create
+        self.ok(create(h, L.as_dp(np.ascontiguousarray(pv)), idx.ctypes.data_as(I32), D, L.as_dp(lo), L.as_dp(hi), L.as_dp(X0), K, loss, 1.0,
+                       1e-10, 1e-10, 1e-10, 100 * D, ctypes.byref(loop)))
+        pending = ctypes.c_int64()
+        t0 = time.perf_counter()
+        self.ok(self.lib.alp_lm_run(loop, rounds))
+        self.ok(self.lib.alp_lm_wait(loop, ctypes.byref(pending)))
+        ms = (time.perf_counter() - t0) * 1e3 / rounds
+        x, trial = np.empty((K, D)), np.empty((K, D))
+        cost, gn, mu, nu = (np.empty(K) for _ in range(4))
+        it, ev = np.empty(K, dtype=np.int64), np.empty(K, dtype=np.int64)
+        status = np.empty(K, dtype=np.int32)
+        self.ok(self.lib.alp_lm_get(loop, L.as_dp(x), L.as_dp(cost), L.as_dp(gn), it.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                    ev.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), status.ctypes.data_as(I32), L.as_dp(trial), L.as_dp(mu),
+                                    L.as_dp(nu)))
+        self.ok(self.lib.alp_lm_destroy(loop))
+        return ms, np.concatenate([x.ravel(), trial.ravel(), cost, gn, mu, nu, it, ev, status])
+
+
+def weights_of(n, R, seed):
+    """R rows of n weights: integer counts 0..3, uniform fractions, a 0/1 mask, in turn"""
+    rng = np.random.default_rng(seed)
+    kinds = (lambda: rng.integers(0, 4, n).astype(np.float64), lambda: rng.uniform(0, 3, n), lambda: (rng.uniform(0, 1, n) < 0.7).astype(np.float64))
+    return np.array([kinds[r % 3]() for r in range(R)])
+
+
+def same_bits(outs):
+    return all(np.array_equal(outs[0].view(np.uint64), o.view(np.uint64)) for o in outs[1:])
+
+
+def single_bits(libs, args):
+    """every multi-pose call and a round of the device loop in the three libraries: rows that differ in any bit, by case"""
+    differ, cases = [], 0
+    for n in (257, 100_003):
+        xyz, origin, (u, v), pv, cand, cols = problem(n, TARGETS_D9, 64, 3)
+        uv = np.column_stack([u, v])
+        w = weights_of(n, 8, 5)
+        for precision in (L.ALP_F64, L.ALP_F32):
+            handles = [lib.points(xyz, origin, uv, precision) for _, lib in libs]
+            X0 = cand[:8][:, cols]
+
+            def case(what, fn):
+                nonlocal cases
+                cases += 1
+                if not same_bits([fn(lib, h) for (_, lib), h in zip(libs, handles)]):
+                    differ.append(f"n={n} {'f64' if precision == L.ALP_F64 else 'f32'} {what}")
+
+            for weighted in (False, True):
+                if weighted:
+                    for (_, lib), h in zip(libs, handles):
+                        lib.set_weights(h, w[1])
+                for loss in (0, 2):                          # linear, huber
+                    for B in (1, 8, 64):
+                        case(f"batch B={B} loss={loss} weighted={weighted}", lambda lib, h: lib.normal(h, cand[:B], cols, loss))
+                    case(f"lm round loss={loss} weighted={weighted}", lambda lib, h: lib.lm_rounds(h, pv, cols, X0, 1, loss)[1])
+            for (_, lib), h in zip(libs, handles):
+                lib.set_weights(h, w)
+            for loss in (0, 2):
+                for rows in ([3, 3, 0, 7, 1, 1, 5, 3], [7, 6, 5, 4, 3, 2, 1, 0], [2], list(np.random.default_rng(1).integers(0, 8, 64))):
+                    case(f"rows {rows[:8]} loss={loss}", lambda lib, h: lib.normal(h, cand[:len(rows)], cols, loss, rows))
+                case(f"lm round under weight rows loss={loss}", lambda lib, h: lib.lm_rounds(h, pv, cols, X0, 1, loss, True)[1])
+            for (_, lib), h in zip(libs, handles):
+                lib.ok(lib.lib.alp_points_destroy(h))
+    return dict(step="single", what="bits", libraries=[who for who, _ in libs], cases=cases, cases_with_differing_bits=differ,
+                condition="no differing bit", holds=not differ)
+
+
+def single_times(libs, args):
+    """this library's medians inside the spread of the two parent instances, alternated round by round"""
+    rows = []
+
+    def compare(what, handles, fn, **info):
+        """fn(lib, handle) -> {figure: ms}; per figure the values of every round and library"""
+        ms = {}
+        for rnd in range(args.rounds + 1):
+            for (who, lib), h in zip(libs, handles):
+                for fig, t in fn(lib, h).items():
+                    if rnd:                                  # round 0 warms the scratch of every shape
+                        ms.setdefault(fig, {}).setdefault(who, []).append(round(t, 5))
+        for fig, by in ms.items():
+            parents = by["parent_a"] + by["parent_b"]
+            lo, hi, med = min(parents), max(parents), float(np.median(by["this"]))
+            rows.append(dict(step="single", what=what, figure=fig, rounds=args.rounds, ms=by, parent_min_ms=lo, parent_max_ms=hi,
+                             this_median_ms=round(med, 5), this_over_parent_median=round(med / float(np.median(parents)), 4),
+                             condition="parent_min <= this_median <= parent_max", inside_parent_spread=bool(lo <= med <= hi),
+                             above_parent_max=bool(med > hi), **info))
+
+    def call(fn, reps):
+        return lambda lib, h: dict(zip(("call_wall_ms", "kernel_ms"), lib.timed(lambda: fn(lib, h), reps)))
+
+    xyz, origin, (u, v), pv, cand, cols = problem(1127, TARGETS_D9, 64, 3)
+    handles = [lib.points(xyz, origin, np.column_stack([u, v])) for _, lib in libs]
+    compare("alp_normal_equations", handles, call(lambda lib, h: lib.normal(h, pv, cols), 50), points=1127, columns=9)
+    compare("alp_normal_equations_batch", handles, call(lambda lib, h: lib.normal(h, cand, cols), 50), points=1127, columns=9, poses=64)
+    X0 = cand[:, cols]
+    compare("device loop", handles, lambda lib, h: {"wall_ms_per_round": lib.lm_rounds(h, pv, cols, X0, 8)[0]}, points=1127, columns=9,
+            starts=64, rounds_per_run=8)
+    for (_, lib), h in zip(libs, handles):
+        lib.ok(lib.lib.alp_points_destroy(h))
+
+    n = args.points
+    xyz, origin, (u, v), pv, cand, cols = problem(n, TARGETS_D21, 8, 3)
+    handles = [lib.points(xyz, origin, np.column_stack([u, v])) for _, lib in libs]
+    del xyz
+    w = weights_of(n, 2, 5)
+    for (_, lib), h in zip(libs, handles):
+        lib.set_weights(h, w)
+    del w
+    compare("alp_normal_equations", handles, call(lambda lib, h: lib.normal(h, pv, cols), 5), points=n, columns=21)
+    compare("alp_normal_equations_batch", handles, call(lambda lib, h: lib.normal(h, cand, cols), 3), points=n, columns=21, poses=8)
+    compare("alp_normal_equations_batch_rows", handles, call(lambda lib, h: lib.normal(h, cand, cols, 0, [0, 1, 1, 0, 0, 1, 0, 1]), 3),
+            points=n, columns=21, poses=8)
+    for (_, lib), h in zip(libs, handles):
+        lib.ok(lib.lib.alp_points_destroy(h))
+    return rows
 
 
 def step_single(args):
@@ -178,31 +329,7 @@ def step_single(args):
         second = os.path.join(tmp, "libalproj_hip_parent_b.so")
         shutil.copy(args.parent_lib, second)
         libs = [("parent_a", RawLib(args.parent_lib)), ("this", RawLib(L.LIB_PATH)), ("parent_b", RawLib(second))]
-    assert [hasattr(lib.lib, "alp_normal_equations_batch") for _, lib in libs] == [False, True, False]
-    rows = []
-    for n, targets, reps in ((1127, TARGETS_D9, 50), (args.points, TARGETS_D21, 5)):
-        xyz, origin, (u, v), pv, _, cols = problem(n, targets, 1, 3)
-        uv = np.column_stack([u, v])
-        handles = [lib.points(xyz, origin, uv) for _, lib in libs]
-        ms = {who: [] for who, _ in libs}
-        same, first = True, None
-        for rnd in range(args.rounds + 1):
-            for (who, lib), h in zip(libs, handles):
-                t, out = lib.normal(h, pv, cols, reps)
-                if rnd:
-                    ms[who].append(round(t, 5))
-                first = out if first is None else first
-                same = same and np.array_equal(first, out, equal_nan=True)
-        for (_, lib), h in zip(libs, handles):
-            lib.ok(lib.lib.alp_points_destroy(h))
-        parents = ms["parent_a"] + ms["parent_b"]
-        lo, hi = min(parents), max(parents)
-        med = float(np.median(ms["this"]))
-        rows.append(dict(step="single", points=n, columns=len(cols), calls_per_round=reps, rounds=args.rounds, kernel_ms=ms,
-                         parent_min_ms=lo, parent_max_ms=hi, this_median_ms=round(med, 5),
-                         this_over_parent_median=round(med / float(np.median(parents)), 4), inside_parent_spread=bool(lo <= med <= hi),
-                         above_parent_max=bool(med > hi), sums_bit_equal=bool(same)))
-    return rows
+    return [single_bits(libs, args)] + single_times(libs, args)
 
 
 def step_solve(args):
