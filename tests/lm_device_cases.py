@@ -1,6 +1,7 @@
 """Helpers of the device loop of LsqOptimizer.optimize(method="normal", device_loop=True), shared by
 tests/test_lm_device_host.py (CPU: the state machine of host/alp_lm.h through the selfcheck driver's --lm mode) and
-tests/test_gpu_lm_device.py (GPU: the same machine inside alp_lm_step_host, and the whole loop).
+tests/test_gpu_lm_device.py (GPU: the same machine inside alp_lm_step_host, and the whole loop); and the start counts and
+stop patterns of tests/test_gpu_lm_device_starts.py (GPU: the loop with up to 1024 starts).
 
 The reference of the state machine is alproj_amd/optimize.py: _normal_lm_steps.  ``lockstep`` runs it and records, per round, the
 trial point and the sums it received there; the machine under test then receives the same sums round by round and must
@@ -20,6 +21,70 @@ TRIAL_TOL = 1e-10
 TOLS = dict(ftol=1e-10, xtol=1e-10, gtol=1e-10)
 LINEAR_D = (1, 2, 16, 17, 23)
 RUNNING = -2                    # alp_lm_get's status of a start that has not stopped
+
+
+# ---------------------------------------------------------------------------------------------------- start counts and stop patterns
+# (tests/test_gpu_lm_device_starts.py; held by tests/test_lm_device_host.py)
+# lm_select_kernel lists the running starts by a ballot per wave of 64, a prefix over the 4 waves of its workgroup, and passes
+# of 256 starts that carry `base`.  The start counts put a handle's last start on either side of a wave seam (63 | 64 | 65), a
+# pass seam (255 | 256 | 257), in the third pass (513) and at the limit; the seam slots are the first and last slot of a wave
+# and of a pass.
+WAVE, PASS = 64, 256
+SEAM_K = (1, 63, 64, 65, 255, 256, 257, 513, 1024)
+SEAM_SLOTS = (0, 63, 64, 65, 255, 256, 257)
+HALF_SEED = 5
+SPARSE_SEED = 17                # survivors at K = 1024: 8, 5, 0 and 3 in the four passes, none in 8 of the 16 waves
+SUBSET_SEED = 11
+TABLE_SEED = 13                 # resample.bootstrap_table(n, 257, TABLE_SEED): 257 distinct integer rows at n = 64 and 400
+
+
+def seam_slots(K):
+    """the seam slots that exist among K starts, and the last start"""
+    return sorted({j for j in SEAM_SLOTS + (K - 1,) if 0 <= j < K})
+
+
+def random_half(K):
+    """K // 2 of the K slots, seeded"""
+    return np.sort(np.random.default_rng(HALF_SEED).permutation(K)[:K // 2])
+
+
+def sparse_survivors(K):
+    """the slots that keep running in the sparse pattern: each with probability 1 / 64, from ONE seeded draw of 1024 numbers,
+    so that the survivors among K starts are those among 1024 that lie below K"""
+    return np.flatnonzero(np.random.default_rng(SPARSE_SEED).uniform(size=1024)[:K] < 1.0 / WAVE)
+
+
+def stop_sets(K):
+    """{name: the sorted slots to stop} among K starts, each set once: a pattern that does not fit in K, or that is the set
+    another name already gave (K = 1: "all but 0" is "none"), is left out"""
+    everyone = np.arange(K)
+    sets = {"none": everyone[:0], "all": everyone}
+    for j in seam_slots(K):
+        sets["all but %d" % j] = np.delete(everyone, j)
+        sets["only %d" % j] = everyone[j:j + 1]
+    sets["even"], sets["odd"] = everyone[0::2], everyone[1::2]
+    if K > WAVE:
+        sets["first wave"] = everyone[:WAVE]
+    if K > PASS:
+        sets["first pass"] = everyone[:PASS]
+    sets["all but the last wave"] = everyone[:(K - 1) // WAVE * WAVE]
+    sets["random half"] = random_half(K)
+    sets["all but sparse survivors"] = np.setdiff1d(everyone, sparse_survivors(K))
+    out, seen = {}, set()
+    for name, s in sets.items():
+        s = np.asarray(s, dtype=np.int64)
+        if s.tobytes() not in seen:
+            seen.add(s.tobytes())
+            out[name] = s
+    return out
+
+
+def subset_slots(K=1024):
+    """48 of K >= 1024 slots: eight on either side of the seams 64, 256 and 512 (four before, four after), the first and the
+    last eight, and eight seeded others"""
+    fixed = np.concatenate([np.arange(0, 8), np.arange(60, 68), np.arange(252, 260), np.arange(508, 516), np.arange(K - 8, K)])
+    others = np.setdiff1d(np.arange(K), fixed)
+    return np.sort(np.concatenate([fixed, np.random.default_rng(SUBSET_SEED).permutation(others)[:8]]))
 
 
 def pack(G, g, cost):

@@ -119,6 +119,77 @@ def test_all_variables_on_bounds_stops_at_once(exe):
     assert ref["status"] == 1 and ref["evaluations"] == 1 and (ref["x"] == lower).all() and ref["grad_norm"] == 0.0
 
 
+# ---------------------------------------------------------------------------------------------------- start counts and stop patterns
+def test_stop_sets_fit_their_start_count_and_reach_every_seam():
+    """the case helpers of tests/test_gpu_lm_device_starts.py"""
+    assert lc.SEAM_K == (1, 63, 64, 65, 255, 256, 257, 513, 1024) and nb.BATCH_MAX == 1024
+    for K in lc.SEAM_K:
+        sets = lc.stop_sets(K)
+        assert list(sets)[:2] == ["none", "all"] and len(sets["none"]) == 0 and np.array_equal(sets["all"], np.arange(K))
+        assert len({s.tobytes() for s in sets.values()}) == len(sets)              # no pattern twice
+        for name, s in sets.items():
+            assert s.dtype == np.int64 and np.array_equal(s, np.unique(s)) and (len(s) == 0 or (0 <= s[0] and s[-1] < K)), (K, name)
+        assert lc.seam_slots(K) == sorted({j for j in (0, 63, 64, 65, 255, 256, 257, K - 1) if j < K})
+        for j in lc.seam_slots(K):
+            if K > 1:
+                assert np.array_equal(sets["only %d" % j], [j])
+                assert np.array_equal(np.setdiff1d(np.arange(K), sets["all but %d" % j]), [j])
+        print("K = %4d: %2d stop sets" % (K, len(sets)))
+    assert list(lc.stop_sets(1)) == ["none", "all"]
+    sets = lc.stop_sets(1024)
+    assert len(sets) == 2 + 2 * 8 + 7
+    assert np.array_equal(sets["even"], np.arange(0, 1024, 2)) and np.array_equal(sets["odd"], np.arange(1, 1024, 2))
+    assert np.array_equal(sets["first wave"], np.arange(64)) and np.array_equal(sets["first pass"], np.arange(256))
+    assert np.array_equal(sets["all but the last wave"], np.arange(960))
+    assert np.array_equal(lc.stop_sets(255)["all but the last wave"], np.arange(192))
+    for K, name in ((65, "all but 64"), (257, "all but 256"), (513, "all but 512")):          # the same set under its first name
+        assert "all but the last wave" not in lc.stop_sets(K) and np.array_equal(lc.stop_sets(K)[name], np.arange(K - 1))
+    half = sets["random half"]
+    assert len(half) == 512 and 0 < (half % 2).sum() < 512 and all(0 < ((half // 64) == w).sum() < 64 for w in range(16))
+    for K in lc.SEAM_K:
+        assert len(lc.random_half(K)) == K // 2
+
+
+def test_the_sparse_survivors_leave_waves_and_a_whole_pass_empty():
+    keep = lc.sparse_survivors(1024)
+    assert np.array_equal(np.setdiff1d(np.arange(1024), lc.stop_sets(1024)["all but sparse survivors"]), keep)
+    per_pass = np.bincount(keep // lc.PASS, minlength=4)
+    per_wave = np.bincount(keep // lc.WAVE, minlength=16)
+    print("sparse survivors", keep.tolist(), "per pass", per_pass.tolist(), "per wave", per_wave.tolist())
+    assert 8 <= len(keep) <= 32
+    assert per_pass[2] == 0 and per_pass[:2].all() and per_pass[3] > 0     # a pass with no running start, survivors on both sides
+    assert per_wave[3] == 0 and per_wave[:3].all() and per_wave[4] > 0     # the same for a wave inside the first pass
+    assert np.diff(keep).max() > lc.PASS                                   # one survivor after a long gap
+    for K in lc.SEAM_K:                                                    # the same draw at every start count
+        assert np.array_equal(lc.sparse_survivors(K), keep[keep < K])
+    assert len(lc.sparse_survivors(513)) > len(lc.sparse_survivors(257)) > 0
+
+
+def test_the_subset_of_48_slots_sits_on_the_seams():
+    slots = lc.subset_slots()
+    assert len(slots) == 48 == len(set(slots.tolist())) and np.array_equal(slots, np.sort(slots)) and slots[0] == 0 and slots[-1] == 1023
+    for block in (range(0, 8), range(60, 68), range(252, 260), range(508, 516), range(1016, 1024)):
+        assert set(block) <= set(slots.tolist())
+
+
+def test_the_starts_are_distinct_and_prefix_stable_and_the_table_rows_distinct():
+    from alproj_amd import resample
+    prob = nc.g14_problem("trf_linear_d7")
+    lower, upper = nc.bounds_of(prob, None)
+    x_init = np.array([prob["init"][t] for t in prob["targets"]])
+    assert len(prob["xyz"]) == 400 and len(x_init) == 7
+    big = nb.integer_starts(x_init, lower, upper, 1024, 1)
+    assert len({row.tobytes() for row in big}) == 1024
+    assert ((big >= lower) & (big <= upper)).all()
+    for K in lc.SEAM_K:
+        assert np.array_equal(nb.integer_starts(x_init, lower, upper, K, 1), big[:K])
+    assert np.array_equal(nb.integer_starts(x_init, lower, upper, 8, 1), big[:8])
+    for n in (64, 400):
+        table = resample.bootstrap_table(n, 257, lc.TABLE_SEED)
+        assert table.shape == (257, n) and (table == np.floor(table)).all() and (table.sum(axis=1) == n).all()
+        assert len({row.tobytes() for row in table}) == 257
+
+
 # ---------------------------------------------------------------------------------------------------- interface and refusals
 def test_the_header_declares_the_entry_points():
     text = open(os.path.join(ROOT, "include", "alproj_hip.h")).read()
