@@ -34,6 +34,12 @@ template <> struct Num<float> {
         const native4 t = *reinterpret_cast<const native4 *>(p);
         return make_float4(t.x, t.y, t.z, t.w);
     }
+    // the same from an address that is aligned to the element only (a row of any length): still one global_load_dwordx4
+    static __device__ __forceinline__ float4 load_unaligned(const float *p) {
+        native4 t;
+        __builtin_memcpy(&t, p, sizeof(t));
+        return make_float4(t.x, t.y, t.z, t.w);
+    }
     static __device__ __forceinline__ void nt_store(const float4 &a, float4 *p) {
         const native4 t = {a.x, a.y, a.z, a.w};
         __builtin_nontemporal_store(t, reinterpret_cast<native4 *>(p));
@@ -97,6 +103,11 @@ template <> struct Num<double> {
     }
     static __device__ __forceinline__ double2 load(const double2 *p) {
         const native2 t = *reinterpret_cast<const native2 *>(p);
+        return make_double2(t.x, t.y);
+    }
+    static __device__ __forceinline__ double2 load_unaligned(const double *p) {
+        native2 t;
+        __builtin_memcpy(&t, p, sizeof(t));
         return make_double2(t.x, t.y);
     }
     static __device__ __forceinline__ void nt_store(const double2 &a, double2 *p) {
@@ -200,8 +211,16 @@ __global__ __launch_bounds__(256) void project_kernel(const T *__restrict__ x, c
 // 4 + 8 = 12 B/vertex streamed (float), 24 (double).  Same launch shape, same arithmetic, same bits as the plane form.
 // Row and column come from a multiply by a host-computed magic number (RowDiv) rather than from a 2-D launch with one
 // row range per workgroup: the launch keeps one vector per lane over the flat index, whatever W is and wherever a row ends.
+// ONE division per lane, for the vector's first point e0 (host/alp_plan.h: RowWalk, which the host self-check holds to a
+// division per point).  A vector that lies in one row -- every vector when VEC divides W (known without a look at the lane:
+// the uniform test in front), all but about VEC in W of them otherwise -- reads its x values as ONE 16-byte load at x + column,
+// aligned to the element only, and one y.  A vector that crosses a row end walks its points with an add and a compare; only rows
+// shorter than a vector (W < VEC: several row ends per vector, tiny sets) keep a division per point.
 // `last` = n - 1.  The elements of the last vector past n are padding that nothing reads (the fetches copy n values): the
-// per-element form clamps their indices to `last`, the aligned form reads them from e0's row; neither leaves the planes.
+// crossing and per-point forms clamp their indices to `last`, the one-row form reads them from e0's row; neither leaves the planes.
+// Measured (profiles/project_grid_widths_ab.txt), best launch, a division and four loads per point -> this form: 9999 x 10001
+// float32 0.231-0.235 -> 0.203-0.206 ms (10000 x 10000: 0.198-0.203), 3163 x 3163 0.0258-0.0262 -> 0.0238-0.0242; float64 within
+// its spread at both (24 B/vertex hide the per-point work).
 template <typename T>
 __global__ __launch_bounds__(256) void project_kernel(const T *__restrict__ x, const T *__restrict__ y,
                                                       const T *__restrict__ z, T *__restrict__ u,
@@ -214,22 +233,26 @@ __global__ __launch_bounds__(256) void project_kernel(const T *__restrict__ x, c
     Vt qz = Num<T>::nt_load(reinterpret_cast<const Vt *>(z) + i);
     const uint32_t e0 = (uint32_t)i * VEC;        // < n_pad <= 2^31
     Vt qx, qy;
-    if (rd.w % VEC == 0) {
-        // the vector lies in one row, and its x values are one aligned vector of the column table
-        const uint32_t r = rd.div(e0);
-        const uint32_t c = e0 - r * rd.w;
-        qx = Num<T>::load(reinterpret_cast<const Vt *>(x + c));
-        const T yr = y[r * rd.w];
+    const RowWalk<VEC> walk(rd, e0, last);        // one division
+    // the vector lies in one row: its x values are one vector of the column table (16-byte aligned only when VEC divides W)
+    const auto one_row = [&] {
+        qx = Num<T>::load_unaligned(x + walk.c);
+        const T yr = y[walk.r0];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) vget<T>(qy, k) = yr;
+    };
+    if (rd.w % VEC == 0) {
+        one_row();                                // every lane, known without a look at the lane: today's aligned form
+    } else if (walk.one_row) {
+        one_row();
     } else {
-        // the vector may cross a row end (or, at W < VEC, several): row and column element by element
+        // the vector crosses a row end (at W < VEC: maybe several): row and column element by element
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-            const uint32_t e = e0 + k < last ? e0 + k : last;
-            const uint32_t r = rd.div(e);
-            vget<T>(qx, k) = x[e - r * rd.w];
-            vget<T>(qy, k) = y[r * rd.w];
+            uint32_t ck, rk;
+            walk.at(k, &ck, &rk);
+            vget<T>(qx, k) = x[ck];
+            vget<T>(qy, k) = y[rk];
         }
     }
     Vt ou, ov;

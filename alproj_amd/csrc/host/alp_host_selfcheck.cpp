@@ -532,6 +532,57 @@ void check_row_div() {
     }
 }
 
+// RowWalk<VEC> against a division per point.  One vector of a set of n points in rows of w: a point that exists has the column
+// and the row start its flat index gives; padding past the last point reads inside the column table and inside the y plane;
+// one_row says exactly that the whole vector lies in e0's row.  Returns the number of vectors that were NOT one_row.
+template <int VEC>
+uint32_t row_walk_vector(const RowDiv &rd, uint32_t e0, uint32_t last) {
+    const uint32_t w = rd.w;
+    const RowWalk<VEC> walk(rd, e0, last);
+    bool ok = walk.one_row == (e0 % w + VEC <= w);
+    for (uint32_t k = 0; k < (uint32_t)VEC; ++k) {
+        uint32_t col = ~0u, row0 = ~0u;
+        walk.at(k, &col, &row0);
+        const uint32_t e = std::min(e0 + k, last);
+        if (e0 + k <= last || !walk.one_row) ok &= col == e % w && row0 == e / w * w;
+        else ok &= col == e0 % w + k && row0 == e0 / w * w;       // padding of a one-row vector: the following columns
+        ok &= col < w && row0 <= last;
+    }
+    if (!ok) CHECK(false, "RowWalk<%d>: w=%u e0=%u last=%u", VEC, w, e0, last);
+    return walk.one_row ? 0 : 1;
+}
+
+template <int VEC>
+void check_row_walk_t() {
+    // every row length around the vector width with every point count up to a few rows (a grid set has n > w), every vector
+    for (uint32_t w = 1; w <= 64; ++w) {
+        const RowDiv rd = host::row_div(w);
+        for (uint32_t n = w + 1; n <= 4 * w + VEC + 1; ++n) {
+            uint32_t crossing = 0;
+            for (uint32_t e0 = 0; e0 < n; e0 += VEC) crossing += row_walk_vector<VEC>(rd, e0, n - 1);
+            if (w % VEC == 0) CHECK(crossing == 0, "RowWalk<%d>: w=%u n=%u leaves the one-row form", VEC, w, n);
+        }
+    }
+    // random row lengths up to the cap with the set ending just below 2^31: the vectors around the last row ends and the last one
+    std::mt19937_64 rng(VEC);
+    for (int t = 0; t < 4000; ++t) {
+        const uint32_t w = t < 8 ? 65536 - t : 1 + (uint32_t)(rng() % 65536);
+        const RowDiv rd = host::row_div(w);
+        const uint32_t n = 0x80000000u - (uint32_t)(rng() % (2 * w + 8));      // n_pad <= 2^31
+        const uint32_t last = n - 1, rows = last / w;
+        for (uint32_t r = rows >= 3 ? rows - 3 : 0; r <= rows; ++r)
+            for (uint32_t e0 = (r * w - std::min(r * w, (uint32_t)(2 * VEC))) / VEC * VEC; e0 <= last && e0 < r * w + 2 * VEC; e0 += VEC)
+                row_walk_vector<VEC>(rd, e0, last);
+        for (uint32_t e0 = (last - std::min(last, (uint32_t)(3 * VEC))) / VEC * VEC; e0 <= last; e0 += VEC) row_walk_vector<VEC>(rd, e0, last);
+        for (int s = 0; s < 16; ++s) row_walk_vector<VEC>(rd, (uint32_t)(rng() % n) / VEC * VEC, last);
+    }
+}
+
+void check_row_walk() {
+    check_row_walk_t<2>();
+    check_row_walk_t<4>();
+}
+
 // ------------------------------------------------------------------ the error message is per thread
 void check_errors() {
     std::vector<std::thread> th;
@@ -919,7 +970,7 @@ int main(int argc, char **argv) {
     const Group groups[] = {{"hash", check_hash},     {"minmax", check_minmax},   {"prefault", check_prefault}, {"fold_pose", check_fold_pose},
                             {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors},
                             {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}, {"lm", check_lm},
-                            {"buffer", check_buffer}};
+                            {"buffer", check_buffer},   {"row_walk", check_row_walk}};
     const bool concurrent = !(argc > 1 && !strcmp(argv[1], "--serial"));
     // every group on its own caller thread at once: the library promises that independent calls may overlap
     std::vector<std::thread> th;

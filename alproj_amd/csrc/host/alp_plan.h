@@ -1,11 +1,11 @@
 // Launch planning of the point-set kernels (alp_points.hip): the stripes x tile columns of a population evaluation, the points of
 // one staged residual / Jacobian launch, the stripes of the normal-equations kernel, the grid of a streaming kernel, the
-// magic-number division by a grid set's row length -- and of a render frame (alp_raster.hip): the grid of every kernel of the
+// magic-number division by a grid set's row length and the rows and columns of one vector of its points -- and of a render frame (alp_raster.hip): the grid of every kernel of the
 // frame, the sizes of the once-per-mesh tile plan, the capacities of the device queues and which of them a finished frame's
 // counters say must grow.
 // Integer arithmetic on (n, P, precision, V, cu_count) resp. (mesh shape, frame size, tile size, cu_count, counters) alone; the
 // caller allocates and launches.  Included by host/alp_host.h after host/alp_fold.h (ALP_HD); no HIP header.
-// host/alp_host_selfcheck.cpp sweeps it (check_plan, check_frame_plan) and prints it (--plan).
+// host/alp_host_selfcheck.cpp sweeps it (check_plan, check_frame_plan, check_row_div, check_row_walk) and prints it (--plan).
 #pragma once
 
 #include <cstdint>
@@ -20,6 +20,44 @@ namespace alp {
 struct RowDiv {
     uint32_t w = 0, shift = 0, mul = 0;          // w = 0: not a grid (K1 reads the x and y planes)
     ALP_HD uint32_t div(uint32_t e) const { return (uint32_t)(((uint64_t)e * mul) >> shift); }
+};
+
+// Row and column of the VEC consecutive points e0 .. e0 + VEC - 1 of a grid set, as K1's grid form reads them: point k has its x
+// at index col(k) of the x plane (its column) and its y at index row0(k) of the y plane (the first point of its row).
+// e0 <= last = n - 1; a point past `last` (padding of the final vector, which nothing reads) never leaves the planes.
+// ONE division, for e0.  Then
+//   one_row (c + VEC <= W: every vector when VEC divides W, all but about VEC in W of them otherwise): the points lie in e0's row
+//     at the columns c, c + 1, ... < W -- K1 reads them as one vector at x + c and one y; padding follows in the same row;
+//   else, W >= VEC: exactly one row end lies inside the vector -- an add and a compare per point; padding is clamped to `last`,
+//     so a row that is not there is never addressed;
+//   else (W < VEC: several row ends in one vector; such sets are tiny): a division per point, clamped to `last`.
+template <int VEC>
+struct RowWalk {
+    RowDiv rd;
+    uint32_t c, r0, room;          // e0's column, the first index of its row, last - e0
+    bool one_row;
+    ALP_HD RowWalk(const RowDiv &d, uint32_t e0, uint32_t last) : rd(d) {
+        const uint32_t r = d.div(e0);
+        r0 = r * d.w;
+        c = e0 - r0;
+        room = last - e0;
+        one_row = d.w % VEC == 0 || c + VEC <= d.w;      // the first test is uniform and implies the second
+    }
+    ALP_HD void at(uint32_t k, uint32_t *col, uint32_t *row0) const {
+        if (one_row) {
+            *col = c + k;
+            *row0 = r0;
+        } else if (rd.w >= VEC) {
+            const uint32_t ck = c + (k < room ? k : room);
+            const bool next = ck >= rd.w;
+            *col = next ? ck - rd.w : ck;
+            *row0 = next ? r0 + rd.w : r0;
+        } else {
+            const uint32_t e = r0 + c + (k < room ? k : room), r = rd.div(e);
+            *col = e - r * rd.w;
+            *row0 = r * rd.w;
+        }
+    }
 };
 
 namespace host {
