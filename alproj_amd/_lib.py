@@ -441,6 +441,17 @@ def normal_targets_check(target_idx):
     return idx
 
 
+def normal_rows_unpack(out, d, fs):
+    """(B, D(D+1)/2 + D + 2) rows as alp_normal_equations and its batch forms write them -- the row-major upper triangle of G,
+    g, sum rho, the count slot -- -> (G (B, D, D) symmetric, g (B, D), cost (B,) = scipy's 0.5 f_scale^2 sum rho, slots (B,))"""
+    tri = d * (d + 1) // 2
+    iu = np.triu_indices(d)
+    G = np.zeros((len(out), d, d), dtype=np.float64)
+    G[:, iu[0], iu[1]] = out[:, :tri]
+    G = G + np.triu(G, 1).transpose(0, 2, 1)
+    return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], out[:, tri + d + 1]
+
+
 def weights_check(w, n, precision=None):
     """(n,) float32 / float64 contiguous weights, or ValueError (host arithmetic, before the library is called): another
     length, a negative, NaN or infinite weight, and -- when no communicator shards the points -- weights whose sum is 0.
@@ -689,20 +700,19 @@ class Points:
         if pvec.shape != (NPARAM,):
             raise ValueError("pvec must have shape (25,)")
         d = len(idx)
-        tri = d * (d + 1) // 2
-        out = np.empty(tri + d + 2, dtype=np.float64)
+        out = np.empty((1, d * (d + 1) // 2 + d + 2), dtype=np.float64)          # one row of the batch layout
         check(self._lib.alp_normal_equations(self._h, as_dp(pvec), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), d, kind, fs,
                                              as_dp(out)))
-        G = np.zeros((d, d), dtype=np.float64)
-        G[np.triu_indices(d)] = out[:tri]
-        G = G + np.triu(G, 1).T
-        return G, out[tri:tri + d].copy(), 0.5 * fs * fs * float(out[tri + d]), self._count(out[tri + d + 1])
+        G, g, cost, slots = normal_rows_unpack(out, d, fs)
+        return G[0], g[0], float(cost[0]), self._count(slots[0])
 
     def normal_equations_batch(self, cand, target_idx, loss="linear", f_scale=1.0):
         """-> (G (B, D, D), g (B, D), cost (B,), n): ``normal_equations`` at the B parameter vectors ``cand`` (B, 25),
         1 <= B <= NORMAL_BATCH_MAX, formed in one launch (alp_normal_equations_batch); targets, loss and f_scale are shared by
-        the rows.  Row b is what ``normal_equations(cand[b], ...)`` returns, to the order of the additions (bit for bit up to
-        256 points), and does not depend on the other rows.  ValueError, before the library is called, for what
+        the rows.  Row b is what ``normal_equations(cand[b], ...)`` returns, bit for bit wherever B poses get
+        the stripes one pose gets (the launch rule normal_batch_grid(n, B, cus): up to 256 points always, and whenever B is small
+        against 6 workgroups per CU, e.g. any n for B <= 3 on 256 CUs) and to the order of the additions otherwise, and does
+        not depend on the other rows.  ValueError, before the library is called, for what
         ``normal_equations`` refuses and for a ``cand`` of another shape."""
         G, g, cost, slots = Points._normal_batch(self, cand, None, target_idx, loss, f_scale)
         return G, g, cost, self._count(slots[0])
@@ -716,8 +726,7 @@ class Points:
         if cand.ndim != 2 or cand.shape[1] != NPARAM or not 1 <= cand.shape[0] <= NORMAL_BATCH_MAX:
             raise ValueError(f"cand must have shape (B, 25) with 1 <= B <= {NORMAL_BATCH_MAX}")
         b, d = cand.shape[0], len(idx)
-        tri = d * (d + 1) // 2
-        out = np.empty((b, tri + d + 2), dtype=np.float64)
+        out = np.empty((b, d * (d + 1) // 2 + d + 2), dtype=np.float64)
         i32 = ctypes.POINTER(ctypes.c_int32)
         if row_of_pose is None:
             check(self._lib.alp_normal_equations_batch(self._h, as_dp(cand), b, idx.ctypes.data_as(i32), d, kind, fs, as_dp(out)))
@@ -727,11 +736,7 @@ class Points:
                 raise ValueError("row_of_pose must hold one row index of the weight table per pose")
             check(self._lib.alp_normal_equations_batch_rows(self._h, as_dp(cand), b, rows.ctypes.data_as(i32), idx.ctypes.data_as(i32), d,
                                                             kind, fs, as_dp(out)))
-        iu = np.triu_indices(d)
-        G = np.zeros((b, d, d), dtype=np.float64)
-        G[:, iu[0], iu[1]] = out[:, :tri]
-        G = G + np.triu(G, 1).transpose(0, 2, 1)
-        return G, out[:, tri:tri + d].copy(), 0.5 * fs * fs * out[:, tri + d], out[:, tri + d + 1]
+        return normal_rows_unpack(out, d, fs)
 
     def eval_population(self, cand, loss_kind, f_scale=10.0, want_argmin=True):
         """-> (losses (P,), argmin).  ``want_argmin=False``: losses only -- the library then skips the float64 confirmation

@@ -744,7 +744,7 @@ __global__ __launch_bounds__(256) void jacobian_kernel(const TS *__restrict__ x,
 // Order of the additions, fixed by the launch shape alone: a wave walks the groups of its workgroup's stripe in index order,
 // inside a group the u rows then the v rows of its 64 points, k ascending; the four waves of a workgroup are added in wave
 // order; every workgroup writes one row of partials -- in the layout of alp_normal_equations' `out` less its last value --
-// and reduce_partials_kernel adds the rows.  No atomics.  A masked lane (past the end of the set) contributes exact zeros.
+// and reduce_normal_poses_kernel adds the rows of each pose.  No atomics.  A masked lane (past the end of the set) contributes exact zeros.
 constexpr int NRM_ROWS = 64;
 constexpr int NRM_RS = 66;
 constexpr int NRM_MAXM = JAC_MAX + 1;
@@ -778,7 +778,7 @@ __device__ __forceinline__ double normal_rho(double z, double &s, double &w) {
     return rho;
 }
 
-// The body of normal_kernel and normal_poses_kernel: the workgroup's stripe `stripe` of `groups_per` groups under `plan`, its
+// The body of normal_poses_kernel: the workgroup's stripe `stripe` of `groups_per` groups under `plan`, its
 // sums to row `out_row` of `partials` (T doubles each).  `stripe`, `plan` and `out_row` are the same in every lane (the plan comes in by
 // scalar loads).
 // WEIGHTED (alp_points_set_weights): both rows of point i count w_i times -- the row scalings s and w are multiplied by
@@ -884,16 +884,8 @@ __device__ __forceinline__ void normal_body(const TS *__restrict__ x, const TS *
     }
 }
 
-template <typename TS, int LOSS, bool WEIGHTED = false>
-__global__ __launch_bounds__(256) void normal_kernel(const TS *__restrict__ x, const TS *__restrict__ y, const TS *__restrict__ z,
-                                                     const TS *__restrict__ uo, const TS *__restrict__ vo, int64_t n,
-                                                     int64_t groups_per, double inv_f_scale, const JacPlan *__restrict__ plan,
-                                                     double *__restrict__ partials, const TS *__restrict__ wts) {
-    normal_body<TS, LOSS, WEIGHTED>(x, y, z, uo, vo, n, groups_per, inv_f_scale, plan, (int64_t)blockIdx.x, partials, (int64_t)blockIdx.x, wts);
-}
-
-// K3n for a batch of poses over the same points (alp_normal_equations_batch, alp_normal_equations_batch_rows and the device
-// loop of alp_lm.hip): one workgroup per (stripe, slot) pair of host::normal_batch_grid.  Which grid index carries the slot is
+// K3n for B poses over the same points (alp_normal_equations: B = 1; alp_normal_equations_batch, alp_normal_equations_batch_rows
+// and the device loop of alp_lm.hip): one workgroup per (stripe, slot) pair of host::normal_batch_grid.  Which grid index carries the slot is
 // the launch's choice (`pose_in_x`: the workgroups of one stripe under all poses are dispatched next to each other, so that the
 // stripe's points are fetched from HBM once and found in the cache by the other poses); the sums do not depend on it.
 //   the pose   `list` NULL: pose = slot.  Else (the device loop: the grid is the one for ALL K starts) pose = list[slot], `list`

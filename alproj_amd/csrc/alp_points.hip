@@ -4,8 +4,8 @@
 //                    (VALU-bound; candidates staged in LDS, wave64 DPP reductions)
 //   residual_batch_kernel  observed - projected for B poses, interleaved (least-squares path)
 //   jacobian_kernel  d projected / d parameters for one pose, exact (least-squares path)
-//   normal_kernel    the same rows contracted to J^T J, J^T r and the cost where they are made (f64 MFMA; least-squares path)
-//   normal_poses_kernel  the same for B poses in one launch, one workgroup per (stripe, pose) pair: every pose under the set's
+//   normal_poses_kernel  the same rows contracted to J^T J, J^T r and the cost where they are made (f64 MFMA; least-squares path),
+//                    for B >= 1 poses in one launch, one workgroup per (stripe, pose) pair: every pose under the set's
 //                    weights or under a row of its weight table (alp_points_set_weight_table), all B or the listed ones (alp_lm.hip)
 //   residuals_assigned_kernel  observed - projected with the pose chosen per point (held-out residuals of a cross-validation)
 //
@@ -19,7 +19,7 @@
 // element type T (float: 20 B/vertex streamed per projection pass; double: 40 B/vertex).
 // Planes are padded to a multiple of 1024 elements so that 16-byte vector accesses and
 // whole-workgroup tiles never leave the allocation.
-// The launch shapes (popeval_kernel's stripes x tiles, the residual / Jacobian chunks, normal_kernel's stripes (and their share per pose of a batch), streaming grids, RowDiv) are planned in
+// The launch shapes (popeval_kernel's stripes x tiles, the residual / Jacobian chunks, normal_poses_kernel's stripes per pose, streaming grids, RowDiv) are planned in
 // host/alp_plan.h, HIP-free and checked on the CPU; this unit allocates, records events and launches what it plans.
 #include "alp_internal.h"
 
@@ -517,42 +517,6 @@ int jacobian_impl(alp_points *p, const JacPlan &plan, double *out) {
     });
 }
 
-// alp_normal_equations: normal_kernel over host::normal_grid's stripes, reduce_partials_kernel over its rows, one all-reduce.
-// The scratch holds the plan, the partial rows and the T + 1 sums; T + 1 doubles cross PCIe.
-template <typename TS>
-int normal_impl(alp_points *p, const JacPlan &plan, int loss, double f_scale, double *out) {
-    using Kernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *, double *,
-                            const TS *);
-    static const Kernel kernels[2][4] = {{normal_kernel<TS, ALP_NORMAL_LINEAR>, normal_kernel<TS, ALP_NORMAL_SOFT_L1>,
-                                          normal_kernel<TS, ALP_NORMAL_HUBER>, normal_kernel<TS, ALP_NORMAL_CAUCHY>},
-                                         {normal_kernel<TS, ALP_NORMAL_LINEAR, true>, normal_kernel<TS, ALP_NORMAL_SOFT_L1, true>,
-                                          normal_kernel<TS, ALP_NORMAL_HUBER, true>, normal_kernel<TS, ALP_NORMAL_CAUCHY, true>}};
-    const int D = plan.D, T = D * (D + 1) / 2 + D + 1;
-    const host::NormalGrid g = host::normal_grid(p->n, ctx().cu_count);
-    const size_t plan_bytes = round_up((int64_t)sizeof(JacPlan), 256);
-    char *dev = nullptr;
-    if (int rc = scratch_reserve(plan_bytes + ((size_t)g.blocks * T + T + 1) * sizeof(double), (void **)&dev)) return rc;
-    JacPlan *plan_dev = (JacPlan *)dev;
-    double *partials = (double *)(dev + plan_bytes), *sums = partials + (size_t)g.blocks * T;
-    hipStream_t st = ctx().stream;
-    if (g.blocks > 0) {
-        ALP_HIP(hipMemcpyAsync(plan_dev, &plan, sizeof(JacPlan), hipMemcpyHostToDevice, st));
-        ktime_begin();
-        hipLaunchKernelGGL(kernels[p->w != nullptr][loss], dim3(g.blocks), dim3(256), 0, st, (const TS *)p->x, (const TS *)p->y, (const TS *)p->z,
-                           (const TS *)p->uo, (const TS *)p->vo, p->n, g.groups_per, 1.0 / f_scale, (const JacPlan *)plan_dev, partials,
-                           (const TS *)p->w);
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((T + 31) / 32)), dim3(256), 0, st, partials, g.blocks, T, p->count_slot(), sums);
-        ktime_end();
-        ALP_HIP(hipGetLastError());
-    } else {
-        ALP_HIP(hipMemsetAsync(sums, 0, (size_t)(T + 1) * sizeof(double), st));      // an empty shard still joins the all-reduce
-    }
-    if (int rc = comm_allreduce_sum_f64(sums, T + 1)) return rc;
-    ALP_HIP(hipMemcpyAsync(out, sums, (size_t)(T + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-    ALP_HIP(hipStreamSynchronize(st));           // the plan (stack) must outlive its copy too
-    return ALP_OK;
-}
-
 // The kernel of the multi-pose K3n for a loss and a weighted / unweighted launch
 template <typename TS>
 using NormalPosesKernel = void (*)(const TS *, const TS *, const TS *, const TS *, const TS *, int64_t, int64_t, double, const JacPlan *,
@@ -603,10 +567,11 @@ int normal_poses_enqueue(alp_points *p, const JacPlan *plans, int K, int D, cons
     return comm_allreduce_sum_f64(sums, (int64_t)K * (T + 1));
 }
 
-// alp_normal_equations_batch (row_of_pose NULL) and alp_normal_equations_batch_rows: the scratch holds the B plans, on the row
-// path the B row indices, the partial rows and the sums; one copy of the B x (T + 1) sums comes back.
+// alp_normal_equations (B = 1), alp_normal_equations_batch (both: row_of_pose NULL) and alp_normal_equations_batch_rows: the
+// scratch holds the B plans, on the row path the B row indices, the partial rows and the sums; one copy of the B x (T + 1) sums
+// comes back.
 // ALP_NORMAL_BATCH_ORDER = "stripe" | "pose" (a development switch, tools/probe_normal_batch.py) names the grid index that runs
-// fastest; the sums do not depend on it.
+// fastest; the sums do not depend on it, and with one pose the two orders launch the same stripes in the same order.
 template <typename TS>
 int normal_batch_impl(alp_points *p, const std::vector<JacPlan> &plans, int loss, double f_scale, double *out, const int32_t *row_of_pose) {
     const int64_t B = (int64_t)plans.size();
@@ -1089,19 +1054,8 @@ int alp_jacobian(alp_points_t *p, const double params[ALP_NPARAM], const int32_t
     return p->precision == ALP_F64 ? jacobian_impl<double>(p, plan, out) : jacobian_impl<float>(p, plan, out);
 }
 
-int alp_normal_equations(alp_points_t *p, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int loss, double f_scale,
-                         double *out) {
-    if (int rc = require_init()) return rc;
-    ALP_REQUIRE(p && params && out, "NULL argument");
-    ALP_REQUIRE(loss >= ALP_NORMAL_LINEAR && loss <= ALP_NORMAL_CAUCHY, "unknown loss");
-    ALP_REQUIRE(f_scale > 0 && std::isfinite(f_scale), "f_scale must be a positive finite number");
-    JacPlan plan;
-    if (int rc = jacobian_plan(params, p->origin, target_idx, D, 1, &plan)) return rc;
-    if (!p->uo) return fail(ALP_ESTATE, "alp_normal_equations: observed uv not set");
-    return p->precision == ALP_F64 ? normal_impl<double>(p, plan, loss, f_scale, out) : normal_impl<float>(p, plan, loss, f_scale, out);
-}
-
-// alp_normal_equations_batch (rows = false) and alp_normal_equations_batch_rows under their own names
+// alp_normal_equations (one pose), alp_normal_equations_batch (both: rows = false) and alp_normal_equations_batch_rows under their
+// own names
 static int normal_equations_batch_entry(const char *name, alp_points_t *p, const double *params, int64_t B, bool rows, const int32_t *row_of_pose,
                                         const int32_t *target_idx, int D, int loss, double f_scale, double *out) {
     if (int rc = require_init()) return rc;
@@ -1122,6 +1076,11 @@ static int normal_equations_batch_entry(const char *name, alp_points_t *p, const
     }
     return p->precision == ALP_F64 ? normal_batch_impl<double>(p, plans, loss, f_scale, out, row_of_pose)
                                    : normal_batch_impl<float>(p, plans, loss, f_scale, out, row_of_pose);
+}
+
+int alp_normal_equations(alp_points_t *p, const double params[ALP_NPARAM], const int32_t *target_idx, int D, int loss, double f_scale,
+                         double *out) {
+    return normal_equations_batch_entry(__func__, p, params, 1, false, nullptr, target_idx, D, loss, f_scale, out);
 }
 
 int alp_normal_equations_batch(alp_points_t *p, const double *params, int64_t B, const int32_t *target_idx, int D, int loss,

@@ -373,21 +373,9 @@ void check_plan() {
                 CHECK(c >= 1 && c <= n && (c % 1024 == 0 || c == n), "stage_chunk_points(%" PRId64 ", %" PRId64 ") = %" PRId64, n, pairs, c);
                 CHECK(c * pairs * 16 <= host::RES_CHUNK_BYTES, "chunk of %" PRId64 " points x %" PRId64 " pairs passes the staging limit", c, pairs);
             }
-            // normal_grid: the stripes cover every group exactly once, no workgroup is empty, the partial rows stay within the cap
-            const host::NormalGrid ng = host::normal_grid(n, cu);
-            CHECK(ng.blocks >= 1 && ng.blocks <= host::NORMAL_MAX_BLOCKS && ng.blocks <= (int64_t)cu * host::NORMAL_WG_PER_CU && ng.groups_per >= 1,
-                  "normal_grid(%" PRId64 ", %d) = %d x %" PRId64, n, cu, ng.blocks, ng.groups_per);
-            CHECK((int64_t)ng.blocks * ng.groups_per >= rows && (int64_t)(ng.blocks - 1) * ng.groups_per < rows,
-                  "normal_grid(%" PRId64 ", %d) = %d x %" PRId64 " does not tile %" PRId64 " groups", n, cu, ng.blocks, ng.groups_per, rows);
-            int64_t covered = 0;
-            for (int b = 0; b < ng.blocks; ++b) {            // the kernel's own stripe arithmetic
-                const int64_t beg = (int64_t)b * ng.groups_per * 256, end = std::min<int64_t>(beg + ng.groups_per * 256, n);
-                CHECK(beg == covered && end > beg, "normal_grid(%" PRId64 ", %d): stripe %d is [%" PRId64 ", %" PRId64 ")", n, cu, b, beg, end);
-                covered = end;
-            }
-            CHECK(covered == n, "normal_grid(%" PRId64 ", %d) covers %" PRId64 " points", n, cu, covered);
-            // normal_batch_grid: per pose the same three, B = 1 is normal_grid, blocks x B stays below the aim + B (so the partial
-            // rows, 300 doubles each, stay bounded up to NORMAL_BATCH_MAX poses)
+            // normal_batch_grid: per pose the stripes cover every group exactly once and no workgroup is empty; blocks x B stays
+            // below the aim + B -- for one pose: at most NORMAL_WG_PER_CU per CU and NORMAL_MAX_BLOCKS -- so the partial rows, 300
+            // doubles each, stay bounded up to NORMAL_BATCH_MAX poses
             const int64_t aim = std::min<int64_t>((int64_t)cu * host::NORMAL_WG_PER_CU, host::NORMAL_MAX_BLOCKS);
             for (int64_t B : {1, 2, 3, 7, 64, 255, 256, 1000, 1023, 1024}) {
                 const host::NormalGrid bg = host::normal_batch_grid(n, B, cu);
@@ -395,7 +383,6 @@ void check_plan() {
                           (int64_t)(bg.blocks - 1) * bg.groups_per < rows,
                       "normal_batch_grid(%" PRId64 ", %" PRId64 ", %d) = %d x %" PRId64 " does not tile %" PRId64 " groups", n, B, cu, bg.blocks,
                       bg.groups_per, rows);
-                CHECK(B != 1 || (bg.blocks == ng.blocks && bg.groups_per == ng.groups_per), "normal_batch_grid(%" PRId64 ", 1, %d) is not normal_grid", n, cu);
                 CHECK((int64_t)bg.blocks * B < aim + B && (int64_t)bg.blocks * B * 300 * 8 <= (int64_t)(host::NORMAL_MAX_BLOCKS + host::NORMAL_BATCH_MAX) * 300 * 8,
                       "normal_batch_grid(%" PRId64 ", %" PRId64 ", %d): %d x %" PRId64 " partial rows", n, B, cu, bg.blocks, B);
                 int64_t bcovered = 0;
@@ -408,8 +395,6 @@ void check_plan() {
                 CHECK(bcovered == n, "normal_batch_grid(%" PRId64 ", %" PRId64 ", %d) covers %" PRId64 " points", n, B, cu, bcovered);
             }
         }
-    const host::NormalGrid none = host::normal_grid(0, 256);
-    CHECK(none.blocks == 0 && none.groups_per == 0, "normal_grid(0) launches %d workgroups", none.blocks);
     for (auto &nb : {std::pair<int64_t, int64_t>{0, 1}, {0, 64}, {1127, 0}, {1127, -1}, {0, 0}}) {
         const host::NormalGrid g = host::normal_batch_grid(nb.first, nb.second, 256);
         CHECK(g.blocks == 0 && g.groups_per == 0, "normal_batch_grid(%" PRId64 ", %" PRId64 ") launches %d workgroups", nb.first, nb.second, g.blocks);
@@ -630,7 +615,7 @@ int canary(const char *which) {
 
 // --plan: one query per argument, or per line of stdin when there is none: n,P,f32|f64,V,TC,cu,batched,pairs[,stripes,tile_cols]
 // (the last two: an ALP_POP_GRID pair) -> "stripes tile_cols chunk_points stream_grid confirm_grid";
-// normal,n,cu -> "blocks groups_per" of normal_grid
+// normal,n,cu -> "blocks groups_per" of normal_batch_grid for one pose
 // normal_batch,n,B,cu -> "blocks groups_per" of normal_batch_grid (blocks = the stripes per pose), 1 <= B <= NORMAL_BATCH_MAX
 // mend,n,P,V,TC,cu -> "stripes tile_cols" of mend_grid
 // frame,implicit,grid_h,grid_w,n_tri,w,h,cu,tile_w,tile_h -> "tiles_x tiles plan_grid grid_wgs parked_wgs[0] parked_wgs[1] general_wgs large_wgs
@@ -695,7 +680,7 @@ int plan_query(const char *q) {
             fprintf(stderr, "bad plan query: %s\n", q);
             return 2;
         }
-        const host::NormalGrid g = host::normal_grid(nn, ncu);
+        const host::NormalGrid g = host::normal_batch_grid(nn, 1, ncu);
         printf("%d %lld\n", g.blocks, (long long)g.groups_per);
         return 0;
     }

@@ -1,4 +1,4 @@
-// The derivative of the fold (fold_pose_jacobian) and the plan jacobian_kernel / normal_kernel read (jacobian_plan), written
+// The derivative of the fold (fold_pose_jacobian) and the plan jacobian_kernel / normal_poses_kernel read (jacobian_plan), written
 // once for the host and the device: a forward-mode dual number run through fold_pose_any of host/alp_fold.h.
 // host/alp_host.cpp wraps them as the host functions of host/alp_host.h (argument checks and error texts stay there, the
 // results bit for bit); the device loop of the least-squares iteration (alp_lm.hip) builds the plan of every trial point on

@@ -180,31 +180,18 @@ inline PopGrid mend_grid(int64_t n, int64_t P, int V, int TC, int cu_count) {
     return {(int)nblk, (int)(tiles > 0 ? tiles : 1)};
 }
 
-// The grid of normal_kernel (alp_normal_equations):`blocks` workgroups, each over a stripe of `groups_per` whole groups of 256
-// points (the last stripe may be shorter and its last group ragged); every workgroup writes ONE row of partial sums.
-// Workgroups: NORMAL_WG_PER_CU per CU -- two rounds of the three a CU holds at once (50 KB of LDS each) -- and never more than
-// NORMAL_MAX_BLOCKS, which keeps the partial rows (at most 300 doubles each) below 5 MB whatever the device.  The stripes are
-// then made as long as they must be and the workgroups that would be left without a group are not launched.  n = 0: no launch.
+// The grid of normal_poses_kernel (alp_normal_equations -- B = 1 --, alp_normal_equations_batch, its _rows form and the rounds
+// of alp_lm.hip): B poses over the same points, one workgroup per (stripe, pose) pair, `blocks` stripes per pose -- blocks x B
+// workgroups.  A stripe is `groups_per` whole groups of 256 points (a pose's last stripe may be shorter and its last group
+// ragged); every workgroup writes ONE row of partial sums.
+// Workgroups aimed at: NORMAL_WG_PER_CU per CU -- two rounds of the three a CU holds at once (50 KB of LDS each) -- and never
+// more than NORMAL_MAX_BLOCKS, which keeps the partial rows (at most 300 doubles each) of one pose below 5 MB whatever the
+// device.  They are shared out among the poses: a pose gets ceil(want / B) stripes, at least one, at most one per group; the
+// stripes are then made as long as they must be and those that would be left without a group are not launched.
+// blocks x B < want + B, so the partial rows stay below 7.4 MB up to NORMAL_BATCH_MAX poses.  n = 0 or B < 1: no launch.
 constexpr int NORMAL_WG_PER_CU = 6;
 constexpr int NORMAL_MAX_BLOCKS = 2048;
 struct NormalGrid { int blocks; int64_t groups_per; };
-
-inline NormalGrid normal_grid(int64_t n, int cu_count) {
-    const int64_t groups = (n + 255) / 256;
-    if (groups <= 0) return {0, 0};
-    int64_t want = (int64_t)cu_count * NORMAL_WG_PER_CU;
-    if (want > NORMAL_MAX_BLOCKS) want = NORMAL_MAX_BLOCKS;
-    if (want > groups) want = groups;
-    const int64_t per = (groups + want - 1) / want;
-    return {(int)((groups + per - 1) / per), per};
-}
-
-// The grid of normal_poses_kernel (alp_normal_equations_batch, its _rows form and the rounds of alp_lm.hip): B poses over the same points, one workgroup per (stripe, pose)
-// pair, `blocks` stripes per pose -- blocks x B workgroups, each writing ONE row of partial sums.  The workgroups normal_grid
-// aims at are shared out among the poses: a pose gets ceil(want / B) stripes, at least one, at most one per group; the stripes
-// are then made as long as they must be and those left without a group are dropped, as in normal_grid.  B = 1 is normal_grid
-// itself; blocks x B < want + B, so the partial rows (300 doubles each) stay below 7.4 MB up to NORMAL_BATCH_MAX poses.
-// n = 0 or B < 1: no launch.
 constexpr int NORMAL_BATCH_MAX = 1024;
 
 inline NormalGrid normal_batch_grid(int64_t n, int64_t B, int cu_count) {

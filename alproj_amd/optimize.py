@@ -799,11 +799,31 @@ class LsqOptimizer(BaseOptimizer):
                 raise ValueError(f"starts must be 1 .. {self.MAX_STARTS}")
         return np.ascontiguousarray(np.clip(X0, lower, upper))
 
+    _RESULT_KEYS = ("cost", "iterations", "evaluations", "status", "grad_norm")
+
+    @staticmethod
+    def _check_every_check(device_loop, check_every):
+        if device_loop and (isinstance(check_every, (bool, np.bool_)) or not isinstance(check_every, (int, np.integer)) or check_every < 1):
+            raise ValueError("check_every must be a positive integer")
+
+    def _device_runs(self, pts, cols, bounds, X0, loss, f_scale, ftol, xtol, gtol, max_nfev, check_every, weight_rows=False):
+        """the K = len(X0) runs on the device (alp_lm_*; ``weight_rows``: run k under row k of the set's weight table) -> the K
+        result dicts of normal_lm.  Every rank enqueues the same rounds on the same all-reduced sums and computes the same
+        states; max_nfev stops every start, so the loop ends."""
+        with _lib.LmDevice(pts, _lib.params_vector(self.params_init), cols, bounds[:, 0], bounds[:, 1], X0, loss, f_scale, ftol, xtol,
+                           gtol, max_nfev, weight_rows=weight_rows) as loop:
+            pending = len(X0)
+            while pending:
+                loop.run(int(check_every))
+                pending = loop.wait()
+            rec = loop.get()
+        return [dict(x=rec["x"][k], cost=float(rec["cost"][k]), grad_norm=float(rec["grad_norm"][k]), iterations=int(rec["iterations"][k]),
+                     evaluations=int(rec["evaluations"][k]), status=int(rec["status"][k])) for k in range(len(X0))]
+
     def _optimize_normal(self, bound_widths, loss, f_scale, ftol=1e-10, xtol=1e-10, gtol=1e-10, max_nfev=None, precision=None,
                          starts=None, seed=None, device_loop=False, check_every=8, **kwargs):
         """optimize(method="normal"); every refusal comes before the device is touched"""
-        if device_loop and (isinstance(check_every, (bool, np.bool_)) or not isinstance(check_every, (int, np.integer)) or check_every < 1):
-            raise ValueError("check_every must be a positive integer")
+        self._check_every_check(device_loop, check_every)
         if "jac" in kwargs:
             raise ValueError("method='normal' takes no jac=: it solves on J^T J and J^T r, no Jacobian exists in it")
         if kwargs:
@@ -814,78 +834,49 @@ class LsqOptimizer(BaseOptimizer):
         _lib.normal_loss_check(loss, f_scale)
         bounds = bounds_to_array(self.params_init, self.target_params, bound_widths)
         X0 = None if starts is None else self._start_matrix(starts, seed, bounds[:, 0], bounds[:, 1])
-        single = X0 is None
+        single = X0 is None                  # decides the reporting alone: no "start" key, start_results not set
         if device_loop and single:           # the K = 1 case, from params_init (clipped on the device, as normal_lm clips x0)
             X0 = np.ascontiguousarray(np.asarray(self.target_params_init, dtype=np.float64)[None, :])
         pts = self._device_points(precision)
-        keys = ("cost", "iterations", "evaluations", "status", "grad_norm")
         try:
             _, world = _lib.comm_info()
+            # rank 0's starts (its own draw when seed is None) are everybody's: the sums arrive all-reduced, so every rank then
+            # runs the same iterations in lockstep
+            if world > 1 and X0 is not None:
+                _lib.comm_bcast(X0, root=0)
             if device_loop:
-                # the K runs on the device (alp_lm_*): rank 0's starts are everybody's, every rank enqueues the same rounds on the
-                # same all-reduced sums and computes the same states; max_nfev stops every start, so the loop ends
-                if world > 1:
-                    _lib.comm_bcast(X0, root=0)
-                with _lib.LmDevice(pts, _lib.params_vector(self.params_init), cols, bounds[:, 0], bounds[:, 1], X0, loss, f_scale, ftol,
-                                   xtol, gtol, max_nfev) as loop:
-                    pending = len(X0)
-                    while pending:
-                        loop.run(int(check_every))
-                        pending = loop.wait()
-                    rec = loop.get()
-                runs = [dict(x=rec["x"][k], cost=float(rec["cost"][k]), grad_norm=float(rec["grad_norm"][k]),
-                             iterations=int(rec["iterations"][k]), evaluations=int(rec["evaluations"][k]), status=int(rec["status"][k]))
-                        for k in range(len(X0))]
-                finals = np.ascontiguousarray(rec["x"], dtype=np.float64)
-                if world > 1:
-                    _lib.comm_bcast(finals, root=0)
-                errs, _ = pts.eval_population(self._candidate_matrix(finals), _lib.LOSS_MEAN_DIST, 0.0, want_argmin=False)
-                if single:
-                    res, best, err = runs[0], finals[0], errs[:1]
-                    X0 = None
-            elif X0 is None:
+                runs = self._device_runs(pts, cols, bounds, X0, loss, f_scale, ftol, xtol, gtol, max_nfev, check_every)
+            elif single:
                 def sums(values):
                     return pts.normal_equations(self._candidate_matrix(values)[0], cols, loss, f_scale)[:3]
 
-                res = normal_lm(sums, self.target_params_init, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol,
-                                max_nfev=max_nfev)
-                # every rank has run the same iteration on the same all-reduced sums; rank 0's solution is broadcast before the
-                # final error, a collective over the shards, as for the other methods
-                best = np.ascontiguousarray(res["x"], dtype=np.float64)
-                if world > 1:
-                    _lib.comm_bcast(best, root=0)
-                err, _ = pts.eval_population(self._candidate_matrix(best), _lib.LOSS_MEAN_DIST, 0.0)
-            else:
-                # rank 0's starts (its own draw when seed is None) are everybody's: the sums arrive all-reduced, so every rank
-                # then runs the same K iterations in lockstep, one alp_normal_equations_batch call per round
-                if world > 1:
-                    _lib.comm_bcast(X0, root=0)
-
+                runs = [normal_lm(sums, self.target_params_init, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol,
+                                  max_nfev=max_nfev)]
+            else:                            # one alp_normal_equations_batch call per round
                 def sums_batch(X):
                     return pts.normal_equations_batch(self._candidate_matrix(X), cols, loss, f_scale)[:3]
 
                 runs = normal_lm_batch(sums_batch, X0, bounds[:, 0], bounds[:, 1], ftol=ftol, xtol=xtol, gtol=gtol, max_nfev=max_nfev)
-                finals = np.ascontiguousarray([r["x"] for r in runs], dtype=np.float64)
-                if world > 1:
-                    _lib.comm_bcast(finals, root=0)
-                errs, _ = pts.eval_population(self._candidate_matrix(finals), _lib.LOSS_MEAN_DIST, 0.0, want_argmin=False)
+            # rank 0's solutions are broadcast before the final errors, a collective over the shards, as for the other methods
+            finals = np.ascontiguousarray([r["x"] for r in runs], dtype=np.float64)
+            if world > 1:
+                _lib.comm_bcast(finals, root=0)
+            errs, _ = pts.eval_population(self._candidate_matrix(finals), _lib.LOSS_MEAN_DIST, 0.0, want_argmin=False)
         finally:
             pts.close()
-        if X0 is None:
-            self.result_ = {k: res[k] for k in keys}
-            return self._result_params(best), float(err[0])
-        self.start_results = [(self._result_params(x), float(e), {k: r[k] for k in keys}) for x, e, r in zip(finals, errs, runs)]
+        results = [(self._result_params(x), float(e), {k: r[k] for k in self._RESULT_KEYS}) for x, e, r in zip(finals, errs, runs)]
+        if single:
+            self.result_ = results[0][2]
+            return results[0][0], results[0][1]
+        self.start_results = results
         b = best_start([r["cost"] for r in runs])
-        self.result_ = dict(self.start_results[b][2], start=b)
-        return self.start_results[b][0], self.start_results[b][1]
+        self.result_ = dict(results[b][2], start=b)
+        return results[b][0], results[b][1]
 
     # -- K fits under K weight rows: cross-validation and bootstrap ---------------------------
-    _RESULT_KEYS = ("cost", "iterations", "evaluations", "status", "grad_norm")
-
     def _resample_checks(self, loss, f_scale, device_loop, check_every):
         """the refusals cross_validate and bootstrap share with optimize(method="normal"): host arithmetic"""
-        if device_loop and (isinstance(check_every, (bool, np.bool_)) or not isinstance(check_every, (int, np.integer)) or check_every < 1):
-            raise ValueError("check_every must be a positive integer")
+        self._check_every_check(device_loop, check_every)
         _lib.normal_loss_check(loss, f_scale)
         return _jacobian_targets(self.target_params)
 
@@ -916,15 +907,7 @@ class LsqOptimizer(BaseOptimizer):
         pts.set_weight_table(table)
         X0 = np.ascontiguousarray(np.tile(np.clip(np.asarray(self.target_params_init, dtype=np.float64), bounds[:, 0], bounds[:, 1]), (K, 1)))
         if device_loop:
-            with _lib.LmDevice(pts, _lib.params_vector(self.params_init), cols, bounds[:, 0], bounds[:, 1], X0, loss, f_scale, ftol, xtol,
-                               gtol, max_nfev, weight_rows=True) as loop:
-                pending = K
-                while pending:
-                    loop.run(int(check_every))
-                    pending = loop.wait()
-                rec = loop.get()
-            runs = [dict(x=rec["x"][k], cost=float(rec["cost"][k]), grad_norm=float(rec["grad_norm"][k]), iterations=int(rec["iterations"][k]),
-                         evaluations=int(rec["evaluations"][k]), status=int(rec["status"][k])) for k in range(K)]
+            runs = self._device_runs(pts, cols, bounds, X0, loss, f_scale, ftol, xtol, gtol, max_nfev, check_every, weight_rows=True)
         else:
             def sums_rows(X, starts):
                 return pts.normal_equations_batch_rows(self._candidate_matrix(X), starts, cols, loss, f_scale)[:3]

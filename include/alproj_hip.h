@@ -236,9 +236,11 @@ int alp_normal_equations(alp_points_t *pts, const double params[ALP_NPARAM], con
  * params: B x ALP_NPARAM row-major, 1 <= B <= 1024; targets, loss and f_scale are shared by the rows.  out: B rows of
  * D (D + 1) / 2 + D + 2 doubles, row b in alp_normal_equations' layout for params row b (the point count is repeated in every
  * row).  One workgroup per (stripe of points, pose) pair; a pose's stripes are added in stripe order, no atomics: a row does
- * not depend on the other rows of the call, and the same call gives the same bits.  Where the set is one stripe either way
- * (up to 256 points) a row has the bits of the single call; above, the stripes are cut differently and the two agree to the
- * reassociation of the sums.  With a communicator: one all-reduce of B (D (D + 1) / 2 + D + 2) doubles.  n = 0 gives B rows
+ * not depend on the other rows of the call, and the same call gives the same bits.  alp_normal_equations is the B = 1 case
+ * of this launch: a row has the bits of the single call wherever B poses get the stripes one pose gets -- the device's
+ * workgroups (6 per CU, at most 2048) are shared out among the poses, ceil(that / B) stripes each, at most one per group of
+ * 256 points; so always up to 256 points, and for any n while that share is at least the number of groups.  Elsewhere the
+ * stripes are cut differently and the two agree to the reassociation of the sums.  With a communicator: one all-reduce of B (D (D + 1) / 2 + D + 2) doubles.  n = 0 gives B rows
  * of zeros.  Errors as for alp_normal_equations (same codes; ALP_ESTATE without observed uv), and ALP_EINVAL for B < 1 or
  * B > 1024. */
 int alp_normal_equations_batch(alp_points_t *pts, const double *params, int64_t B, const int32_t *target_idx, int D, int loss,

@@ -2,8 +2,10 @@
 LsqOptimizer.optimize(method="normal", starts=...).
 
 A row of the batch against the single call (alp_normal_equations) at the same pose: the per-point arithmetic is the same code,
-so the two differ by the order of the additions alone, and only where the points are cut into stripes differently.  Up to 256
-points there is one group and so one stripe either way: bit for bit.  Above: both are within 2 m eps of the normalisers
+so the two differ by the order of the additions alone, and only where the points are cut into stripes differently.  A row
+depends on its pose and its stripes alone: where B poses get the stripes one pose gets (host/alp_plan.h: normal_batch_grid(n, B,
+cus) == normal_batch_grid(n, 1, cus) -- up to 256 points there is one group and so one stripe either way) it is bit for bit.
+Elsewhere: both are within 2 m eps of the normalisers
 (m = 2N rows, tests/test_gpu_normal.py's derivation) of the library's own Jacobian and residuals contracted on the host, and
 the row is held to that file's bound against those, 4 m eps.  Against the complex-step oracle: tests/test_gpu_normal.py's TOL.
 Everything else here is bit for bit: a row does not depend on the other rows, on their order or on their number as long as
@@ -85,6 +87,9 @@ def test_a_batch_of_one_is_the_single_call_bit_for_bit(L, precision):
 def test_rows_against_single_calls(L, n):
     xyz, uv, origin = points(n)
     cand = three_poses()
+    cus = L.device_info()["cu_count"]
+    same_stripes = nb.normal_batch_grid(n, 3, cus) == nb.normal_batch_grid(n, 1, cus)
+    assert same_stripes or n > 256
     with L.Points(xyz, origin, "f64") as pts:
         pts.set_observed(uv)
         for D in (1, 15, 16, 23):
@@ -92,11 +97,28 @@ def test_rows_against_single_calls(L, n):
             got = pts.normal_equations_batch(cand, idx(targets))
             assert got[0].shape == (3, D, D) and got[1].shape == (3, D) and got[2].shape == (3,) and got[3] == n
             for b in range(3):
-                if n <= 256:
+                if same_stripes:
                     assert_same_bits(row(got, b), pts.normal_equations(cand[b], idx(targets)))
                 else:
                     assert_reassociation_only(row(got, b), host_pieces(L, pts, cand[b], targets))
         assert (got[2][0] != got[2][1]) and (got[2][1] != got[2][2])             # three poses, three costs
+
+
+def test_rows_of_other_stripes_against_the_host_contraction(L):
+    """64 poses over 100 003 points cut a pose's 391 groups into far fewer stripes than one pose gets (24 against 391 on 256
+    CUs): the same sums in another order"""
+    n, D, B = 100_003, 23, 64
+    xyz, uv, origin = points(n)
+    cand = poses(B, seed=B)
+    cus = L.device_info()["cu_count"]
+    assert nb.normal_batch_grid(n, B, cus) != nb.normal_batch_grid(n, 1, cus)
+    targets = D_TARGETS[D]
+    with L.Points(xyz, origin, "f64") as pts:
+        pts.set_observed(uv)
+        got = pts.normal_equations_batch(cand, idx(targets))
+        assert got[0].shape == (B, D, D) and got[3] == n
+        for b in (0, B - 1):
+            assert_reassociation_only(row(got, b), host_pieces(L, pts, cand[b], targets))
 
 
 # ---------------------------------------------------------------------------------------------------- 8. rows against the oracle

@@ -1,4 +1,4 @@
-// The lane map of v_mfma_f64_16x16x4_f64 as normal_kernel (alproj_amd/csrc/alp_point_kernels.h, K3n) relies on it, checked with
+// The lane map of v_mfma_f64_16x16x4_f64 as normal_body (alproj_amd/csrc/alp_point_kernels.h, K3n) relies on it, checked with
 // exact small-integer data: one wave, a 64 x 24 tile R of integers in -7..7 (so that every product and sum is exact in
 // float64), stored column-major with the kernel's row stride; the wave forms the Gram matrix R^T R in the three blocks 00, 01,
 // 11 with the kernel's own operand reads (A = B = R[k0 + (l >> 4)][16 b + (l & 15)]) and parks it with the kernel's own C / D

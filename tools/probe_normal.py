@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""alp_normal_equations (normal_kernel: J^T J, J^T r and the cost formed on the device) against the path it replaces, at
+"""alp_normal_equations (normal_poses_kernel for one pose: J^T J, J^T r and the cost formed on the device) against the path it replaces, at
 bench.py's f1 shape: 10 M GCP-like points in a float64 set, D = 21 (g5's targets).  One process, one run, one JSON line each:
 
   (a) "host_contraction": pts.jacobian + pts.residuals + J.T @ J and J.T @ r in numpy -- the (2N, D) matrix crosses PCIe
       (3.36 GB at 10 M points) and one host process contracts it;
   (b) "normal_equations": one pts.normal_equations call -- 2.4 KB cross PCIe;
   (c) the kernel sections of either, summed by the library's HIP-event timer (alp_kernel_timing): jacobian_kernel's 13
-      launches next to normal_kernel + reduce_partials_kernel.
+      launches next to normal_poses_kernel + reduce_normal_poses_kernel.
   --big N: one more line, (b) alone on N float32 points (100 M: the size of the bench's grid set).
 
 The condition the change is held to: call_ms of (b) <= 0.5 x call_ms of (a).  The two results are compared as well (the

@@ -11,7 +11,8 @@ the normal-equation entry points against the parent commit's.  One process, one 
              stripe | pose: which grid index runs fastest).  Condition, for the order the library ships: the batch's median per
              pose is not above the single call's median by more than the single call's own spread, (max - min) / median.
   single (c) --parent-lib PATH: the parent's library (loaded twice, as tools/probe_mend.py does) and this one in one process.
-             Bits: alp_normal_equations_batch (B = 1, 8, 64; unweighted and weighted), alp_normal_equations_batch_rows (repeated
+             Bits: alp_normal_equations (every loss, D = 9 and 23; unweighted and weighted), alp_normal_equations_batch (B = 1, 8,
+             64; unweighted and weighted), alp_normal_equations_batch_rows (repeated
              and permuted rows) and one round of the device loop with and without weight rows, read back through alp_lm_get, at
              n = 257 and 100 003, float64 and float32, linear and huber: no bit may differ between the three.  Time, alternated
              round by round: the whole call and the kernel section of alp_normal_equations and alp_normal_equations_batch at the
@@ -236,8 +237,10 @@ def same_bits(outs):
 
 
 def single_bits(libs, args):
-    """every multi-pose call and a round of the device loop in the three libraries: rows that differ in any bit, by case"""
+    """the single call, every multi-pose call and a round of the device loop in the three libraries: rows that differ in any bit,
+    by case"""
     differ, cases = [], 0
+    cols23 = [k for k, name in enumerate(L.PARAM_KEYS) if name not in ("w", "h")]
     for n in (257, 100_003):
         xyz, origin, (u, v), pv, cand, cols = problem(n, TARGETS_D9, 64, 3)
         uv = np.column_stack([u, v])
@@ -256,6 +259,9 @@ def single_bits(libs, args):
                 if weighted:
                     for (_, lib), h in zip(libs, handles):
                         lib.set_weights(h, w[1])
+                for loss in (0, 1, 2, 3):                    # the single call: every loss, D = 9 and all 23 targets
+                    for tc in (cols, cols23):
+                        case(f"single D={len(tc)} loss={loss} weighted={weighted}", lambda lib, h: lib.normal(h, pv, tc, loss))
                 for loss in (0, 2):                          # linear, huber
                     for B in (1, 8, 64):
                         case(f"batch B={B} loss={loss} weighted={weighted}", lambda lib, h: lib.normal(h, cand[:B], cols, loss))
