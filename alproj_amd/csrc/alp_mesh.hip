@@ -22,7 +22,7 @@ __device__ __forceinline__ double surface_z(const Z *dsm, long long i, double z_
     return z;
 }
 
-// min over the clamped elevations (>= 0, so the float64 bit patterns order like the values)
+// min over the clamped elevations (>= +0.0 once the sign of a zero is dropped, so the float64 bit patterns order like the values)
 template <typename Z>
 __global__ __launch_bounds__(256) void surface_zmin_kernel(const Z *__restrict__ dsm, long long n, double z_max,
                                                            unsigned long long *__restrict__ out) {
@@ -46,6 +46,9 @@ __global__ __launch_bounds__(256) void surface_zmin_kernel(const Z *__restrict__
         const double z = surface_z(dsm, i, z_max);
         m = z < m ? z : m;
     }
+    // a -0.0 elevation passes the clamp (-0.0 < 0 is false) and is this lane's minimum wherever it is the lowest; its bit
+    // pattern 0x8000... lies above +inf's as an unsigned integer, so atomicMin would never take it: +0.0 from here on
+    if (m <= 0) m = 0;
     for (int d = 32; d >= 1; d >>= 1) {
         const double o = __shfl_xor(m, d);
         m = o < m ? o : m;
