@@ -1012,7 +1012,7 @@ __global__ __launch_bounds__(256) void residuals_assigned_kernel(const TS *__res
 }
 
 // TS = element type of the planes in HBM, T = arithmetic type (TS = float with T = double is the
-// float64 re-evaluation of a float32 point set: alp_eval_population's argmin confirmation)
+// float64 re-evaluation of a float32 point set: popeval_counted_kernel)
 // WEIGHTED: the weight plane `wts` is read beside uo / vo, at the same index (the masked lanes' stand-in index included, whose
 // weight is then set to 0); otherwise wts is never read.
 template <typename T, int LOSS, int V, bool MASKED, bool SHARED_POSE, typename TS = T, bool EXACT_POLES = false, bool LENS_FREE = false,
@@ -1161,22 +1161,21 @@ __global__ __launch_bounds__(256, Cfg::MINW) void popeval_kernel(
     popeval_body<T, LOSS, Cfg, SHARED_POSE, TS, LENS_FREE, WEIGHTED>(x, y, z, uo, vo, n, cands, P, f_scale, partials, cands_general, wts);
 }
 
-// ------------------------------------------------------------------ K2m: the mend pass of a float32 population evaluation
-// (alp_points_set_mend; alp_points.hip: mend_launch).  Behind the all-reduce of the float32 sums:
+// ------------------------------------------------------------------ K2m: float64 arithmetic on the stored points of a float32 set
+// The counted pass (alp_points.hip: counted_pass) over the first `count` of a list of float64 records, the count a device word:
+//   popeval_counted_kernel  the float64-arithmetic evaluation of those records on the float32 planes
+//   reduce_counted_kernel   its partial rows in fixed order, zeros behind the count
+// The argmin confirmation (confirm_losses) uploads its count in front of its records.  The mend pass (alp_points_set_mend;
+// mend_launch) runs it behind the all-reduce of the float32 sums, between
 //   mend_select_kernel      the candidates whose sum is not finite, compacted in ascending order, and their float64 records
-//   popeval_counted_kernel  the float64-arithmetic evaluation of those (the argmin confirmation's kernel, count from the device)
-//   mend_reduce_kernel      its partial rows in fixed order
-//   (the all-reduce of the mended sums when a communicator exists)
-//   mend_scatter_kernel     sums[idx[k]] = mended[k]
-// MendCount: what the pass keeps on the device between its kernels and for alp_eval_population_mended.
+//   mend_scatter_kernel     sums[idx[k]] = mended[k]  (behind the all-reduce of the mended sums when a communicator exists)
 struct MendCount {
-    long long last;       // candidates selected by the last pass
-    long long total;      // ... since mend was enabled
+    long long last;       // records to evaluate: the candidates selected by the last mend pass, or the confirmation's K
+    long long total;      // (mend pass, which keeps its word for alp_eval_population_mended) ... since mend was enabled
 };
 
-// popeval_kernel<double, LOSS, PopCfg<double>, false, float> over the first cnt->last records: the grid is planned for the worst
-// case (host::mend_grid: every candidate selected), and a workgroup whose first tile lies at or beyond the count returns at
-// once.  The partial rows are `count` doubles long.
+// popeval_body in float64 on float32 planes over the first cnt->last records, partial rows of `count` doubles.  The grid may be
+// planned for more (host::mend_grid: every candidate selected): a workgroup whose first tile lies at or beyond the count returns at once.
 template <int LOSS, bool WEIGHTED = false>
 __global__ __launch_bounds__(256, PopCfg<double>::MINW) void popeval_counted_kernel(
     const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, const float *__restrict__ uo,
@@ -1227,10 +1226,11 @@ __global__ __launch_bounds__(256) void mend_select_kernel(const double *__restri
     }
 }
 
-// mended[k] = sum over the stripes of partials[b][k] (fixed order: reduce_partials_kernel's) for k < count, 0 for count <= k < P:
-// the buffer has a fixed size for the all-reduce.  One workgroup handles 32 candidates x 8 row-groups.
-__global__ __launch_bounds__(256) void mend_reduce_kernel(const double *__restrict__ partials, int nblk, int P,
-                                                          const MendCount *__restrict__ cnt, double *__restrict__ mended) {
+// out[k] = sum over the stripes of partials[b][k] (reduce_partials_kernel's order) for k < count = cnt->last, 0 for count <= k < width
+// (a fixed size for the all-reduce); `slot`: out[width] = n_local as well, the count slot the confirmation's buffer has.
+__global__ __launch_bounds__(256) void reduce_counted_kernel(const double *__restrict__ partials, int nblk, int width,
+                                                             const MendCount *__restrict__ cnt, double *__restrict__ out, bool slot,
+                                                             double n_local) {
     __shared__ double s[8][32];
     const int count = (int)cnt->last;
     const int cl = threadIdx.x & 31;
@@ -1241,12 +1241,13 @@ __global__ __launch_bounds__(256) void mend_reduce_kernel(const double *__restri
         for (int b = g; b < nblk; b += 8) acc += partials[(int64_t)b * count + c];
     s[g][cl] = acc;
     __syncthreads();
-    if (g == 0 && c < P) {
+    if (g == 0 && c < width) {
         double t = s[0][cl];
 #pragma unroll
         for (int k = 1; k < 8; ++k) t += s[k][cl];
-        mended[c] = t;
+        out[c] = t;
     }
+    if (slot && blockIdx.x == 0 && threadIdx.x == 0) out[width] = n_local;
 }
 
 __global__ __launch_bounds__(256) void mend_scatter_kernel(const int *__restrict__ idx, const double *__restrict__ mended,

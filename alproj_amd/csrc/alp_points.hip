@@ -2,6 +2,7 @@
 //   project_kernel   forward projection of every point with ONE pose (HBM-bound stream)
 //   popeval_kernel   P candidate poses x every point -> per-candidate loss sums
 //                    (VALU-bound; candidates staged in LDS, wave64 DPP reductions)
+//   popeval_counted_kernel  its body in float64 on a float32 set's planes: argmin confirmation and mend pass (counted_pass)
 //   residual_batch_kernel  observed - projected for B poses, interleaved (least-squares path)
 //   jacobian_kernel  d projected / d parameters for one pose, exact (least-squares path)
 //   normal_poses_kernel  the same rows contracted to J^T J, J^T r and the cost where they are made (f64 MFMA; least-squares path),
@@ -218,6 +219,25 @@ int ensure_pop_events(alp_points *p) {
     return ALP_OK;
 }
 
+// ------------------------------------------------------------------ float64 arithmetic on the stored points of a float32 set
+// The counted pass, enqueue only: the first cnt->last of the records `recs` over the planes of `p` on the grid `g`, their partial
+// rows (g.stripes x count doubles) added in fixed order into out[0 .. width), zeros behind the count; `slot`: out[width] = the
+// set's count slot.  The count and the records lie on the device, in stream order, before this.
+int counted_pass(alp_points *p, const PoseRec<double> *recs, const MendCount *cnt, const host::PopGrid &g, int loss_kind, double f_scale,
+                 double *partials, double *out, int64_t width, bool slot) {
+    static const decltype(&popeval_counted_kernel<ALP_LOSS_HUBER>) kernels[2][2] = {
+        {popeval_counted_kernel<ALP_LOSS_MEAN_DIST>, popeval_counted_kernel<ALP_LOSS_HUBER>},
+        {popeval_counted_kernel<ALP_LOSS_MEAN_DIST, true>, popeval_counted_kernel<ALP_LOSS_HUBER, true>}};
+    hipLaunchKernelGGL(kernels[p->w != nullptr][loss_kind == ALP_LOSS_HUBER], dim3(g.stripes, g.tile_cols), dim3(256), 0, ctx().stream,
+                       (const float *)p->x, (const float *)p->y, (const float *)p->z, (const float *)p->uo, (const float *)p->vo, p->n, recs, cnt,
+                       f_scale, partials, (const float *)p->w);
+    ALP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(reduce_counted_kernel, dim3((unsigned)((width + 31) / 32)), dim3(256), 0, ctx().stream, (const double *)partials,
+                       g.stripes, (int)width, cnt, out, slot, p->count_slot());
+    ALP_HIP(hipGetLastError());
+    return ALP_OK;
+}
+
 // ------------------------------------------------------------------ the mend pass (alp_points_set_mend)
 // One allocation for cap candidates: the compacted indices, the mended sums, the float64 records.
 int *mend_idx(const alp_points *p) { return (int *)p->mend_dev; }
@@ -237,28 +257,17 @@ int ensure_mend_scratch(alp_points *p) {
     return ALP_OK;
 }
 
-// Behind the all-reduce of the float32 sums in p->sums_dev (identical on every rank, so every rank selects the same
-// candidates): every candidate whose sum is not finite gets the sum float64 arithmetic gives on the stored points.  No host
-// round trip: the count stays on the device.  `g` = host::mend_grid for (n, P); p->partials holds g.stripes x P doubles and
-// is free again (reduce_partials_kernel has read it, in stream order).
+// Behind the all-reduce of the float32 sums in p->sums_dev (identical on every rank, so every rank selects the same candidates):
+// every candidate whose sum is not finite gets the sum float64 arithmetic gives on the stored points.  No host round trip: the
+// count stays on the device.  `g` = host::mend_grid for (n, P); p->partials holds g.stripes x P doubles and is free again
+// (reduce_partials_kernel has read it, in stream order).  No count slot: the records start right behind the mend_cap sums.
 int mend_launch(alp_points *p, int64_t P, int loss_kind, double f_scale, const double *params_dev, const host::PopGrid &g) {
     hipStream_t st = ctx().stream;
     MendCount *cnt = (MendCount *)p->mend_cnt;
-    const float *x = (const float *)p->x, *y = (const float *)p->y, *z = (const float *)p->z;
-    const float *uo = (const float *)p->uo, *vo = (const float *)p->vo;
     hipLaunchKernelGGL(mend_select_kernel, dim3(1), dim3(256), 0, st, (const double *)p->sums_dev, (int)P, params_dev, p->origin[0],
                        p->origin[1], p->origin[2], mend_idx(p), mend_recs(p), cnt);
     ALP_HIP(hipGetLastError());
-    using Kernel = void (*)(const float *, const float *, const float *, const float *, const float *, int64_t, const PoseRec<double> *,
-                            const MendCount *, double, double *, const float *);
-    static const Kernel kernels[2][2] = {{popeval_counted_kernel<ALP_LOSS_MEAN_DIST>, popeval_counted_kernel<ALP_LOSS_HUBER>},
-                                         {popeval_counted_kernel<ALP_LOSS_MEAN_DIST, true>, popeval_counted_kernel<ALP_LOSS_HUBER, true>}};
-    hipLaunchKernelGGL(kernels[p->w != nullptr][loss_kind == ALP_LOSS_HUBER], dim3(g.stripes, g.tile_cols), dim3(256), 0, st, x, y, z, uo,
-                       vo, p->n, (const PoseRec<double> *)mend_recs(p), (const MendCount *)cnt, f_scale, p->partials, (const float *)p->w);
-    ALP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mend_reduce_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, st, (const double *)p->partials, g.stripes,
-                       (int)P, (const MendCount *)cnt, mend_sums(p));
-    ALP_HIP(hipGetLastError());
+    if (int rc = counted_pass(p, mend_recs(p), cnt, g, loss_kind, f_scale, p->partials, mend_sums(p), P, false)) return rc;
     if (int rc = comm_allreduce_sum_f64(mend_sums(p), P)) return rc;
     hipLaunchKernelGGL(mend_scatter_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (const int *)mend_idx(p),
                        (const double *)mend_sums(p), (const MendCount *)cnt, p->sums_dev);
@@ -395,36 +404,24 @@ int enqueue_popeval(alp_points *p, const double *cand, int64_t P, int loss_kind,
 }
 
 // float64 re-evaluation of K <= CONFIRM_MAX candidates of a float32 point set (same stored
-// coordinates, double arithmetic, same fixed-order reduction and the same all-reduce):
-// sums_out[0..K) = loss sums, sums_out[K] = vertex count (the sum of the weights on a weighted set).  Synchronous.
-int confirm_losses(alp_points *p, const double *cand, const int64_t *which, int K, int loss_kind, double f_scale,
-                   double *sums_out) {
-    const int nblk = host::confirm_grid(p->n, ctx().cu_count);
-    const size_t rec_bytes = (size_t)CONFIRM_MAX * sizeof(PoseRec<double>);
-    if (int rc = p->conf_dev.reserve(rec_bytes + (size_t)(nblk + 2) * CONFIRM_MAX * sizeof(double))) return rc;
+// coordinates, double arithmetic, same fixed-order reduction and the same all-reduce): the counted pass with a count the host
+// knows.  sums_out[0..K) = loss sums, sums_out[K] = vertex count (the sum of the weights on a weighted set).  Synchronous.
+int confirm_losses(alp_points *p, const double *cand, const int64_t *which, int K, int loss_kind, double f_scale, double *sums_out) {
+    const host::PopGrid g = {host::confirm_grid(p->n, ctx().cu_count), 1};
+    // the count word {K, 0} and, 256 bytes behind it, the K records: one copy, which the stream runs before the kernels
+    struct Upload { MendCount cnt; char pad[256 - sizeof(MendCount)]; PoseRec<double> recs[CONFIRM_MAX]; } up = {};
+    if (int rc = p->conf_dev.reserve(sizeof(Upload) + (size_t)(g.stripes + 2) * CONFIRM_MAX * sizeof(double))) return rc;
     if (int rc = p->conf_host.reserve((CONFIRM_MAX + 1) * sizeof(double))) return rc;
-    PoseRec<double> recs[CONFIRM_MAX];
-    for (int k = 0; k < K; ++k) fold_pose_t<double>(cand + which[k] * ALP_NPARAM, p->origin, &recs[k]);
-    PoseRec<double> *recs_dev = (PoseRec<double> *)p->conf_dev;
-    double *partials = (double *)((char *)p->conf_dev + rec_bytes);
-    double *sums_dev = partials + (size_t)nblk * CONFIRM_MAX;
-    ALP_HIP(hipMemcpyAsync(recs_dev, recs, (size_t)K * sizeof(PoseRec<double>), hipMemcpyHostToDevice, ctx().stream));
-    const float *x = (const float *)p->x, *y = (const float *)p->y, *z = (const float *)p->z;
-    const float *uo = (const float *)p->uo, *vo = (const float *)p->vo;
-    using Kernel = void (*)(const float *, const float *, const float *, const float *, const float *, int64_t, const PoseRec<double> *, int,
-                            double, double *, const PoseRec<double> *, const float *);
-    static const Kernel kernels[2][2] = {{popeval_kernel<double, ALP_LOSS_MEAN_DIST, PopCfg<double>, false, float>,
-                                          popeval_kernel<double, ALP_LOSS_HUBER, PopCfg<double>, false, float>},
-                                         {popeval_kernel<double, ALP_LOSS_MEAN_DIST, PopCfg<double>, false, float, false, true>,
-                                          popeval_kernel<double, ALP_LOSS_HUBER, PopCfg<double>, false, float, false, true>}};
-    hipLaunchKernelGGL(kernels[p->w != nullptr][loss_kind == ALP_LOSS_HUBER], dim3(nblk), dim3(256), 0, ctx().stream, x, y, z, uo, vo, p->n,
-                       (const PoseRec<double> *)recs_dev, K, f_scale, partials, (const PoseRec<double> *)recs_dev, (const float *)p->w);
-    ALP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, ctx().stream, partials, nblk, K, p->count_slot(), sums_dev);
-    ALP_HIP(hipGetLastError());
+    up.cnt.last = K;
+    for (int k = 0; k < K; ++k) fold_pose_t<double>(cand + which[k] * ALP_NPARAM, p->origin, &up.recs[k]);
+    const Upload *up_dev = (const Upload *)p->conf_dev;
+    double *partials = (double *)(up_dev + 1);
+    double *sums_dev = partials + (size_t)g.stripes * CONFIRM_MAX;
+    ALP_HIP(hipMemcpyAsync(p->conf_dev, &up, (const char *)&up.recs[K] - (const char *)&up, hipMemcpyHostToDevice, ctx().stream));
+    if (int rc = counted_pass(p, up_dev->recs, &up_dev->cnt, g, loss_kind, f_scale, partials, sums_dev, K, true)) return rc;
     if (int rc = comm_allreduce_sum_f64(sums_dev, K + 1)) return rc;
     ALP_HIP(hipMemcpyAsync(p->conf_host, sums_dev, (size_t)(K + 1) * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-    ALP_HIP(hipStreamSynchronize(ctx().stream));      // recs (stack) must outlive the H2D copy too
+    ALP_HIP(hipStreamSynchronize(ctx().stream));      // `up` (stack) must outlive the H2D copy too
     memcpy(sums_out, p->conf_host, (size_t)(K + 1) * sizeof(double));
     return ALP_OK;
 }

@@ -46,10 +46,10 @@ struct alp_points {
     int pending_loss = 0;
     double pending_f_scale = 0;
     std::vector<double> cand_copy;   // the P x 25 parameter vectors of the pending call (argmin confirmation)
-    // argmin confirmation (float32 sets): float64 records, partial sums and sums of up to CONFIRM_MAX candidates
     // last population evaluation: before the kernels, after them, after the all-reduce, after the mend pass
     alp::Event ev[4];
     bool timed = false;
+    // argmin confirmation (float32 sets): the count word, float64 records, partial sums and sums of up to CONFIRM_MAX candidates
     alp::DeviceBuffer<> conf_dev;
     alp::PinnedBuffer<double> conf_host;   // CONFIRM_MAX + 1
     // the mend pass of a float32 set (alp_points_set_mend; alp_points.hip: mend_launch)
