@@ -277,6 +277,9 @@ _SIGNATURES = {
     "alp_rasterize_columns": [_c_dp, _c_dp, ctypes.POINTER(ctypes.c_void_p), _c_i64, _c_i64, _c_double, _c_double, _c_double,
                               _c_i64, _c_i64, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_uint8)],
     "alp_distance_mask": [_c_dp, _c_i64, _c_dp, _c_double, _c_double, ctypes.POINTER(ctypes.c_uint8)],
+    "alp_match_knn2": [_c_void_p, _c_i64, _c_void_p, _c_i64, _c_int, _c_int, _c_double, _c_int, ctypes.POINTER(ctypes.c_int32),
+                       ctypes.POINTER(ctypes.c_int32), _c_fp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64),
+                       ctypes.POINTER(_c_i64)],
     "alp_rasterize_points": [_c_dp, _c_dp, _c_dp, _c_i64, _c_i64, _c_double, _c_double, _c_double, _c_i64, _c_i64,
                              _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_uint8)],
     "alp_rasterize_points_f32": [_c_dp, _c_dp, _c_dp, _c_i64, _c_i64, _c_double, _c_double, _c_double, _c_i64, _c_i64,
@@ -1092,6 +1095,52 @@ def distance_mask(xyz, camera, min_distance=None, max_distance=None):
                                   float("nan") if max_distance is None else float(max_distance),
                                   keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
     return keep.astype(bool)
+
+
+MATCH_MAX_LEN = 512             # alp_match_knn2: values per descriptor
+MATCH_INFO = ("query_tile", "train_tile", "splits", "padded_len", "workgroups", "scratch_bytes")
+
+
+def match_check(des1, des2, ratio=0.7):
+    """The two descriptor arrays as alp_match_knn2 takes them, or ValueError -- without touching the device: C-contiguous (N, L)
+    arrays of one dtype, uint8 or float32, with equal L in 1..512, at least 2 rows in ``des2``, a finite ratio."""
+    if not isinstance(des1, np.ndarray) or not isinstance(des2, np.ndarray):
+        raise ValueError("descriptors must be numpy arrays")
+    if des1.ndim != 2 or des2.ndim != 2:
+        raise ValueError(f"descriptors must be two-dimensional (N, L), not {des1.shape} and {des2.shape}")
+    if des1.dtype != des2.dtype or des1.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+        raise ValueError(f"descriptors must both be uint8 or both float32, not {des1.dtype} and {des2.dtype}")
+    if not des1.flags["C_CONTIGUOUS"] or not des2.flags["C_CONTIGUOUS"]:
+        raise ValueError("descriptors must be C-contiguous")
+    if des1.shape[1] != des2.shape[1]:
+        raise ValueError(f"descriptor lengths differ: {des1.shape[1]} and {des2.shape[1]}")
+    if not 1 <= des1.shape[1] <= MATCH_MAX_LEN:
+        raise ValueError(f"descriptor length must be 1..{MATCH_MAX_LEN}, not {des1.shape[1]}")
+    if des2.shape[0] < 2:
+        raise ValueError("des2 needs at least 2 rows: there is no second neighbour otherwise")
+    if not np.isfinite(ratio):
+        raise ValueError("ratio must be finite")
+    return ALP_U8 if des1.dtype == np.uint8 else ALP_F32
+
+
+def match_knn2(des1, des2, ratio=0.7, splits=0):
+    """alp_match_knn2: for every row of ``des1`` the two nearest rows of ``des2`` (exact squared L2 distance, the lower index first
+    on a tie) and Lowe's ratio test.  -> dict idx (N1, 2) int32, dist2 (N1, 2) int32, dist (N1, 2) float32, good (N1,) bool,
+    n_good, info (the launch plan: MATCH_INFO)."""
+    code = match_check(des1, des2, ratio)
+    n1, n2, length = des1.shape[0], des2.shape[0], des1.shape[1]
+    idx = np.empty((n1, 2), dtype=np.int32)
+    dist2 = np.empty((n1, 2), dtype=np.int32)
+    dist = np.empty((n1, 2), dtype=np.float32)
+    good = np.empty(n1, dtype=np.uint8)
+    n_good = _c_i64(0)
+    info = (_c_i64 * 6)()
+    ip = ctypes.POINTER(ctypes.c_int32)
+    check(lib().alp_match_knn2(des1.ctypes.data_as(_c_void_p), n1, des2.ctypes.data_as(_c_void_p), n2, length, code, float(ratio),
+                               int(splits), idx.ctypes.data_as(ip), dist2.ctypes.data_as(ip), as_fp(dist),
+                               good.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(n_good), info))
+    return {"idx": idx, "dist2": dist2, "dist": dist, "good": good.astype(bool), "n_good": int(n_good.value),
+            "info": dict(zip(MATCH_INFO, (int(v) for v in info)))}
 
 
 AGG_CODES = {"mean": 0, "max": 1, "min": 2, "median": 3}

@@ -568,6 +568,89 @@ void check_row_walk() {
     check_row_walk_t<4>();
 }
 
+// ------------------------------------------------------------------ the launch plan of the descriptor matcher (host/alp_matchplan.h)
+void check_match_plan() {
+    // the padded length: the first instantiated K-step count that holds the descriptor, restated by counting up
+    for (int len = 1; len <= MATCH_MAX_LEN; ++len) {
+        const int ks = host::match_ksteps(len);
+        int want = 0;
+        for (int c = 1; c <= 16 && !want; ++c) {
+            bool listed = false;
+            for (int k : MATCH_KSTEPS) listed = listed || k == c;
+            if (listed && c * MATCH_K >= len) want = c;
+        }
+        CHECK(ks == want && ks * MATCH_K >= len, "match_ksteps(%d) = %d, not %d", len, ks, want);
+    }
+    CHECK(host::match_ksteps(61) == 2 && host::match_ksteps(128) == 4 && host::match_ksteps(MATCH_MAX_LEN) == 16, "AKAZE / SIFT / longest");
+    const int64_t edges[] = {0, 1, 2, 3, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 4096, 50000, 1000003};
+    const int lens[] = {1, 31, 32, 33, 61, 64, 65, 96, 97, 128, 129, 192, 193, 256, 257, 384, 385, 512};
+    for (int len : lens)
+        for (int esize : {1, 4})
+            for (int cu : {1, 64, 256})
+                for (int64_t nq : edges)
+                    for (int64_t nt : edges) {
+                        if (nt < 2) continue;
+                        const int64_t tiles = (nt + 31) / 32;
+                        for (int forced : {0, 1, 2, 3, (int)std::min<int64_t>(tiles, 1 << 20)}) {
+                            const host::MatchPlan p = host::match_plan(nq, nt, len, esize, forced, cu);
+                            CHECK(p.padded_len == p.ksteps * 32 && p.padded_len >= len && p.groups == (p.ksteps <= 4 ? 2 : 1) &&
+                                      p.query_tile == 128 * p.groups && p.train_tile == 32,
+                                  "tiles of len %d", len);
+                            CHECK(p.train_tiles == tiles && p.nt_pad == tiles * 32 && p.nt_pad >= nt && p.nt_pad - nt < 32, "train tiles of %" PRId64, nt);
+                            CHECK(p.nq_pad % p.query_tile == 0 && p.nq_pad >= nq && p.nq_pad - nq < p.query_tile && p.query_tiles * p.query_tile == p.nq_pad,
+                                  "query tiles of %" PRId64, nq);
+                            if (forced > tiles) continue;          // the entry point refuses it
+                            if (forced) CHECK(p.splits == forced, "forced splits %d -> %d", forced, p.splits);
+                            else {
+                                // serial restatement: the first count that brings the grid to two workgroups per CU, capped by the tiles
+                                int64_t s = 1;
+                                while (s < tiles && s * p.query_tiles < 2 * cu) ++s;
+                                if (p.query_tiles == 0) s = 1;
+                                CHECK(p.splits == s, "splits(%" PRId64 " x %" PRId64 ", %d CUs) = %d, not %" PRId64, nq, nt, cu, p.splits, s);
+                            }
+                            CHECK(p.splits >= 1 && p.splits <= tiles && p.workgroups == p.query_tiles * p.splits, "grid");
+                            // the splits cover the tiles once, in order, none empty
+                            int64_t covered = 0;
+                            for (int sp = 0; sp < p.splits; ++sp) {
+                                int64_t b, e;
+                                match_split_range(tiles, p.splits, sp, &b, &e);
+                                CHECK(b == covered && e > b && e - b <= tiles / p.splits + 1, "split %d of %d over %" PRId64 " tiles: [%" PRId64 ", %" PRId64 ")",
+                                      sp, p.splits, tiles, b, e);
+                                covered = e;
+                                if (p.splits > 64 && sp == 2) {     // (the long lists: both ends; the walk goes on at split splits - 3)
+                                    sp = p.splits - 4;
+                                    match_split_range(tiles, p.splits, sp + 1, &covered, &e);
+                                }
+                            }
+                            CHECK(covered == tiles, "splits cover %" PRId64 " of %" PRId64 " tiles", covered, tiles);
+                            // the device block: the arrays in order, aligned, none overlapping the next
+                            const size_t off[] = {p.off_raw_q, p.off_raw_t, p.off_pack_q, p.off_pack_t, p.off_norm_q, p.off_norm_t, p.off_partial,
+                                                  p.off_idx, p.off_dist2, p.off_dist, p.off_good, p.off_flags, p.scratch_bytes};
+                            const size_t need[] = {(size_t)nq * len * esize, (size_t)nt * len * esize, (size_t)p.nq_pad * p.padded_len,
+                                                   (size_t)p.nt_pad * p.padded_len, (size_t)p.nq_pad * 4, (size_t)p.nt_pad * 4,
+                                                   (size_t)p.splits * p.nq_pad * 16, (size_t)nq * 8, (size_t)nq * 8, (size_t)nq * 8, (size_t)nq, 24};
+                            CHECK(off[0] == 0, "first offset");
+                            for (int i = 0; i < 12; ++i)
+                                CHECK(off[i] % 256 == 0 && off[i + 1] >= off[i] + need[i] && off[i + 1] < off[i] + need[i] + 256 + 8, "array %d of the block", i);
+                        }
+                    }
+    // the fragment order: a bijection of (row, byte) onto the packed array, 16 consecutive bytes of a row together
+    for (int ks : MATCH_KSTEPS) {
+        const int64_t rows = 96;
+        std::vector<int> seen((size_t)rows * ks * 32, 0);
+        for (int64_t r = 0; r < rows; ++r)
+            for (int k = 0; k < ks * 32; ++k) {
+                const size_t o = host::match_packed_offset(r, k, ks);
+                CHECK(o < seen.size(), "packed offset of (%" PRId64 ", %d) outside the array", r, k);
+                if (o < seen.size()) ++seen[o];
+                if (k % 16) CHECK(o == host::match_packed_offset(r, k - 1, ks) + 1, "bytes %d and %d of a row apart", k - 1, k);
+            }
+        bool once = true;
+        for (int v : seen) once = once && v == 1;
+        CHECK(once, "fragment order with %d K steps is no bijection", ks);
+    }
+}
+
 // ------------------------------------------------------------------ the error message is per thread
 void check_errors() {
     std::vector<std::thread> th;
@@ -955,7 +1038,7 @@ int main(int argc, char **argv) {
     const Group groups[] = {{"hash", check_hash},     {"minmax", check_minmax},   {"prefault", check_prefault}, {"fold_pose", check_fold_pose},
                             {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors},
                             {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}, {"lm", check_lm},
-                            {"buffer", check_buffer},   {"row_walk", check_row_walk}};
+                            {"buffer", check_buffer},   {"row_walk", check_row_walk}, {"match_plan", check_match_plan}};
     const bool concurrent = !(argc > 1 && !strcmp(argv[1], "--serial"));
     // every group on its own caller thread at once: the library promises that independent calls may overlap
     std::vector<std::thread> th;

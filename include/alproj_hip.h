@@ -668,6 +668,25 @@ int alp_render_gather(alp_mesh_t *mesh, const int32_t *u, const int32_t *v, int6
 int alp_distance_mask(const double *xyz, int64_t n, const double camera[3], double min_distance,
                       double max_distance, uint8_t *keep);
 
+/* The arithmetic core of the reference's built-in matchers, src/alproj/gcp.py:55-70 (cv2.BFMatcher() -- NORM_L2 -- .knnMatch(des1,
+ * des2, k=2), then Lowe's ratio test): for each of the n_query rows of `query` (des1, the photograph) the two nearest of the
+ * n_train rows of `train` (des2, the simulated image) by brute force, exactly.  Rows are `len` values, contiguous: ALP_U8 (AKAZE),
+ * or ALP_F32 holding the integers 0..255 (OpenCV's SIFT), cast to bytes on the device; a value that is no such integer (NaN
+ * included) is ALP_EINVAL naming the lowest offending flat index, and nothing is computed.  Squared distances are exact integers
+ * (int8 matrix cores, int32 accumulators); the order is (squared distance, train index): the lower index first on a tie.
+ *   idx[n_query][2]    the nearest and the second nearest train row;
+ *   dist2[n_query][2]  their squared distances;
+ *   dist[n_query][2]   the correctly rounded float32 square root of (float) dist2: cv2's DMatch.distance;
+ *   good[n_query]      (double) dist[0] < ratio * (double) dist[1]: the comparison of gcp.py:63 as Python evaluates it;
+ *   n_good             the number of good rows.
+ * Each output may be NULL.  splits: 0 = the launch plan's choice of how many ranges the train rows are divided into, > 0 forces it
+ * (tests; the results do not depend on it).  info, may be NULL: query tile, train tile, splits used, padded len, workgroups,
+ * device bytes of the call.  ALP_EINVAL before anything is uploaded: NULL inputs, len outside 1..512, n_train < 2, a ratio that
+ * is not finite, splits above the number of train tiles, a padded array above 2^31 bytes.  n_query = 0: nothing happens. */
+int alp_match_knn2(const void *query, int64_t n_query, const void *train, int64_t n_train, int len, int dtype,
+                   double ratio, int splits, int32_t *idx, int32_t *dist2, float *dist, uint8_t *good,
+                   int64_t *n_good, int64_t info[6]);
+
 /* Compute part of to_geotiff(), src/alproj/project.py:376-503 (the GeoTIFF file itself is
  * written by the caller): n points (x, y, values[n][nb]) -> uint8 raster out[nb][height][width].
  * Pixel of a point: col = int((x - x_min) / resolution), row = int((y_max - y) / resolution),
