@@ -16,16 +16,17 @@ INCLUDE = os.path.join(ROOT, "include")
 BUILD = os.path.join(ROOT, "build")
 LIB = os.path.join(HERE, "libalproj_hip.so")
 SOURCES = ["alp_core.hip", "alp_points.hip", "alp_raster.hip", "alp_mesh.hip", "alp_rasterize.hip", "alp_sampler.hip",
-           "alp_cma.hip", "alp_lm.hip", "alp_match.hip", "host/alp_host.cpp"]
+           "alp_cma.hip", "alp_lm.hip", "alp_match.hip", "alp_epipolar.hip", "host/alp_host.cpp"]
 # host/: the HIP-free part of the library (plain C++; build_host() compiles the same files with g++ under the sanitizers)
 HOST_DIR = os.path.join(CSRC, "host")
 HOST_SAN = os.path.join(BUILD, "host_san")
 HOST_KINDS = {"plain": [], "asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "tsan": ["-fsanitize=thread"]}
 # the raster's coverage/visibility arithmetic is specified operation by operation (DESIGN.md
 # section 5), and the device loop of the CMA-ES generation follows numpy's order of operations: no implicit fused
-# multiply-adds there; nor in the device loop of the least-squares iteration, which follows optimize.py: _normal_lm_steps
+# multiply-adds there; nor in the device loop of the least-squares iteration, which follows optimize.py: _normal_lm_steps; nor
+# in the geometric match filter, whose error expression numpy reproduces bit for bit (include/alproj_hip.h: alp_epipolar_*)
 EXTRA_FLAGS = {"alp_raster.hip": ["-ffp-contract=off"], "alp_mesh.hip": ["-ffp-contract=off"], "alp_cma.hip": ["-ffp-contract=off"],
-               "alp_lm.hip": ["-ffp-contract=off"]}
+               "alp_lm.hip": ["-ffp-contract=off"], "alp_epipolar.hip": ["-ffp-contract=off"]}
 ARCH = "gfx950"
 
 
@@ -98,7 +99,7 @@ def build_host(kind="plain", compiler="clang", force=False):
         raise RuntimeError(f"no {compiler} C++ compiler found")
     os.makedirs(HOST_SAN, exist_ok=True)
     srcs = [os.path.join(HOST_DIR, f) for f in ("alp_host.cpp", "alp_host_selfcheck.cpp")]
-    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("alp_host.h", "alp_fold.h", "alp_plan.h", "alp_matchplan.h", "alp_jacplan.h", "alp_lm.h", "alp_buffer.h")] + [os.path.join(INCLUDE, "alproj_hip.h"), os.path.abspath(__file__)]
+    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("alp_host.h", "alp_fold.h", "alp_plan.h", "alp_matchplan.h", "alp_epiplan.h", "alp_jacplan.h", "alp_lm.h", "alp_buffer.h")] + [os.path.join(INCLUDE, "alproj_hip.h"), os.path.abspath(__file__)]
     exe = os.path.join(HOST_SAN, f"alp_host_{kind}_{compiler}")
     if force or _stale(exe, deps):
         cmd = [cxx, "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", f"-I{INCLUDE}", f"-I{CSRC}"] + \

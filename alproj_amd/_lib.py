@@ -280,6 +280,14 @@ _SIGNATURES = {
     "alp_match_knn2": [_c_void_p, _c_i64, _c_void_p, _c_i64, _c_int, _c_int, _c_double, _c_int, ctypes.POINTER(ctypes.c_int32),
                        ctypes.POINTER(ctypes.c_int32), _c_fp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64),
                        ctypes.POINTER(_c_i64)],
+    "alp_epipolar_samples": [_c_i64, _c_i64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)],
+    "alp_epipolar_solve8": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, _c_dp],
+    "alp_epipolar_score": [_c_dp, _c_dp, _c_i64, _c_dp, _c_i64, _c_double, _c_int, ctypes.POINTER(ctypes.c_int32),
+                           ctypes.POINTER(_c_i64)],
+    "alp_epipolar_mask": [_c_dp, _c_dp, _c_i64, _c_dp, _c_double, ctypes.POINTER(ctypes.c_uint8), _c_dp],
+    "alp_epipolar_ransac": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_uint64, _c_double, _c_int, _c_int,
+                            _c_dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64)],
+    "alp_grid_thin": [ctypes.POINTER(_c_i64), _c_dp, _c_i64, ctypes.POINTER(ctypes.c_uint8)],
     "alp_rasterize_points": [_c_dp, _c_dp, _c_dp, _c_i64, _c_i64, _c_double, _c_double, _c_double, _c_i64, _c_i64,
                              _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_uint8)],
     "alp_rasterize_points_f32": [_c_dp, _c_dp, _c_dp, _c_i64, _c_i64, _c_double, _c_double, _c_double, _c_i64, _c_i64,
@@ -1141,6 +1149,110 @@ def match_knn2(des1, des2, ratio=0.7, splits=0):
                                good.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(n_good), info))
     return {"idx": idx, "dist2": dist2, "dist": dist, "good": good.astype(bool), "n_good": int(n_good.value),
             "info": dict(zip(MATCH_INFO, (int(v) for v in info)))}
+
+
+EPI_MIN_N, EPI_MAX_N, EPI_MAX_H, EPI_MAX_WORK, EPI_MAX_REFITS = 8, 1 << 20, 1 << 20, 1 << 35, 8
+EPI_SCORE_INFO = ("hyp_tile", "match_tile", "splits", "workgroups", "scratch_bytes", "match_tiles")
+THIN_MAX_SPAN = 1 << 26
+
+
+def _epi_points(p1, p2):
+    """The two point arrays as the alp_epipolar_* entry points take them: C-contiguous (n, 2) float64 of one length, or ValueError."""
+    p1, p2 = np.ascontiguousarray(p1, dtype=np.float64), np.ascontiguousarray(p2, dtype=np.float64)
+    if p1.ndim != 2 or p1.shape[1] != 2 or p1.shape != p2.shape:
+        raise ValueError(f"points must be two (n, 2) arrays of one length, not {p1.shape} and {p2.shape}")
+    return p1, p2
+
+
+def _epi_samples(samples, n):
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    if samples.ndim != 2 or samples.shape[1] != 8 or samples.shape[0] < 1:
+        raise ValueError(f"samples must be (H, 8) with H >= 1, not {samples.shape}")
+    return samples
+
+
+_c_i32p = ctypes.POINTER(ctypes.c_int32)
+_c_u8p = ctypes.POINTER(ctypes.c_uint8)
+
+
+def epipolar_samples(n, hypotheses, seed=0):
+    """alp_epipolar_samples: (H, 8) int32, every row 8 distinct indices in [0, n); a function of (n, H, seed) alone."""
+    hypotheses = int(hypotheses)
+    if hypotheses < 1:
+        raise ValueError("hypotheses must be at least 1")
+    out = np.empty((hypotheses, 8), dtype=np.int32)
+    check(lib().alp_epipolar_samples(int(n), hypotheses, int(seed) & (2 ** 64 - 1), out.ctypes.data_as(_c_i32p)))
+    return out
+
+
+def epipolar_solve8(p1, p2, samples):
+    """alp_epipolar_solve8: (H, 3, 3) float64, the normalised 8-point fundamental matrix of every sample (NaN: a degenerate one)."""
+    p1, p2 = _epi_points(p1, p2)
+    samples = _epi_samples(samples, len(p1))
+    F = np.empty((len(samples), 3, 3), dtype=np.float64)
+    check(lib().alp_epipolar_solve8(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p), len(samples), as_dp(F)))
+    return F
+
+
+def epipolar_score(p1, p2, F, threshold, splits=0):
+    """alp_epipolar_score: (counts (H,) int32, info: the launch plan, EPI_SCORE_INFO) of the (H, 3, 3) matrices ``F``."""
+    p1, p2 = _epi_points(p1, p2)
+    F = np.ascontiguousarray(F, dtype=np.float64).reshape(-1, 9)
+    counts = np.empty(len(F), dtype=np.int32)
+    info = (_c_i64 * 6)()
+    check(lib().alp_epipolar_score(as_dp(p1), as_dp(p2), len(p1), as_dp(F), len(F), float(threshold), int(splits),
+                                   counts.ctypes.data_as(_c_i32p), info))
+    return counts, dict(zip(EPI_SCORE_INFO, (int(v) for v in info)))
+
+
+def epipolar_mask(p1, p2, F, threshold):
+    """alp_epipolar_mask: (mask (n,) bool, err (n,) float64) of every match under one F."""
+    p1, p2 = _epi_points(p1, p2)
+    F = np.ascontiguousarray(F, dtype=np.float64).reshape(-1)
+    if F.shape != (9,):
+        raise ValueError("F must hold 9 values")
+    mask = np.empty(len(p1), dtype=np.uint8)
+    err = np.empty(len(p1), dtype=np.float64)
+    check(lib().alp_epipolar_mask(as_dp(p1), as_dp(p2), len(p1), as_dp(F), float(threshold), mask.ctypes.data_as(_c_u8p), as_dp(err)))
+    return mask.astype(bool), err
+
+
+def epipolar_ransac(p1, p2, threshold, hypotheses=16384, seed=0, refits=4, samples=None, splits=0):
+    """alp_epipolar_ransac: the whole geometric filter in one device loop -> dict F (3, 3), mask (n,) bool, info (chosen,
+    chosen_count, final_count, refits_run, refits_kept, keep_all, refit_counts, and the launch plan)."""
+    p1, p2 = _epi_points(p1, p2)
+    if samples is not None:
+        samples = _epi_samples(samples, len(p1))
+        hypotheses = len(samples)
+    hypotheses = int(hypotheses)
+    F = np.empty((3, 3), dtype=np.float64)
+    mask = np.empty(len(p1), dtype=np.uint8)
+    info = (_c_i64 * 24)()
+    check(lib().alp_epipolar_ransac(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
+                                    hypotheses, int(seed) & (2 ** 64 - 1), float(threshold), int(refits), int(splits), as_dp(F),
+                                    mask.ctypes.data_as(_c_u8p), info))
+    v = [int(x) for x in info]
+    run = v[3]
+    return {"F": F, "mask": mask.astype(bool),
+            "info": {"chosen": v[0], "chosen_count": v[1], "final_count": v[2], "refits_run": run, "refits_kept": v[4],
+                     "keep_all": bool(v[5]), "hyp_tile": v[6], "match_tile": v[7], "splits": v[8], "workgroups": v[9],
+                     "scratch_bytes": v[10], "reduce_blocks": v[11], "refit_counts": v[12:12 + run]}}
+
+
+def grid_thin(cell_id, dist=None):
+    """alp_grid_thin: bool mask that keeps one point per distinct cell id: the lowest index, or with ``dist`` (n,) float64 >= 0 the
+    lowest dist, the lowest index on an equal dist."""
+    cell_id = np.ascontiguousarray(cell_id, dtype=np.int64)
+    if cell_id.ndim != 1:
+        raise ValueError("cell_id must be one-dimensional")
+    if dist is not None:
+        dist = np.ascontiguousarray(dist, dtype=np.float64)
+        if dist.shape != cell_id.shape:
+            raise ValueError("dist must have one value per cell id")
+    mask = np.empty(len(cell_id), dtype=np.uint8)
+    check(lib().alp_grid_thin(cell_id.ctypes.data_as(ctypes.POINTER(_c_i64)), as_dp(dist) if dist is not None else None, len(cell_id),
+                              mask.ctypes.data_as(_c_u8p)))
+    return mask.astype(bool)
 
 
 AGG_CODES = {"mean": 0, "max": 1, "min": 2, "median": 3}

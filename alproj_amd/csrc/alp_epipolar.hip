@@ -1,0 +1,816 @@
+// libalproj_hip.so -- the geometric match filter and the grid thinning that the reference's image_match runs between its matcher
+// and set_gcp (src/alproj/gcp.py:507-544: _filter_geometric with outlier_filter="fundamental", then _filter_spatial).
+//
+// cv2's USAC (its random stream, PROSAC, SPRT, MAGSAC scoring) cannot be restated, so the filter is an algorithm of this project's
+// own: hypothesise and verify outright.  H minimal samples of 8 matches -> H fundamental matrices by the normalised 8-point
+// solve -> the inlier count of every one of them over all n matches -> the best one, refitted on its inliers while that strictly
+// grows the count.  Everything is float64, and the unit is compiled with -ffp-contract=off: the error of a match under F is
+// written in the order include/alproj_hip.h gives, so that numpy reproduces it bit for bit.
+//
+//   epi_pack_kernel       p1, p2 -> (x1, y1, x2, y2), 32 B per match
+//   epi_norm_kernel       one workgroup: Hartley's normalisation of both images from all n points (centroid, mean distance sqrt 2)
+//   epi_samples_kernel    a thread per hypothesis: 8 distinct indices from the counter-based generator of alp_sampler.h keyed by
+//                         (seed, hypothesis, attempt); a repeat is rejected and the next draw taken
+//   epi_solve_kernel      a thread per hypothesis, 64 per workgroup.  The 8 x 9 matrix of the normalised sample lives in LDS, element
+//                         e of lane l at e * 64 + l (72 doubles indexed by a pivot search would otherwise go to scratch); Gaussian
+//                         elimination with complete pivoting, the null vector by back substitution, rank 2 by a one-sided Jacobi
+//                         sweep over the three columns, T2^T F T1, unit Frobenius norm.  Rank below 8 or a non-finite F: NaN.
+//   epi_score_kernel      a workgroup = 256 hypotheses (one per lane, F in registers) x one split of the match tiles.  A tile of
+//                         512 matches is staged in LDS and every lane walks it: all lanes read the same address (a broadcast),
+//                         the count stays in a register.  One division per error: max(s2 / a, s2 / b) = s2 / min(a, b) bit for
+//                         bit, since a correctly rounded quotient is monotone in its divisor.
+//   epi_merge_kernel      a thread per hypothesis: the sum of its partial counts over the splits (no atomics)
+//   epi_choose_kernel     one workgroup: the highest count, the lowest index on a tie
+//   epi_accum_kernel, epi_refit_kernel, epi_count_kernel, epi_decide_kernel
+//                         one refit: the upper triangle of sum a a^T over the inliers of the current F (45 sums per lane, wave and
+//                         workgroup reduction, fixed order), its smallest eigenvector by Jacobi rotations in one wave, rank 2,
+//                         the count of the candidate, and the decision.  All of them read `stopped` from the state record and return
+//                         at once when it is set: the host enqueues `refits` rounds and never looks.
+//   epi_mask_kernel       mask and error of every match under one F
+//   thin_*_kernel         alp_grid_thin: atomic minima on (distance bits) and then on the index, per cell
+#include "alp_sampler.h"
+
+#include <climits>
+#include <cmath>
+
+namespace {
+
+using namespace alp;
+
+typedef unsigned long long u64;
+
+struct EpiState {
+    double T[6];                  // cx1, cy1, s1, cx2, cy2, s2: x' = (x - c) * s
+    double Fcur[9], Fcand[9];
+    long long info[EPI_INFO];
+    int count, stopped, keep_all, pad;
+};
+static_assert(sizeof(EpiState) <= EPI_STATE_BYTES, "the state record outgrew its slot");
+
+// info words of alp_epipolar_ransac
+enum { I_CHOSEN = 0, I_CHOSEN_COUNT, I_FINAL_COUNT, I_REFITS_RUN, I_REFITS_KEPT, I_KEEP_ALL, I_HYP_TILE, I_MATCH_TILE, I_SPLITS,
+       I_WORKGROUPS, I_BYTES, I_REDUCE_BLOCKS, I_REFIT_COUNT0 };
+static_assert(I_REFIT_COUNT0 + EPI_MAX_REFITS <= EPI_INFO, "info too short");
+
+__device__ __forceinline__ double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// the three quantities of the error expression, in the header's order
+__device__ __forceinline__ void epi_terms(const double (&F)[9], double x1, double y1, double x2, double y2, double &ss, double &d2,
+                                          double &d1) {
+    const double l20 = (F[0] * x1 + F[1] * y1) + F[2];
+    const double l21 = (F[3] * x1 + F[4] * y1) + F[5];
+    const double l22 = (F[6] * x1 + F[7] * y1) + F[8];
+    const double l10 = (F[0] * x2 + F[3] * y2) + F[6];
+    const double l11 = (F[1] * x2 + F[4] * y2) + F[7];
+    const double s = (x2 * l20 + y2 * l21) + l22;
+    ss = s * s;
+    d2 = l20 * l20 + l21 * l21;
+    d1 = l10 * l10 + l11 * l11;
+}
+
+// e as written: the larger of the two quotients, NaN when either is
+__device__ __forceinline__ double epi_error(const double (&F)[9], const double4 q) {
+    double ss, d2, d1;
+    epi_terms(F, q.x, q.y, q.z, q.w, ss, d2, d1);
+    const double e2 = ss / d2, e1 = ss / d1;
+    return e2 != e2 ? e2 : e1 != e1 ? e1 : e2 > e1 ? e2 : e1;
+}
+
+// e <= t2 with one division (the score kernel): the larger quotient is the one by the smaller divisor
+__device__ __forceinline__ bool epi_inlier(const double (&F)[9], const double4 q, double t2) {
+    double ss, d2, d1;
+    epi_terms(F, q.x, q.y, q.z, q.w, ss, d2, d1);
+    double dm = d1 < d2 ? d1 : d2;
+    if (d1 != d1) dm = d1;
+    return ss / dm <= t2;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the sum of v over a workgroup of 256, the same value in every thread (buf: 4 doubles of LDS)
+__device__ __forceinline__ double block_sum256(double v, double *buf) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (buf[0] + buf[1]) + (buf[2] + buf[3]);
+}
+
+__global__ __launch_bounds__(256) void epi_pack_kernel(const double2 *__restrict__ p1, const double2 *__restrict__ p2, int n,
+                                                       double4 *__restrict__ pts) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double2 a = p1[i], b = p2[i];
+    pts[i] = make_double4(a.x, a.y, b.x, b.y);
+}
+
+__global__ __launch_bounds__(256) void epi_norm_kernel(const double4 *__restrict__ pts, int n, EpiState *__restrict__ st) {
+    __shared__ double buf[4];
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double4 q = pts[i];
+        s[0] += q.x, s[1] += q.y, s[2] += q.z, s[3] += q.w;
+    }
+    double c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = block_sum256(s[k], buf) / (double)n;
+    double m1 = 0.0, m2 = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double4 q = pts[i];
+        const double ax = q.x - c[0], ay = q.y - c[1], bx = q.z - c[2], by = q.w - c[3];
+        m1 += sqrt(ax * ax + ay * ay);
+        m2 += sqrt(bx * bx + by * by);
+    }
+    m1 = block_sum256(m1, buf) / (double)n;
+    m2 = block_sum256(m2, buf) / (double)n;
+    if (threadIdx.x == 0) {
+        st->T[0] = c[0], st->T[1] = c[1], st->T[2] = 1.4142135623730951 / m1;
+        st->T[3] = c[2], st->T[4] = c[3], st->T[5] = 1.4142135623730951 / m2;
+    }
+}
+
+constexpr int EPI_MAX_ATTEMPTS = 4096;
+constexpr unsigned EPI_STREAM = 0x45504950u;      // the generator's third counter word: this unit's stream
+
+__global__ __launch_bounds__(256) void epi_samples_kernel(int n, int H, unsigned k0, unsigned k1, int *__restrict__ samples) {
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= H) return;
+    int row[EPI_SAMPLE];
+#pragma unroll
+    for (int i = 0; i < EPI_SAMPLE; ++i) row[i] = -1;
+    int filled = 0;
+    auto offer = [&](int c) {
+        bool dup = false;
+#pragma unroll
+        for (int i = 0; i < EPI_SAMPLE; ++i) dup = dup || row[i] == c;
+        if (!dup && filled < EPI_SAMPLE) {
+#pragma unroll
+            for (int i = 0; i < EPI_SAMPLE; ++i)
+                if (i == filled) row[i] = c;
+            ++filled;
+        }
+    };
+    for (int attempt = 0; filled < EPI_SAMPLE && attempt < EPI_MAX_ATTEMPTS; ++attempt) {
+        unsigned w[4];
+        philox4x32_10((unsigned)attempt, (unsigned)h, EPI_STREAM, 0u, k0, k1, w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) offer((int)(((u64)w[j] * (u64)(unsigned)n) >> 32));
+    }
+    for (int c = 0; filled < EPI_SAMPLE && c < n; ++c) offer(c);      // (never in practice: 16 384 draws without 8 distinct values)
+#pragma unroll
+    for (int i = 0; i < EPI_SAMPLE; ++i) samples[(size_t)h * EPI_SAMPLE + i] = row[i];
+}
+
+// f: a 3 x 3 matrix in normalised coordinates, row-major -> out: its smallest singular value zeroed, T2^T f T1, unit Frobenius
+// norm; NaN when that is not finite
+__device__ void rank2_denorm(const double (&f)[9], const double *__restrict__ T, double (&out)[9]) {
+    double g[3][3], v[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g[r][c] = f[3 * r + c], v[r][c] = r == c ? 1.0 : 0.0;
+    // one-sided Jacobi: rotate pairs of columns of g until they are orthogonal; g = U S, f = g v^T
+    for (int sweep = 0; sweep < 16; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+            const double alpha = (g[0][p] * g[0][p] + g[1][p] * g[1][p]) + g[2][p] * g[2][p];
+            const double beta = (g[0][q] * g[0][q] + g[1][q] * g[1][q]) + g[2][q] * g[2][q];
+            const double gamma = (g[0][p] * g[0][q] + g[1][p] * g[1][q]) + g[2][p] * g[2][q];
+            if (gamma != 0.0 && fabs(gamma) > 1e-17 * sqrt(alpha * beta)) {
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const double gp = g[r][p], gq = g[r][q], vp = v[r][p], vq = v[r][q];
+                    g[r][p] = c * gp - s * gq, g[r][q] = s * gp + c * gq;
+                    v[r][p] = c * vp - s * vq, v[r][q] = s * vp + c * vq;
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+    double nrm[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) nrm[c] = (g[0][c] * g[0][c] + g[1][c] * g[1][c]) + g[2][c] * g[2][c];
+    const int drop = nrm[0] <= nrm[1] ? (nrm[0] <= nrm[2] ? 0 : 2) : (nrm[1] <= nrm[2] ? 1 : 2);
+    double m[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double a = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) a += (j == drop ? 0.0 : g[r][j]) * v[c][j];
+            m[r][c] = a;
+        }
+    // m T1, then T2^T (m T1)
+    const double cx1 = T[0], cy1 = T[1], s1 = T[2], cx2 = T[3], cy2 = T[4], s2 = T[5];
+    double a[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        a[r][0] = s1 * m[r][0];
+        a[r][1] = s1 * m[r][1];
+        a[r][2] = m[r][2] - s1 * (cx1 * m[r][0] + cy1 * m[r][1]);
+    }
+    double o[9], fro = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        o[c] = s2 * a[0][c];
+        o[3 + c] = s2 * a[1][c];
+        o[6 + c] = a[2][c] - s2 * (cx2 * a[0][c] + cy2 * a[1][c]);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) fro += o[k] * o[k];
+    fro = sqrt(fro);
+    const bool ok = fro > 0.0 && fro < INFINITY;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out[k] = ok ? o[k] / fro : nan64();
+}
+
+constexpr double EPI_RANK_TOL = 1e-13;        // a pivot below this share of the first one: the sample's matrix has rank below 8
+
+__global__ __launch_bounds__(EPI_SOLVE_BLOCK) void epi_solve_kernel(const double4 *__restrict__ pts, const int *__restrict__ samples, int H,
+                                                                    const EpiState *__restrict__ st, double *__restrict__ Fout) {
+    __shared__ double A_[72 * EPI_SOLVE_BLOCK];
+    __shared__ double Y_[9 * EPI_SOLVE_BLOCK];
+    __shared__ double X_[9 * EPI_SOLVE_BLOCK];
+    const int lane = threadIdx.x;
+    const int h = blockIdx.x * EPI_SOLVE_BLOCK + lane;
+    if (h >= H) return;                 // no barrier below: a lane touches its own LDS column only
+#define A(i, j) A_[((i) * 9 + (j)) * EPI_SOLVE_BLOCK + lane]
+#define Y(j) Y_[(j) * EPI_SOLVE_BLOCK + lane]
+#define X(j) X_[(j) * EPI_SOLVE_BLOCK + lane]
+    double T[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) T[k] = st->T[k];
+    for (int i = 0; i < EPI_SAMPLE; ++i) {
+        const double4 q = pts[samples[(size_t)h * EPI_SAMPLE + i]];
+        const double x1 = (q.x - T[0]) * T[2], y1 = (q.y - T[1]) * T[2], x2 = (q.z - T[3]) * T[5], y2 = (q.w - T[4]) * T[5];
+        A(i, 0) = x2 * x1, A(i, 1) = x2 * y1, A(i, 2) = x2;
+        A(i, 3) = y2 * x1, A(i, 4) = y2 * y1, A(i, 5) = y2;
+        A(i, 6) = x1, A(i, 7) = y1, A(i, 8) = 1.0;
+    }
+    u64 perm = 0;                       // 4 bits per column: which unknown stands in column j
+    for (int j = 0; j < 9; ++j) perm |= (u64)j << (4 * j);
+    bool ok = true;
+    double first = 0.0;
+    for (int k = 0; k < 8; ++k) {
+        int pi = k, pj = k;
+        double pv = -1.0;
+        for (int i = k; i < 8; ++i)
+            for (int j = k; j < 9; ++j) {
+                const double a = fabs(A(i, j));
+                if (!(a <= pv)) pv = a, pi = i, pj = j;        // (a NaN entry becomes the pivot and fails the test below)
+            }
+        if (k == 0) first = pv;
+        if (!(pv > first * EPI_RANK_TOL) || !(pv < INFINITY)) {
+            ok = false;
+            break;
+        }
+        if (pi != k)
+            for (int j = k; j < 9; ++j) {
+                const double t = A(k, j);
+                A(k, j) = A(pi, j), A(pi, j) = t;
+            }
+        if (pj != k) {
+            for (int i = 0; i < 8; ++i) {
+                const double t = A(i, k);
+                A(i, k) = A(i, pj), A(i, pj) = t;
+            }
+            const u64 a = (perm >> (4 * k)) & 15, b = (perm >> (4 * pj)) & 15;
+            perm = (perm & ~((u64)15 << (4 * k)) & ~((u64)15 << (4 * pj))) | a << (4 * pj) | b << (4 * k);
+        }
+        const double piv = A(k, k);
+        for (int i = k + 1; i < 8; ++i) {
+            const double mlt = A(i, k) / piv;
+            for (int j = k + 1; j < 9; ++j) A(i, j) -= mlt * A(k, j);
+        }
+    }
+    double f[9], out[9];
+    if (ok) {
+        Y(8) = 1.0;
+        for (int k = 7; k >= 0; --k) {
+            double s = 0.0;
+            for (int j = k + 1; j < 9; ++j) s += A(k, j) * Y(j);
+            Y(k) = -s / A(k, k);
+        }
+        for (int j = 0; j < 9; ++j) X((int)((perm >> (4 * j)) & 15)) = Y(j);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = X(k);
+        rank2_denorm(f, T, out);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out[k] = nan64();
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Fout[(size_t)h * 9 + k] = out[k];
+#undef A
+#undef Y
+#undef X
+}
+
+__global__ __launch_bounds__(EPI_HYP_TILE) void epi_score_kernel(const double4 *__restrict__ pts, int n, const double *__restrict__ F, int H,
+                                                                 double t2, int splits, long long match_tiles, long long h_pad,
+                                                                 int *__restrict__ partial) {
+    __shared__ double4 tile[EPI_MATCH_TILE];
+    const long long htile = blockIdx.x / (unsigned)splits;
+    const int split = (int)(blockIdx.x % (unsigned)splits);
+    const long long h = htile * EPI_HYP_TILE + threadIdx.x;
+    double f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = h < H ? F[(size_t)h * 9 + k] : nan64();
+    int64_t tb, te;
+    match_split_range(match_tiles, splits, split, &tb, &te);
+    int count = 0;
+    for (long long t = tb; t < te; ++t) {
+        const int base = (int)(t * EPI_MATCH_TILE);
+        const int cnt = n - base < EPI_MATCH_TILE ? n - base : EPI_MATCH_TILE;
+        __syncthreads();
+        for (int i = threadIdx.x; i < cnt; i += EPI_HYP_TILE) tile[i] = pts[base + i];
+        __syncthreads();
+#pragma unroll 4
+        for (int m = 0; m < cnt; ++m) count += epi_inlier(f, tile[m], t2) ? 1 : 0;
+    }
+    partial[(size_t)split * h_pad + h] = count;
+}
+
+__global__ __launch_bounds__(256) void epi_merge_kernel(const int *__restrict__ partial, int splits, long long h_pad, int H,
+                                                        int *__restrict__ counts) {
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= H) return;
+    int c = 0;
+    for (int s = 0; s < splits; ++s) c += partial[(size_t)s * h_pad + h];
+    counts[h] = c;
+}
+
+// the highest count, the lowest index on a tie: the largest key count << 32 | ~index
+__global__ __launch_bounds__(256) void epi_choose_kernel(const int *__restrict__ counts, int H, const double *__restrict__ F,
+                                                         EpiState *__restrict__ st) {
+    __shared__ u64 best[4];
+    u64 key = 0;
+    for (int h = threadIdx.x; h < H; h += 256) {
+        const u64 k = (u64)(unsigned)counts[h] << 32 | (u64)(0xffffffffu - (unsigned)h);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)key, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), o, 64);
+        const u64 k = (u64)hi << 32 | lo;
+        key = k > key ? k : key;
+    }
+    if ((threadIdx.x & 63) == 0) best[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) key = best[w] > key ? best[w] : key;
+        const int idx = (int)(0xffffffffu - (unsigned)key), count = (int)(key >> 32);
+        for (int k = 0; k < 9; ++k) st->Fcur[k] = F[(size_t)idx * 9 + k], st->Fcand[k] = nan64();
+        for (int k = 0; k < EPI_INFO; ++k) st->info[k] = 0;
+        for (int k = 0; k < EPI_MAX_REFITS; ++k) st->info[I_REFIT_COUNT0 + k] = -1;
+        st->count = count;
+        st->keep_all = st->stopped = count < EPI_SAMPLE ? 1 : 0;
+        st->info[I_CHOSEN] = idx, st->info[I_CHOSEN_COUNT] = st->info[I_FINAL_COUNT] = count, st->info[I_KEEP_ALL] = st->keep_all;
+    }
+}
+
+__global__ __launch_bounds__(EPI_REDUCE_BLOCK) void epi_accum_kernel(const double4 *__restrict__ pts, int n, double t2,
+                                                                     const EpiState *__restrict__ st, double *__restrict__ sym) {
+    __shared__ double red[4 * EPI_SYM];
+    if (st->stopped) return;
+    double f[9], T[6], acc[EPI_SYM];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = st->Fcur[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) T[k] = st->T[k];
+#pragma unroll
+    for (int k = 0; k < EPI_SYM; ++k) acc[k] = 0.0;
+    for (int i = blockIdx.x * EPI_REDUCE_BLOCK + threadIdx.x; i < n; i += gridDim.x * EPI_REDUCE_BLOCK) {
+        const double4 q = pts[i];
+        if (!(epi_error(f, q) <= t2)) continue;
+        const double x1 = (q.x - T[0]) * T[2], y1 = (q.y - T[1]) * T[2], x2 = (q.z - T[3]) * T[5], y2 = (q.w - T[4]) * T[5];
+        const double a[9] = {x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, 1.0};
+        int k = 0;
+#pragma unroll
+        for (int r = 0; r < 9; ++r)
+#pragma unroll
+            for (int c = r; c < 9; ++c) acc[k++] += a[r] * a[c];
+    }
+#pragma unroll
+    for (int k = 0; k < EPI_SYM; ++k) {
+        const double v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * EPI_SYM + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < EPI_SYM)
+        sym[(size_t)blockIdx.x * EPI_SYM + threadIdx.x] =
+            (red[threadIdx.x] + red[EPI_SYM + threadIdx.x]) + (red[2 * EPI_SYM + threadIdx.x] + red[3 * EPI_SYM + threadIdx.x]);
+}
+
+// one wave: the 45 sums over the workgroups of epi_accum_kernel in order, then the eigenvector of the smallest eigenvalue of the
+// 9 x 9 matrix by Jacobi rotations, four disjoint pairs at a time (matrix and vectors in LDS: they are indexed by the rotation's
+// pair), and on lane 0 rank 2 and T2^T f T1
+__global__ __launch_bounds__(64) void epi_refit_kernel(const double *__restrict__ sym, int blocks, EpiState *__restrict__ st) {
+    __shared__ double S[EPI_SYM], M[81], V[81];
+    if (st->stopped) return;
+    if (threadIdx.x < EPI_SYM) {
+        double s = 0.0;
+        for (int b = 0; b < blocks; ++b) s += sym[(size_t)b * EPI_SYM + threadIdx.x];
+        S[threadIdx.x] = s;
+    }
+    __syncthreads();
+    const int i = threadIdx.x;          // lanes 0..8 own index i of every rotation; all lanes walk the pairs together
+    for (int e = i; e < 81; e += 64) {
+        const int r = e / 9, c = e % 9, lo_rc = r < c ? r : c, hi_rc = r < c ? c : r;
+        M[e] = S[lo_rc * 9 - lo_rc * (lo_rc - 1) / 2 + (hi_rc - lo_rc)];
+        V[e] = r == c ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    // round-robin order: 9 rounds of 4 disjoint pairs cover the 36 pairs once (the circle method over 9 indices and a bye); the 4
+    // rotations of a round touch different rows and columns, so M <- J^T M J is their columns, a barrier, their rows.  Lane
+    // 9 k + e turns element e of pair k.
+    const int pair = i / 9, e = i % 9;
+    for (int sweep = 0; sweep < 40; ++sweep) {
+        bool rotated = false;
+        for (int round = 0; round < 9; ++round) {
+            const int a = (round + pair + 1) % 9, b = (round + 8 - pair) % 9;
+            const int p = a < b ? a : b, q = a < b ? b : a;
+            bool rot = false;
+            double c = 1.0, s = 0.0;
+            if (pair < 4) {
+                const double apq = M[p * 9 + q], app = M[p * 9 + p], aqq = M[q * 9 + q];
+                rot = apq != 0.0 && fabs(apq) > 1e-17 * sqrt(fabs(app) * fabs(aqq));
+                if (rot) {
+                    const double zeta = (aqq - app) / (2.0 * apq);
+                    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+                }
+            }
+            rotated = rotated || __any(rot);           // (the workgroup is one wave)
+            __syncthreads();
+            if (rot) {                                 // columns p, q of M and of V
+                const double mp = M[e * 9 + p], mq = M[e * 9 + q], vp = V[e * 9 + p], vq = V[e * 9 + q];
+                M[e * 9 + p] = c * mp - s * mq, M[e * 9 + q] = s * mp + c * mq;
+                V[e * 9 + p] = c * vp - s * vq, V[e * 9 + q] = s * vp + c * vq;
+            }
+            __syncthreads();
+            if (rot) {                                 // rows p, q
+                const double mp = M[p * 9 + e], mq = M[q * 9 + e];
+                M[p * 9 + e] = c * mp - s * mq, M[q * 9 + e] = s * mp + c * mq;
+            }
+            __syncthreads();
+            if (rot && e == 0) M[p * 9 + q] = M[q * 9 + p] = 0.0;
+            __syncthreads();
+        }
+        if (!rotated) break;
+    }
+    if (i != 0) return;
+    int lo = 0;
+    for (int i = 1; i < 9; ++i)
+        if (M[i * 9 + i] < M[lo * 9 + lo]) lo = i;
+    double f[9], out[9], T[6];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) f[i] = V[i * 9 + lo];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) T[i] = st->T[i];
+    rank2_denorm(f, T, out);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) st->Fcand[i] = out[i];
+}
+
+__global__ __launch_bounds__(EPI_REDUCE_BLOCK) void epi_count_kernel(const double4 *__restrict__ pts, int n, double t2,
+                                                                     const EpiState *__restrict__ st, int *__restrict__ cpart) {
+    __shared__ int red[4];
+    if (st->stopped) return;
+    double f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = st->Fcand[k];
+    int c = 0;
+    for (int i = blockIdx.x * EPI_REDUCE_BLOCK + threadIdx.x; i < n; i += gridDim.x * EPI_REDUCE_BLOCK)
+        c += epi_error(f, pts[i]) <= t2 ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) cpart[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ void epi_decide_kernel(const int *__restrict__ cpart, int blocks, int round, EpiState *__restrict__ st) {
+    if (threadIdx.x != 0 || st->stopped) return;
+    int c = 0;
+    for (int b = 0; b < blocks; ++b) c += cpart[b];
+    st->info[I_REFIT_COUNT0 + round] = c;
+    st->info[I_REFITS_RUN] = round + 1;
+    if (c > st->count) {
+        for (int k = 0; k < 9; ++k) st->Fcur[k] = st->Fcand[k];
+        st->count = c;
+        st->info[I_FINAL_COUNT] = c;
+        st->info[I_REFITS_KEPT] += 1;
+    } else {
+        st->stopped = 1;
+    }
+}
+
+// F: 9 doubles on the device; keep_all: NULL, or a flag on the device that turns every mask entry into 1
+__global__ __launch_bounds__(256) void epi_mask_kernel(const double4 *__restrict__ pts, int n, const double *__restrict__ F, double t2,
+                                                       const int *__restrict__ keep_all, unsigned char *__restrict__ mask,
+                                                       double *__restrict__ err) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = F[k];
+    const double e = epi_error(f, pts[i]);
+    err[i] = e;
+    mask[i] = (e <= t2 || (keep_all && *keep_all)) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ alp_grid_thin
+__global__ __launch_bounds__(256) void thin_dist_kernel(const long long *__restrict__ cell, const double *__restrict__ dist, long long n,
+                                                        long long lo, u64 *__restrict__ best) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    atomicMin(best + (cell[i] - lo), (u64)__double_as_longlong(dist[i] + 0.0));       // (+ 0.0: a -0.0 orders as 0.0)
+}
+__global__ __launch_bounds__(256) void thin_index_kernel(const long long *__restrict__ cell, const double *__restrict__ dist, long long n,
+                                                         long long lo, const u64 *__restrict__ best, u64 *__restrict__ first) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long c = cell[i] - lo;
+    if (!dist || (u64)__double_as_longlong(dist[i] + 0.0) == best[c]) atomicMin(first + c, (u64)i);
+}
+__global__ __launch_bounds__(256) void thin_mask_kernel(const long long *__restrict__ cell, long long n, long long lo,
+                                                        const u64 *__restrict__ first, unsigned char *__restrict__ mask) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    mask[i] = first[cell[i] - lo] == (u64)i ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ host side
+struct EpiCall {
+    host::EpiPlan p;
+    DeviceBuffer<char> dev;
+    char *d = nullptr;
+    double4 *pts() const { return (double4 *)(d + p.off_pts); }
+    int *samples() const { return (int *)(d + p.off_samples); }
+    double *F() const { return (double *)(d + p.off_F); }
+    int *partial() const { return (int *)(d + p.off_partial); }
+    int *counts() const { return (int *)(d + p.off_counts); }
+    EpiState *state() const { return (EpiState *)(d + p.off_state); }
+    double *sym() const { return (double *)(d + p.off_sym); }
+    int *cpart() const { return (int *)(d + p.off_cpart); }
+    unsigned char *mask() const { return (unsigned char *)(d + p.off_mask); }
+    double *err() const { return (double *)(d + p.off_err); }
+
+    int reserve(int64_t n, int64_t H, int splits) {
+        p = host::epi_plan(n, H, splits, ctx().cu_count);
+        if (int rc = dev.reserve(p.scratch_bytes)) return rc;
+        d = dev;
+        return ALP_OK;
+    }
+    // p1, p2 -> the packed matches and (with_norm) the normalisation in the state record
+    hipError_t upload(const double *p1, const double *p2, int64_t n, bool with_norm) {
+        hipStream_t st = ctx().stream;
+        hipError_t e = hipMemcpyAsync(d + p.off_raw1, p1, (size_t)n * 16, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + p.off_raw2, p2, (size_t)n * 16, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync(state(), 0, EPI_STATE_BYTES, st);
+        if (e != hipSuccess) return e;
+        KTimeScope kt;
+        hipLaunchKernelGGL(epi_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double2 *)(d + p.off_raw1),
+                           (const double2 *)(d + p.off_raw2), (int)n, pts());
+        if (with_norm) hipLaunchKernelGGL(epi_norm_kernel, dim3(1), dim3(256), 0, st, (const double4 *)pts(), (int)n, state());
+        return hipGetLastError();
+    }
+    void launch_samples(int64_t n, int64_t H, uint64_t seed) {
+        hipLaunchKernelGGL(epi_samples_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx().stream, (int)n, (int)H,
+                           (unsigned)seed, (unsigned)(seed >> 32), samples());
+    }
+    void launch_solve(int64_t H) {
+        hipLaunchKernelGGL(epi_solve_kernel, dim3((unsigned)p.solve_blocks), dim3(EPI_SOLVE_BLOCK), 0, ctx().stream, (const double4 *)pts(),
+                           (const int *)samples(), (int)H, (const EpiState *)state(), F());
+    }
+    void launch_score(int64_t n, int64_t H, double t2) {
+        hipLaunchKernelGGL(epi_score_kernel, dim3((unsigned)p.workgroups), dim3(EPI_HYP_TILE), 0, ctx().stream, (const double4 *)pts(), (int)n,
+                           (const double *)F(), (int)H, t2, p.splits, (long long)p.match_tiles, (long long)p.h_pad, partial());
+        hipLaunchKernelGGL(epi_merge_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx().stream, (const int *)partial(), p.splits,
+                           (long long)p.h_pad, (int)H, counts());
+    }
+};
+
+int epi_check_points(const char *fn, const double *p1, const double *p2, int64_t n, int64_t H) {
+    if (!p1 || !p2) return fail(ALP_EINVAL, "%s: NULL input", fn);
+    if (n < EPI_MIN_N || n > EPI_MAX_N) return fail(ALP_EINVAL, "%s: n = %lld, must be 8..2^20", fn, (long long)n);
+    if (H < 1 || H > EPI_MAX_H) return fail(ALP_EINVAL, "%s: H = %lld, must be 1..2^20", fn, (long long)H);
+    if (!host::epi_caps_ok(n, H)) return fail(ALP_EINVAL, "%s: H * n = %lld * %lld passes 2^35 error evaluations", fn, (long long)H, (long long)n);
+    return ALP_OK;
+}
+
+int epi_check_samples(const char *fn, const int32_t *samples, int64_t H, int64_t n) {
+    for (int64_t i = 0; i < H * EPI_SAMPLE; ++i)
+        if (samples[i] < 0 || samples[i] >= n)
+            return fail(ALP_EINVAL, "%s: sample %lld of hypothesis %lld is %d, outside 0..%lld", fn, (long long)(i % EPI_SAMPLE),
+                        (long long)(i / EPI_SAMPLE), samples[i], (long long)(n - 1));
+    return ALP_OK;
+}
+
+int epi_check_splits(const char *fn, int splits, int64_t n) {
+    const int64_t tiles = (n + EPI_MATCH_TILE - 1) / EPI_MATCH_TILE;
+    if (splits < 0) return fail(ALP_EINVAL, "%s: splits is negative", fn);
+    if (splits > tiles)
+        return fail(ALP_EINVAL, "%s: splits = %d, but %lld matches are only %lld tiles of %d", fn, splits, (long long)n, (long long)tiles,
+                    EPI_MATCH_TILE);
+    return ALP_OK;
+}
+
+int epi_finish(const char *fn, hipError_t e) {
+    const hipError_t es = hipStreamSynchronize(ctx().stream);          // before the device block and the caller's arrays go away
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALP_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    return ALP_OK;
+}
+
+}  // namespace
+
+extern "C" int alp_epipolar_samples(int64_t n, int64_t H, uint64_t seed, int32_t *samples) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(samples, "NULL output");
+    ALP_REQUIRE(n >= EPI_MIN_N && n <= EPI_MAX_N, "n must be 8..2^20");
+    ALP_REQUIRE(H >= 1 && H <= EPI_MAX_H, "H must be 1..2^20");
+    DeviceBuffer<int> dev;
+    if (int rc = dev.reserve((size_t)H * EPI_SAMPLE * 4)) return rc;
+    hipStream_t st = ctx().stream;
+    hipError_t e;
+    {
+        KTimeScope kt;
+        hipLaunchKernelGGL(epi_samples_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, (int)n, (int)H, (unsigned)seed,
+                           (unsigned)(seed >> 32), (int *)dev);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(samples, (int *)dev, (size_t)H * EPI_SAMPLE * 4, hipMemcpyDeviceToHost, st);
+    return epi_finish(__func__, e);
+}
+
+extern "C" int alp_epipolar_solve8(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, double *F) {
+    if (int rc = require_init()) return rc;
+    if (int rc = epi_check_points(__func__, p1, p2, n, H)) return rc;
+    ALP_REQUIRE(samples && F, "NULL samples or output");
+    if (int rc = epi_check_samples(__func__, samples, H, n)) return rc;
+    EpiCall c;
+    if (int rc = c.reserve(n, H, 1)) return rc;
+    hipStream_t st = ctx().stream;
+    hipError_t e = c.upload(p1, p2, n, true);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.samples(), samples, (size_t)H * EPI_SAMPLE * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        KTimeScope kt;
+        c.launch_solve(H);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(F, c.F(), (size_t)H * 72, hipMemcpyDeviceToHost, st);
+    return epi_finish(__func__, e);
+}
+
+extern "C" int alp_epipolar_score(const double *p1, const double *p2, int64_t n, const double *F, int64_t H, double threshold, int splits,
+                                  int32_t *counts, int64_t info[6]) {
+    if (int rc = require_init()) return rc;
+    if (int rc = epi_check_points(__func__, p1, p2, n, H)) return rc;
+    ALP_REQUIRE(F && counts, "NULL F or output");
+    ALP_REQUIRE(std::isfinite(threshold) && threshold >= 0.0, "threshold must be finite and not negative");
+    if (int rc = epi_check_splits(__func__, splits, n)) return rc;
+    EpiCall c;
+    if (int rc = c.reserve(n, H, splits)) return rc;
+    if (info) {
+        info[0] = c.p.hyp_tile, info[1] = c.p.match_tile, info[2] = c.p.splits, info[3] = c.p.workgroups;
+        info[4] = (int64_t)c.p.scratch_bytes, info[5] = c.p.match_tiles;
+    }
+    hipStream_t st = ctx().stream;
+    hipError_t e = c.upload(p1, p2, n, false);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.F(), F, (size_t)H * 72, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        KTimeScope kt;
+        c.launch_score(n, H, threshold * threshold);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, c.counts(), (size_t)H * 4, hipMemcpyDeviceToHost, st);
+    return epi_finish(__func__, e);
+}
+
+extern "C" int alp_epipolar_mask(const double *p1, const double *p2, int64_t n, const double F[9], double threshold, uint8_t *mask,
+                                 double *err) {
+    if (int rc = require_init()) return rc;
+    if (int rc = epi_check_points(__func__, p1, p2, n, 1)) return rc;
+    ALP_REQUIRE(F, "NULL F");
+    ALP_REQUIRE(std::isfinite(threshold) && threshold >= 0.0, "threshold must be finite and not negative");
+    EpiCall c;
+    if (int rc = c.reserve(n, 1, 1)) return rc;
+    hipStream_t st = ctx().stream;
+    hipError_t e = c.upload(p1, p2, n, false);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.F(), F, 72, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        KTimeScope kt;
+        hipLaunchKernelGGL(epi_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double4 *)c.pts(), (int)n,
+                           (const double *)c.F(), threshold * threshold, (const int *)nullptr, c.mask(), c.err());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, c.mask(), (size_t)n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && err) e = hipMemcpyAsync(err, c.err(), (size_t)n * 8, hipMemcpyDeviceToHost, st);
+    return epi_finish(__func__, e);
+}
+
+extern "C" int alp_epipolar_ransac(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, uint64_t seed,
+                                   double threshold, int refits, int splits, double F[9], uint8_t *mask, int64_t info[24]) {
+    if (int rc = require_init()) return rc;
+    if (int rc = epi_check_points(__func__, p1, p2, n, H)) return rc;
+    ALP_REQUIRE(std::isfinite(threshold) && threshold >= 0.0, "threshold must be finite and not negative");
+    ALP_REQUIRE(refits >= 0 && refits <= EPI_MAX_REFITS, "refits must be 0..8");
+    if (int rc = epi_check_splits(__func__, splits, n)) return rc;
+    if (samples)
+        if (int rc = epi_check_samples(__func__, samples, H, n)) return rc;
+    EpiCall c;
+    if (int rc = c.reserve(n, H, splits)) return rc;
+    const double t2 = threshold * threshold;
+    hipStream_t st = ctx().stream;
+    EpiState host_state;
+    hipError_t e = c.upload(p1, p2, n, true);
+    if (e == hipSuccess && samples) e = hipMemcpyAsync(c.samples(), samples, (size_t)H * EPI_SAMPLE * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        // the whole filter is enqueued at once; what a round does is decided on the device (EpiState::stopped)
+        KTimeScope kt;
+        const double4 *pts = c.pts();
+        EpiState *state = c.state();
+        const unsigned rb = (unsigned)c.p.reduce_blocks;
+        if (!samples) c.launch_samples(n, H, seed);
+        c.launch_solve(H);
+        c.launch_score(n, H, t2);
+        hipLaunchKernelGGL(epi_choose_kernel, dim3(1), dim3(256), 0, st, (const int *)c.counts(), (int)H, (const double *)c.F(), state);
+        for (int r = 0; r < refits; ++r) {
+            hipLaunchKernelGGL(epi_accum_kernel, dim3(rb), dim3(EPI_REDUCE_BLOCK), 0, st, pts, (int)n, t2, (const EpiState *)state, c.sym());
+            hipLaunchKernelGGL(epi_refit_kernel, dim3(1), dim3(64), 0, st, (const double *)c.sym(), (int)rb, state);
+            hipLaunchKernelGGL(epi_count_kernel, dim3(rb), dim3(EPI_REDUCE_BLOCK), 0, st, pts, (int)n, t2, (const EpiState *)state, c.cpart());
+            hipLaunchKernelGGL(epi_decide_kernel, dim3(1), dim3(64), 0, st, (const int *)c.cpart(), (int)rb, r, state);
+        }
+        hipLaunchKernelGGL(epi_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pts, (int)n, (const double *)state->Fcur, t2,
+                           (const int *)&state->keep_all, c.mask(), c.err());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, c.mask(), (size_t)n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&host_state, c.state(), sizeof(EpiState), hipMemcpyDeviceToHost, st);
+    if (int rc = epi_finish(__func__, e)) return rc;
+    if (F) memcpy(F, host_state.Fcur, 72);
+    if (info) {
+        for (int k = 0; k < EPI_INFO; ++k) info[k] = host_state.info[k];
+        info[I_HYP_TILE] = c.p.hyp_tile, info[I_MATCH_TILE] = c.p.match_tile, info[I_SPLITS] = c.p.splits, info[I_WORKGROUPS] = c.p.workgroups;
+        info[I_BYTES] = (int64_t)c.p.scratch_bytes, info[I_REDUCE_BLOCKS] = c.p.reduce_blocks;
+    }
+    return ALP_OK;
+}
+
+extern "C" int alp_grid_thin(const int64_t *cell_id, const double *dist, int64_t n, uint8_t *mask) {
+    if (int rc = require_init()) return rc;
+    ALP_REQUIRE(n >= 0 && n <= THIN_MAX_N, "n must be 0..2^30");
+    if (n == 0) return ALP_OK;
+    ALP_REQUIRE(cell_id && mask, "NULL input or output");
+    int64_t lo = cell_id[0], hi = cell_id[0];
+    for (int64_t i = 1; i < n; ++i) lo = std::min(lo, cell_id[i]), hi = std::max(hi, cell_id[i]);
+    // (unsigned: the difference of two int64 may pass INT64_MAX)
+    if ((uint64_t)hi - (uint64_t)lo >= (uint64_t)THIN_MAX_SPAN)
+        return fail(ALP_EINVAL, "alp_grid_thin: cell ids span %lld..%lld, more than 2^26 cells", (long long)lo, (long long)hi);
+    if (dist)
+        for (int64_t i = 0; i < n; ++i)
+            if (!(dist[i] >= 0.0)) return fail(ALP_EINVAL, "alp_grid_thin: dist[%lld] is negative or NaN", (long long)i);
+    const size_t span = (size_t)(hi - lo) + 1;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) / 256 * 256;
+        return o;
+    };
+    const size_t off_cell = take((size_t)n * 8), off_dist = take(dist ? (size_t)n * 8 : 0), off_tables = take(span * 16), off_mask = take((size_t)n);
+    DeviceBuffer<char> dev;
+    if (int rc = dev.reserve(at)) return rc;
+    char *d = dev;
+    long long *cell_dev = (long long *)(d + off_cell);
+    double *dist_dev = dist ? (double *)(d + off_dist) : nullptr;
+    u64 *best = (u64 *)(d + off_tables), *first = best + span;
+    hipStream_t st = ctx().stream;
+    hipError_t e = hipMemcpyAsync(cell_dev, cell_id, (size_t)n * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && dist) e = hipMemcpyAsync(dist_dev, dist, (size_t)n * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(best, 0xff, span * 16, st);
+    if (e == hipSuccess) {
+        KTimeScope kt;
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (dist) hipLaunchKernelGGL(thin_dist_kernel, grid, dim3(256), 0, st, (const long long *)cell_dev, (const double *)dist_dev, (long long)n, (long long)lo, best);
+        hipLaunchKernelGGL(thin_index_kernel, grid, dim3(256), 0, st, (const long long *)cell_dev, (const double *)dist_dev, (long long)n, (long long)lo,
+                           (const u64 *)best, first);
+        hipLaunchKernelGGL(thin_mask_kernel, grid, dim3(256), 0, st, (const long long *)cell_dev, (long long)n, (long long)lo, (const u64 *)first,
+                           (unsigned char *)(d + off_mask));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(mask, d + off_mask, (size_t)n, hipMemcpyDeviceToHost, st);
+    return epi_finish(__func__, e);
+}

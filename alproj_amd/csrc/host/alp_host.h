@@ -69,6 +69,7 @@ struct alignas(16) PoseRec {
 #include "host/alp_fold.h"      // fold_pose_hd / lens_free_from_general_hd: the arithmetic, host and device
 #include "host/alp_plan.h"      // RowDiv, pop_grid, stage_chunk_points, stream_grid, frame_plan, frame_verdict: the launch planning of alp_points.hip and alp_raster.hip
 #include "host/alp_matchplan.h" // MatchPlan, match_plan, match_split_range: the launch planning of alp_match.hip
+#include "host/alp_epiplan.h"   // EpiPlan, epi_plan, epi_caps_ok: the launch planning of alp_epipolar.hip
 namespace alp {
 
 // params: the 25 ABI parameters; origin: local origin of the point set (absolute coords).

@@ -651,6 +651,61 @@ void check_match_plan() {
     }
 }
 
+// ------------------------------------------------------------------ the launch plan of the geometric match filter (host/alp_epiplan.h)
+void check_epi_plan() {
+    // the caps: n in [8, 2^20], H in [1, 2^20], H * n <= 2^35, and nothing overflows on the way
+    CHECK(!host::epi_caps_ok(7, 1) && host::epi_caps_ok(8, 1) && host::epi_caps_ok(EPI_MAX_N, 1) && !host::epi_caps_ok(EPI_MAX_N + 1, 1), "caps of n");
+    CHECK(!host::epi_caps_ok(8, 0) && host::epi_caps_ok(8, EPI_MAX_H) && !host::epi_caps_ok(8, EPI_MAX_H + 1), "caps of H");
+    CHECK(host::epi_caps_ok(1 << 15, EPI_MAX_H) && !host::epi_caps_ok((1 << 15) + 1, EPI_MAX_H) && !host::epi_caps_ok(EPI_MAX_N, EPI_MAX_H) &&
+              host::epi_caps_ok(EPI_MAX_N, 1 << 15) && !host::epi_caps_ok(INT64_MAX, INT64_MAX) && !host::epi_caps_ok(-1, -1),
+          "caps of H * n");
+    const int64_t ns[] = {8, 9, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 5000, 50000, 1 << 20};
+    const int64_t hs[] = {1, 2, 63, 64, 65, 255, 256, 257, 1024, 16384, 131072, 600000, 1 << 20};
+    for (int cu : {1, 64, 256})
+        for (int64_t n : ns)
+            for (int64_t H : hs) {
+                if (!host::epi_caps_ok(n, H)) continue;
+                const int64_t tiles = (n + EPI_MATCH_TILE - 1) / EPI_MATCH_TILE;
+                for (int forced : {0, 1, 2, 3, 7, (int)tiles}) {
+                    if (forced > tiles) continue;              // the entry point refuses it
+                    const host::EpiPlan p = host::epi_plan(n, H, forced, cu);
+                    CHECK(p.hyp_tile == 256 && p.match_tile == 512, "tiles");
+                    CHECK(p.match_tiles == tiles && p.match_tiles * p.match_tile >= n && (p.match_tiles - 1) * p.match_tile < n, "match tiles of %" PRId64, n);
+                    CHECK(p.h_pad == p.hyp_tiles * p.hyp_tile && p.h_pad >= H && p.h_pad - H < p.hyp_tile, "hypothesis tiles of %" PRId64, H);
+                    CHECK(p.solve_blocks * EPI_SOLVE_BLOCK >= H && (p.solve_blocks - 1) * EPI_SOLVE_BLOCK < H, "solve blocks of %" PRId64, H);
+                    CHECK(p.reduce_blocks >= 1 && p.reduce_blocks <= EPI_REDUCE_MAX_BLOCKS &&
+                              (p.reduce_blocks == EPI_REDUCE_MAX_BLOCKS || (int64_t)p.reduce_blocks * EPI_REDUCE_BLOCK >= n),
+                          "reduce blocks of %" PRId64, n);
+                    if (forced) CHECK(p.splits == forced, "forced splits %d -> %d", forced, p.splits);
+                    else {
+                        // serial restatement: the first count that brings the grid to four workgroups per CU, capped by the tiles
+                        int64_t s = 1;
+                        while (s < tiles && s * p.hyp_tiles < 4 * cu) ++s;
+                        CHECK(p.splits == s, "splits(%" PRId64 " x %" PRId64 ", %d CUs) = %d, not %" PRId64, n, H, cu, p.splits, s);
+                    }
+                    CHECK(p.splits >= 1 && p.splits <= tiles && p.workgroups == p.hyp_tiles * p.splits && p.workgroups < ((int64_t)1 << 31), "grid");
+                    // the splits cover the match tiles once, in order, none empty
+                    int64_t covered = 0;
+                    for (int sp = 0; sp < p.splits; ++sp) {
+                        int64_t b, e;
+                        match_split_range(tiles, p.splits, sp, &b, &e);
+                        CHECK(b == covered && e > b, "split %d of %d over %" PRId64 " tiles: [%" PRId64 ", %" PRId64 ")", sp, p.splits, tiles, b, e);
+                        covered = e;
+                    }
+                    CHECK(covered == tiles, "splits cover %" PRId64 " of %" PRId64 " tiles", covered, tiles);
+                    // the device block: the arrays in order, aligned, none overlapping the next
+                    const size_t off[] = {p.off_raw1, p.off_raw2, p.off_pts, p.off_samples, p.off_F, p.off_partial, p.off_counts, p.off_state,
+                                          p.off_sym, p.off_cpart, p.off_mask, p.off_err, p.scratch_bytes};
+                    const size_t need[] = {(size_t)n * 16, (size_t)n * 16, (size_t)n * 32, (size_t)H * 32, (size_t)H * 72, (size_t)p.splits * p.h_pad * 4,
+                                           (size_t)H * 4, (size_t)EPI_STATE_BYTES, (size_t)p.reduce_blocks * EPI_SYM * 8, (size_t)p.reduce_blocks * 4,
+                                           (size_t)n, (size_t)n * 8};
+                    CHECK(off[0] == 0, "first offset");
+                    for (int i = 0; i < 12; ++i)
+                        CHECK(off[i] % 256 == 0 && off[i + 1] >= off[i] + need[i] && off[i + 1] < off[i] + need[i] + 256, "array %d of the block", i);
+                }
+            }
+}
+
 // ------------------------------------------------------------------ the error message is per thread
 void check_errors() {
     std::vector<std::thread> th;
@@ -701,6 +756,7 @@ int canary(const char *which) {
 // normal,n,cu -> "blocks groups_per" of normal_batch_grid for one pose
 // normal_batch,n,B,cu -> "blocks groups_per" of normal_batch_grid (blocks = the stripes per pose), 1 <= B <= NORMAL_BATCH_MAX
 // mend,n,P,V,TC,cu -> "stripes tile_cols" of mend_grid
+// epi,n,H,forced_splits,cu -> "hyp_tile match_tile splits hyp_tiles match_tiles workgroups solve_blocks reduce_blocks bytes" of epi_plan
 // frame,implicit,grid_h,grid_w,n_tri,w,h,cu,tile_w,tile_h -> "tiles_x tiles plan_grid grid_wgs parked_wgs[0] parked_wgs[1] general_wgs large_wgs
 //   index_grid resolve_grid tile_bounds_bytes tile_lists_bytes" of frame_plan
 // queues,ALP_QUEUE_CAP text or '-' -> "cap small large cells small_b large_b cells_b": the start capacities
@@ -765,6 +821,19 @@ int plan_query(const char *q) {
         }
         const host::NormalGrid g = host::normal_batch_grid(nn, 1, ncu);
         printf("%d %lld\n", g.blocks, (long long)g.groups_per);
+        return 0;
+    }
+    if (!strncmp(q, "epi,", 4)) {
+        long long nn = 0, hh = 0;
+        int forced = 0, ecu = 0;
+        if (sscanf(q + 4, "%lld,%lld,%d,%d", &nn, &hh, &forced, &ecu) != 4 || !host::epi_caps_ok(nn, hh) || forced < 0 || ecu < 1 ||
+            forced > (nn + EPI_MATCH_TILE - 1) / EPI_MATCH_TILE) {
+            fprintf(stderr, "bad plan query: %s\n", q);
+            return 2;
+        }
+        const host::EpiPlan p = host::epi_plan(nn, hh, forced, ecu);
+        printf("%d %d %d %lld %lld %lld %lld %d %lld\n", p.hyp_tile, p.match_tile, p.splits, (long long)p.hyp_tiles, (long long)p.match_tiles,
+               (long long)p.workgroups, (long long)p.solve_blocks, p.reduce_blocks, (long long)p.scratch_bytes);
         return 0;
     }
     if (!strncmp(q, "mend,", 5)) {
@@ -1038,7 +1107,8 @@ int main(int argc, char **argv) {
     const Group groups[] = {{"hash", check_hash},     {"minmax", check_minmax},   {"prefault", check_prefault}, {"fold_pose", check_fold_pose},
                             {"convert", check_convert}, {"grid", check_grid},     {"selection", check_selection}, {"errors", check_errors},
                             {"plan", check_plan},       {"frame_plan", check_frame_plan}, {"row_div", check_row_div}, {"lm", check_lm},
-                            {"buffer", check_buffer},   {"row_walk", check_row_walk}, {"match_plan", check_match_plan}};
+                            {"buffer", check_buffer},   {"row_walk", check_row_walk}, {"match_plan", check_match_plan},
+                            {"epi_plan", check_epi_plan}};
     const bool concurrent = !(argc > 1 && !strcmp(argv[1], "--serial"));
     // every group on its own caller thread at once: the library promises that independent calls may overlap
     std::vector<std::thread> th;

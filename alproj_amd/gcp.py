@@ -15,7 +15,18 @@ too) and Lowe's ratio test:
 
 AKAZE descriptors are bytes and OpenCV's SIFT descriptors are float32 holding the integers 0..255,
 so the squared distances are exact integers formed on the int8 matrix cores (``alp_match_knn2``).
-Detection (``detectAndCompute``), the geometric filters (cv2's USAC / RANSAC), ``_filter_spatial``
+
+The two steps that ``image_match`` runs on every set of matches before it returns (src/alproj/gcp.py:507-544):
+
+* ``filter_geometric``   ``_filter_geometric`` with ``outlier_filter="fundamental"`` (gcp.py:254-273): H fundamental
+                         matrices from 8-point samples, each scored on all matches, the best one refitted
+                         (``alp_epipolar_ransac``).  The inlier set is NOT cv2's: cv2's random stream and MAGSAC
+                         scoring cannot be restated, so the algorithm is this project's own, plain inlier counting
+                         with the error measure of cv2's classic ``FM_RANSAC``
+* ``filter_spatial``     ``_filter_spatial`` (gcp.py:282-357), bit for bit (``alp_grid_thin``)
+* ``filter_matches``     lines 507-544 as a whole: points -> the DataFrame u_org, v_org, u_sim, v_sim
+
+Detection (``detectAndCompute``), the essential-matrix filter, cv2's USAC / MAGSAC / LMedS scoring
 and the learned matchers behind ``vismatch`` stay with the reference: cv2 is neither imported nor
 needed here.  ``set_gcp`` accepts, besides the reference's
 ``reverse_proj`` DataFrame, the device-resident ``alproj_amd.project.ReverseProjection``: the
@@ -28,7 +39,8 @@ import pandas as pd
 from . import _lib
 from .project import ReverseProjection
 
-__all__ = ["set_gcp", "filter_gcp_distance", "knn_match", "match_descriptors", "match_keypoints"]
+__all__ = ["set_gcp", "filter_gcp_distance", "knn_match", "match_descriptors", "match_keypoints", "filter_geometric",
+           "filter_spatial", "filter_matches"]
 
 
 def set_gcp(match, rev_proj):
@@ -110,3 +122,134 @@ def match_keypoints(pts_org, des_org, pts_sim, des_sim, ratio=0.7):
     if len(query_idx) == 0:
         return _no_points()
     return np.float32(pts_org[query_idx]).astype("int32"), np.float32(pts_sim[train_idx]).astype("int32")
+
+
+def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypotheses=16384, seed=0, refits=4, samples=None,
+                     return_model=False):
+    """``_filter_geometric`` (reference gcp.py:160-279) for ``method="fundamental"``, on the device: a bool mask of the matches
+    that agree with one fundamental matrix.
+
+    ``hypotheses`` 8-point samples are drawn from ``seed`` (or taken from ``samples``, (H, 8) indices), each solved by the
+    normalised 8-point algorithm and scored by its number of matches whose larger squared point-to-epipolar-line distance is at
+    most ``threshold``^2 (cv2's classic ``FM_RANSAC`` measure); the best one is refitted on its inliers up to ``refits`` times
+    while that strictly grows the count.  The inlier set is not cv2's: another sampler, and plain counting instead of MAGSAC.
+
+    The default ``hypotheses = 16384`` is what confidence 0.999 needs for 8-point samples down to an inlier share w of about
+    0.38: H = log(1 - 0.999) / log(1 - w^8), about 16 000 at w = 0.38 (3 100 at w = 0.5, 118 at w = 0.7).  The device evaluates
+    all of them outright, so nothing is saved by stopping early.
+
+    The edge cases are the reference's (gcp.py:189-198, 254-257, 275-279): an empty input gives an empty bool array, ``"none"``
+    all True, fewer than 8 points all True, an unknown method the reference's ``ValueError``; fewer than 8 inliers anywhere
+    give all True as well (cv2 returning no mask, gcp.py:270-271).  ``"essential"`` raises ``NotImplementedError``: the 5-point
+    solver stays with the reference.
+
+    ``return_model=True`` returns (mask, F, info): F (3, 3) with b^T F a = 0 for a = (x1, y1, 1), b = (x2, y2, 1), or None when
+    no model was fitted, and the info dict of ``_lib.epipolar_ransac``."""
+    pts1 = np.asarray(pts1, dtype=np.float64)
+    pts2 = np.asarray(pts2, dtype=np.float64)
+
+    def result(mask, F=None, info=None):
+        return (mask, F, info or {}) if return_model else mask
+
+    if len(pts1) == 0:
+        return result(np.array([], dtype=bool))
+    method_lower = method.lower()
+    if method_lower == "none":
+        return result(np.ones(len(pts1), dtype=bool))
+    if method_lower == "essential":
+        raise NotImplementedError("outlier_filter='essential' (cv2.findEssentialMat, the 5-point solver) stays with the reference; "
+                                  "use 'fundamental' or 'none'")
+    if method_lower != "fundamental":
+        raise ValueError(
+            f"Unknown outlier_filter '{method}'. "
+            "Available: 'essential', 'fundamental', 'none'"
+        )
+    if len(pts1) < 8:
+        return result(np.ones(len(pts1), dtype=bool))
+    if pts1.ndim != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise ValueError(f"points must be two (n, 2) arrays of one length, not {pts1.shape} and {pts2.shape}")
+    if not (np.isfinite(pts1).all() and np.isfinite(pts2).all()):
+        raise ValueError("point coordinates must be finite")
+    if not (np.isfinite(threshold) and threshold >= 0):
+        raise ValueError("threshold must be finite and not negative")
+    if samples is None and int(hypotheses) < 1:
+        raise ValueError("hypotheses must be at least 1")
+    if not 0 <= int(refits) <= _lib.EPI_MAX_REFITS:
+        raise ValueError(f"refits must be 0..{_lib.EPI_MAX_REFITS}")
+    r = _lib.epipolar_ransac(pts1, pts2, threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
+    return result(r["mask"], r["F"], r["info"])
+
+
+def _spatial_cells(pts, grid_size, image_size):
+    # reference gcp.py:322-325, verbatim: what this arithmetic does to a point outside the image is part of the contract
+    cell_col = (pts[:, 0] // grid_size).astype(int)
+    cell_row = (pts[:, 1] // grid_size).astype(int)
+    n_cols = int(np.ceil(image_size[0] / grid_size))
+    return cell_col, cell_row, cell_row * n_cols + cell_col
+
+
+def filter_spatial(pts, grid_size, image_size, selection="first", random_state=None):
+    """``_filter_spatial`` (reference gcp.py:282-357), bit for bit: a bool mask that keeps one point per grid cell of
+    ``grid_size`` pixels.
+
+    ``"first"`` keeps the lowest index of each cell and ``"center"`` the point nearest the cell centre (the lowest index on an
+    equal distance); both run on the device (``alp_grid_thin``), on the cell ids and distances formed with the reference's own
+    expressions (gcp.py:322-325, 339-345).  ``"random"`` groups on the host and draws with the reference's own calls,
+    ``default_rng(random_state)`` and one ``rng.choice`` per cell in ascending cell order: numpy's stream cannot be restated on
+    the device.  Validation, messages and the empty case are the reference's (gcp.py:315-319, 349-353)."""
+    if grid_size <= 0:
+        raise ValueError("grid_size must be positive")
+    if len(pts) == 0:
+        return np.array([], dtype=bool)
+    pts = np.asarray(pts)
+    cell_col, cell_row, cell_id = _spatial_cells(pts, grid_size, image_size)
+    if selection == "first":
+        return _lib.grid_thin(cell_id)
+    if selection == "random":
+        rng = np.random.default_rng(random_state)
+        order = np.argsort(cell_id, kind="stable")              # ascending cells, input order within a cell: pandas' groups
+        starts = np.flatnonzero(np.r_[True, cell_id[order][1:] != cell_id[order][:-1]])
+        selected = [rng.choice(group) for group in np.split(order.astype(np.int64), starts[1:])]
+        mask = np.zeros(len(pts), dtype=bool)
+        mask[selected] = True
+        return mask
+    if selection == "center":
+        cell_center_x = (cell_col + 0.5) * grid_size
+        cell_center_y = (cell_row + 0.5) * grid_size
+        dist_to_center = np.sqrt(
+            (pts[:, 0] - cell_center_x) ** 2 +
+            (pts[:, 1] - cell_center_y) ** 2
+        )
+        return _lib.grid_thin(cell_id, dist_to_center)
+    raise ValueError(
+        f"Unknown selection '{selection}'. "
+        "Available: 'first', 'random', 'center'"
+    )
+
+
+def filter_matches(pts1, pts2, image_size, outlier_filter="fundamental", threshold=10.0, spatial_thin_grid=None,
+                   spatial_thin_selection="first", spatial_thin_random_state=None, **ransac):
+    """``image_match`` from its line 507 to 544 (reference gcp.py), given the points ``match_keypoints`` returns: the geometric
+    filter, then the spatial thinning on ``pts1``, then the DataFrame ``u_org, v_org, u_sim, v_sim`` (the empty frame with those
+    columns when nothing is left).  ``image_size`` is (width, height) of the photograph, or None when no thinning is asked for;
+    ``**ransac`` goes to ``filter_geometric`` (hypotheses, seed, refits, samples)."""
+    pts1, pts2 = np.asarray(pts1), np.asarray(pts2)
+    if outlier_filter != "none" and len(pts1) > 0:
+        mask = filter_geometric(pts1, pts2, method=outlier_filter, threshold=threshold, **ransac)
+        pts1 = pts1[mask]
+        pts2 = pts2[mask]
+    if spatial_thin_grid is not None and len(pts1) > 0:
+        if image_size is None:
+            raise ValueError(
+                "image_size could not be determined. "
+                "Ensure path_org is a valid image file."
+            )
+        mask = filter_spatial(pts1, grid_size=spatial_thin_grid, image_size=image_size, selection=spatial_thin_selection,
+                              random_state=spatial_thin_random_state)
+        pts1 = pts1[mask]
+        pts2 = pts2[mask]
+    if len(pts1) == 0:
+        return pd.DataFrame(columns=["u_org", "v_org", "u_sim", "v_sim"])
+    pts1 = np.atleast_2d(pts1)
+    pts2 = np.atleast_2d(pts2)
+    return pd.DataFrame(np.hstack((pts1, pts2)), columns=["u_org", "v_org", "u_sim", "v_sim"])

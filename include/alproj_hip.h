@@ -687,6 +687,57 @@ int alp_match_knn2(const void *query, int64_t n_query, const void *train, int64_
                    double ratio, int splits, int32_t *idx, int32_t *dist2, float *dist, uint8_t *good,
                    int64_t *n_good, int64_t info[6]);
 
+/* The geometric outlier filter that image_match runs on every set of matches, src/alproj/gcp.py:507-519 (_filter_geometric with
+ * outlier_filter="fundamental", gcp.py:254-273).  cv2's USAC cannot be restated (its random stream, MAGSAC scoring), so this is an
+ * algorithm of the library's own: H minimal samples of 8 matches, the normalised 8-point fundamental matrix of each, the inlier
+ * count of each over all n matches, the best one refitted on its inliers.  Everything is float64.  p1[n][2] (the photograph) and
+ * p2[n][2] (the simulated image) are pixel coordinates; F is row-major, 9 doubles, with b^T F a = 0 for a = (x1, y1, 1) and
+ * b = (x2, y2, 1).  The error of a match under F is the measure of cv2's classic FM_RANSAC, the larger of the two squared
+ * point-to-epipolar-line distances, evaluated in exactly this order without fused multiply-adds:
+ *     l2_i = (F[i][0]*x1 + F[i][1]*y1) + F[i][2]      i = 0..2
+ *     l1_j = (F[0][j]*x2 + F[1][j]*y2) + F[2][j]      j = 0..1
+ *     s    = (x2*l2_0 + y2*l2_1) + l2_2
+ *     e    = max(s*s / (l2_0*l2_0 + l2_1*l2_1), s*s / (l1_0*l1_0 + l1_1*l1_1))
+ *     inlier  <=>  e <= threshold*threshold            (a NaN e is no inlier)
+ * Caps of every entry point: 8 <= n <= 2^20, 1 <= H <= 2^20, H * n <= 2^35; a finite threshold >= 0; otherwise ALP_EINVAL before
+ * anything is uploaded, as for NULL arrays, a sample index outside [0, n) and splits above the number of match tiles.
+ *
+ * alp_epipolar_samples: samples[H][8], every row 8 distinct indices in [0, n) from the counter-based generator of the CMA-ES
+ *   sampler keyed by (seed, hypothesis, attempt); a repeat within the row is rejected and the next draw taken.  A function of
+ *   (n, H, seed) alone.
+ * alp_epipolar_solve8: F[H][9], the normalised 8-point solve of every sample: Hartley's normalisation formed once from all n
+ *   points (centroid, mean distance sqrt 2), the null vector of the sample's 8 x 9 matrix, the smallest singular value of the
+ *   3 x 3 matrix zeroed, T2^T F T1, unit Frobenius norm.  A sample whose matrix has rank below 8 (a repeated point), or whose F
+ *   is not finite, gives 9 NaN.  The sign of F is not fixed.
+ * alp_epipolar_score: counts[H], the number of inliers of every F (0 for a NaN F).  splits: 0 = the launch plan's choice of how
+ *   many ranges the matches are divided into, > 0 forces it (tests; the counts do not depend on it).  info, may be NULL:
+ *   hypothesis tile, match tile, splits used, workgroups, device bytes of the call, match tiles.
+ * alp_epipolar_mask: mask[n] and err[n] (either may be NULL) of every match under one F.
+ * alp_epipolar_ransac: the whole filter, enqueued at once with no host round trip between its stages.  samples: NULL = drawn
+ *   from `seed` as alp_epipolar_samples draws them, else samples[H][8].  The hypothesis with the highest count is chosen, the
+ *   lowest index on a tie.  Up to `refits` (0..8) times the 8-point solution is then fitted to all current inliers (the
+ *   eigenvector of the smallest eigenvalue of the 9 x 9 sum over them, rank 2) and re-scored; it replaces the current F only when
+ *   the count strictly grows, otherwise the loop stops.  F[9] and mask[n] (either may be NULL): the final F and its inliers.  When
+ *   the chosen count is below 8, every mask entry is 1 (the reference keeps all matches when cv2 returns no mask, gcp.py:270-271).
+ *   info[24], may be NULL: [0] chosen hypothesis, [1] its count, [2] the final count, [3] refits run, [4] refits kept, [5] 1 when
+ *   all matches were kept for want of 8 inliers, [6] hypothesis tile, [7] match tile, [8] splits, [9] workgroups of the score,
+ *   [10] device bytes, [11] workgroups of the refit's reductions, [12..19] the count of each refit run (-1: not run). */
+int alp_epipolar_samples(int64_t n, int64_t H, uint64_t seed, int32_t *samples);
+int alp_epipolar_solve8(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, double *F);
+int alp_epipolar_score(const double *p1, const double *p2, int64_t n, const double *F, int64_t H, double threshold,
+                       int splits, int32_t *counts, int64_t info[6]);
+int alp_epipolar_mask(const double *p1, const double *p2, int64_t n, const double F[9], double threshold,
+                      uint8_t *mask, double *err);
+int alp_epipolar_ransac(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H,
+                        uint64_t seed, double threshold, int refits, int splits, double F[9], uint8_t *mask,
+                        int64_t info[24]);
+
+/* The spatial thinning of image_match, src/alproj/gcp.py:282-357 (_filter_spatial): mask[n] keeps one point per distinct value
+ * of cell_id[n].  dist == NULL: the lowest index of each cell (selection="first").  Otherwise the lowest dist of each cell, the
+ * lowest index on an equal dist (selection="center": pandas' idxmin); dist must be >= 0 and not NaN.  The table is indexed by
+ * cell_id - min(cell_id): a span above 2^26 cells is ALP_EINVAL, as is n above 2^30.  n = 0: nothing happens. */
+int alp_grid_thin(const int64_t *cell_id, const double *dist, int64_t n, uint8_t *mask);
+
 /* Compute part of to_geotiff(), src/alproj/project.py:376-503 (the GeoTIFF file itself is
  * written by the caller): n points (x, y, values[n][nb]) -> uint8 raster out[nb][height][width].
  * Pixel of a point: col = int((x - x_min) / resolution), row = int((y_max - y) / resolution),

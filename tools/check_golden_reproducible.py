@@ -40,6 +40,7 @@ GENERATORS = [
     ("gen_golden_geotiff_bytes.py", ["g18_geotiff_bytes"]),
     ("gen_golden_first_phase.py", ["g19_first_phase"]),
     ("gen_golden_weighted.py", ["g20_weighted"]),
+    ("gen_golden_spatial.py", ["g21_filter_spatial"]),
 ]
 
 
