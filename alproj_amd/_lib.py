@@ -287,6 +287,10 @@ _SIGNATURES = {
     "alp_epipolar_mask": [_c_dp, _c_dp, _c_i64, _c_dp, _c_double, ctypes.POINTER(ctypes.c_uint8), _c_dp],
     "alp_epipolar_ransac": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_uint64, _c_double, _c_int, _c_int,
                             _c_dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64)],
+    "alp_epipolar_samples5": [_c_i64, _c_i64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)],
+    "alp_epipolar_solve5": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, _c_dp, _c_dp, ctypes.POINTER(ctypes.c_int32)],
+    "alp_essential_ransac": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_uint64, _c_dp, _c_double, _c_int, _c_int,
+                             _c_dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64)],
     "alp_grid_thin": [ctypes.POINTER(_c_i64), _c_dp, _c_i64, ctypes.POINTER(ctypes.c_uint8)],
     "alp_rasterize_points": [_c_dp, _c_dp, _c_dp, _c_i64, _c_i64, _c_double, _c_double, _c_double, _c_i64, _c_i64,
                              _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_uint8)],
@@ -1164,11 +1168,19 @@ def _epi_points(p1, p2):
     return p1, p2
 
 
-def _epi_samples(samples, n):
+def _epi_samples(samples, n, width=8):
     samples = np.ascontiguousarray(samples, dtype=np.int32)
-    if samples.ndim != 2 or samples.shape[1] != 8 or samples.shape[0] < 1:
-        raise ValueError(f"samples must be (H, 8) with H >= 1, not {samples.shape}")
+    if samples.ndim != 2 or samples.shape[1] != width or samples.shape[0] < 1:
+        raise ValueError(f"samples must be (H, {width}) with H >= 1, not {samples.shape}")
     return samples
+
+
+def _epi_K(focal_length, principal_point):
+    """(f, cx, cy) as the essential entry points take it, or ValueError: f finite and positive, (cx, cy) two finite numbers."""
+    K = np.array([focal_length, *np.asarray(principal_point, dtype=np.float64).reshape(-1)], dtype=np.float64)
+    if K.shape != (3,) or not np.isfinite(K).all() or not K[0] > 0:
+        raise ValueError("focal_length must be finite and positive, principal_point two finite numbers")
+    return K
 
 
 _c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -1217,6 +1229,14 @@ def epipolar_mask(p1, p2, F, threshold):
     return mask.astype(bool), err
 
 
+def _epi_ransac_info(info):
+    v = [int(x) for x in info]
+    run = v[3]
+    return {"chosen": v[0], "chosen_count": v[1], "final_count": v[2], "refits_run": run, "refits_kept": v[4],
+            "keep_all": bool(v[5]), "hyp_tile": v[6], "match_tile": v[7], "splits": v[8], "workgroups": v[9],
+            "scratch_bytes": v[10], "reduce_blocks": v[11], "refit_counts": v[12:12 + run]}
+
+
 def epipolar_ransac(p1, p2, threshold, hypotheses=16384, seed=0, refits=4, samples=None, splits=0):
     """alp_epipolar_ransac: the whole geometric filter in one device loop -> dict F (3, 3), mask (n,) bool, info (chosen,
     chosen_count, final_count, refits_run, refits_kept, keep_all, refit_counts, and the launch plan)."""
@@ -1231,12 +1251,49 @@ def epipolar_ransac(p1, p2, threshold, hypotheses=16384, seed=0, refits=4, sampl
     check(lib().alp_epipolar_ransac(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
                                     hypotheses, int(seed) & (2 ** 64 - 1), float(threshold), int(refits), int(splits), as_dp(F),
                                     mask.ctypes.data_as(_c_u8p), info))
-    v = [int(x) for x in info]
-    run = v[3]
-    return {"F": F, "mask": mask.astype(bool),
-            "info": {"chosen": v[0], "chosen_count": v[1], "final_count": v[2], "refits_run": run, "refits_kept": v[4],
-                     "keep_all": bool(v[5]), "hyp_tile": v[6], "match_tile": v[7], "splits": v[8], "workgroups": v[9],
-                     "scratch_bytes": v[10], "reduce_blocks": v[11], "refit_counts": v[12:12 + run]}}
+    return {"F": F, "mask": mask.astype(bool), "info": _epi_ransac_info(info)}
+
+
+def epipolar_samples5(n, hypotheses, seed=0):
+    """alp_epipolar_samples5: (H, 5) int32, every row 5 distinct indices in [0, n); a function of (n, H, seed) alone, and another
+    stream than the 8-wide rows of the same seed."""
+    hypotheses = int(hypotheses)
+    if hypotheses < 1:
+        raise ValueError("hypotheses must be at least 1")
+    out = np.empty((hypotheses, 5), dtype=np.int32)
+    check(lib().alp_epipolar_samples5(int(n), hypotheses, int(seed) & (2 ** 64 - 1), out.ctypes.data_as(_c_i32p)))
+    return out
+
+
+def epipolar_solve5(p1, p2, samples, focal_length, principal_point):
+    """alp_epipolar_solve5: (F (H, 10, 3, 3) float64, nsol (H,) int32): the essential matrices of every sample of five matches as
+    pixel-space matrices K^-T E K^-1 at unit norm, in ascending order of the solver's root, NaN in the unused slots."""
+    p1, p2 = _epi_points(p1, p2)
+    samples = _epi_samples(samples, len(p1), 5)
+    K = _epi_K(focal_length, principal_point)
+    F = np.empty((len(samples), 10, 3, 3), dtype=np.float64)
+    nsol = np.empty(len(samples), dtype=np.int32)
+    check(lib().alp_epipolar_solve5(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p), len(samples), as_dp(K), as_dp(F),
+                                    nsol.ctypes.data_as(_c_i32p)))
+    return F, nsol
+
+
+def essential_ransac(p1, p2, focal_length, principal_point, threshold, hypotheses=16384, seed=0, refits=4, samples=None, splits=0):
+    """alp_essential_ransac: the essential-matrix filter in one device loop -> dict F (3, 3) in pixel coordinates, mask (n,) bool,
+    info as for epipolar_ransac; ``chosen`` is sample * 10 + slot."""
+    p1, p2 = _epi_points(p1, p2)
+    K = _epi_K(focal_length, principal_point)
+    if samples is not None:
+        samples = _epi_samples(samples, len(p1), 5)
+        hypotheses = len(samples)
+    hypotheses = int(hypotheses)
+    F = np.empty((3, 3), dtype=np.float64)
+    mask = np.empty(len(p1), dtype=np.uint8)
+    info = (_c_i64 * 24)()
+    check(lib().alp_essential_ransac(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
+                                     hypotheses, int(seed) & (2 ** 64 - 1), as_dp(K), float(threshold), int(refits), int(splits), as_dp(F),
+                                     mask.ctypes.data_as(_c_u8p), info))
+    return {"F": F, "mask": mask.astype(bool), "info": _epi_ransac_info(info)}
 
 
 def grid_thin(cell_id, dist=None):

@@ -10,7 +10,9 @@
 
 namespace alp {
 
-constexpr int EPI_SAMPLE = 8;                  // matches of a minimal sample
+constexpr int EPI_SAMPLE = 8;                  // matches of a minimal sample of the fundamental filter
+constexpr int EPI_SAMPLE5 = 5;                 // and of the essential filter,
+constexpr int EPI_SLOTS5 = 10;                 // whose every sample fills up to ten hypothesis slots: it is planned as H' = 10 H
 constexpr int EPI_HYP_TILE = 256;              // hypotheses of a workgroup of the score kernel: one per lane
 constexpr int EPI_MATCH_TILE = 512;            // matches staged in LDS at a time, 32 B each
 constexpr int EPI_SOLVE_BLOCK = 64;            // hypotheses of a workgroup of the solve kernel: one per lane, its 8 x 9 matrix in LDS
@@ -42,9 +44,10 @@ struct EpiPlan {
            off_sym = 0, off_cpart = 0, off_mask = 0, off_err = 0, scratch_bytes = 0;
 };
 
-// n in [8, 2^20], H in [1, 2^20], H * n <= 2^35: what every entry point of the unit requires before it plans
-inline bool epi_caps_ok(int64_t n, int64_t H) {
-    return n >= EPI_MIN_N && n <= EPI_MAX_N && H >= 1 && H <= EPI_MAX_H && H <= EPI_MAX_WORK / n;
+// n in [8, 2^20] (min_n = 5: the essential filter), H in [1, 2^20], H * n <= 2^35: what every entry point of the unit requires
+// before it plans
+inline bool epi_caps_ok(int64_t n, int64_t H, int64_t min_n = EPI_MIN_N) {
+    return n >= min_n && n <= EPI_MAX_N && H >= 1 && H <= EPI_MAX_H && H <= EPI_MAX_WORK / n;
 }
 
 // splits: as many as bring the grid to four workgroups per CU, at most one per match tile; `forced` > 0 replaces the choice (the

@@ -659,6 +659,15 @@ void check_epi_plan() {
     CHECK(host::epi_caps_ok(1 << 15, EPI_MAX_H) && !host::epi_caps_ok((1 << 15) + 1, EPI_MAX_H) && !host::epi_caps_ok(EPI_MAX_N, EPI_MAX_H) &&
               host::epi_caps_ok(EPI_MAX_N, 1 << 15) && !host::epi_caps_ok(INT64_MAX, INT64_MAX) && !host::epi_caps_ok(-1, -1),
           "caps of H * n");
+    // the essential filter: samples of 5, and a call of H samples is planned for 10 H slots, whose sample block (32 bytes a slot)
+    // holds the H rows of 5 indices from byte 0 and the H solution counts from byte 32 H
+    CHECK(!host::epi_caps_ok(4, 10, EPI_SAMPLE5) && host::epi_caps_ok(5, 10, EPI_SAMPLE5) && !host::epi_caps_ok(5, EPI_MAX_H + 10, EPI_SAMPLE5),
+          "caps of the essential filter");
+    for (int64_t H : {1, 26, 257, (int)(EPI_MAX_H / EPI_SLOTS5)}) {
+        const host::EpiPlan p = host::epi_plan(5, H * EPI_SLOTS5, 0, 256);
+        CHECK((size_t)H * EPI_SAMPLE5 * 4 <= (size_t)H * 32 && p.off_samples + (size_t)H * 36 <= p.off_F, "sample block of %" PRId64 " samples of 5", H);
+        CHECK(p.off_F + (size_t)H * EPI_SLOTS5 * 72 <= p.off_partial && p.h_pad >= H * EPI_SLOTS5, "slots of %" PRId64 " samples of 5", H);
+    }
     const int64_t ns[] = {8, 9, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 5000, 50000, 1 << 20};
     const int64_t hs[] = {1, 2, 63, 64, 65, 255, 256, 257, 1024, 16384, 131072, 600000, 1 << 20};
     for (int cu : {1, 64, 256})

@@ -20,19 +20,24 @@ The two steps that ``image_match`` runs on every set of matches before it return
 
 * ``filter_geometric``   ``_filter_geometric`` with ``outlier_filter="fundamental"`` (gcp.py:254-273): H fundamental
                          matrices from 8-point samples, each scored on all matches, the best one refitted
-                         (``alp_epipolar_ransac``).  The inlier set is NOT cv2's: cv2's random stream and MAGSAC
+                         (``alp_epipolar_ransac``); and with ``outlier_filter="essential"`` (gcp.py:200-252) given a focal
+                         length: up to 10 essential matrices from each of H 5-point samples (Nister's solver), scored
+                         and chosen the same way in pixel coordinates, the refit projected onto the essential matrices
+                         (``alp_essential_ransac``).  The inlier set is NOT cv2's: cv2's random stream and MAGSAC
                          scoring cannot be restated, so the algorithm is this project's own, plain inlier counting
                          with the error measure of cv2's classic ``FM_RANSAC``
 * ``filter_spatial``     ``_filter_spatial`` (gcp.py:282-357), bit for bit (``alp_grid_thin``)
 * ``filter_matches``     lines 507-544 as a whole: points -> the DataFrame u_org, v_org, u_sim, v_sim
 
-Detection (``detectAndCompute``), the essential-matrix filter, cv2's USAC / MAGSAC / LMedS scoring
-and the learned matchers behind ``vismatch`` stay with the reference: cv2 is neither imported nor
-needed here.  ``set_gcp`` accepts, besides the reference's
+Detection (``detectAndCompute``), the essential-matrix filter's guess of a focal length that nobody
+gave it (gcp.py:206-220), cv2's USAC / MAGSAC / LMedS scoring and the learned matchers behind
+``vismatch`` stay with the reference: cv2 is neither imported nor needed here.  ``set_gcp`` accepts, besides the reference's
 ``reverse_proj`` DataFrame, the device-resident ``alproj_amd.project.ReverseProjection``: the
 (u_sim, v_sim) -> (x, y, z) join then becomes one gather from the coordinate image in HBM
 (``alp_render_gather``) and the multi-million-row table is never built.
 """
+import math
+
 import numpy as np
 import pandas as pd
 
@@ -125,26 +130,36 @@ def match_keypoints(pts_org, des_org, pts_sim, des_sim, ratio=0.7):
 
 
 def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypotheses=16384, seed=0, refits=4, samples=None,
-                     return_model=False):
-    """``_filter_geometric`` (reference gcp.py:160-279) for ``method="fundamental"``, on the device: a bool mask of the matches
-    that agree with one fundamental matrix.
+                     return_model=False, focal_length=None, principal_point=None, image_size=None):
+    """``_filter_geometric`` (reference gcp.py:160-279) for ``method="fundamental"`` and ``method="essential"``, on the device: a
+    bool mask of the matches that agree with one fundamental or essential matrix.
 
-    ``hypotheses`` 8-point samples are drawn from ``seed`` (or taken from ``samples``, (H, 8) indices), each solved by the
-    normalised 8-point algorithm and scored by its number of matches whose larger squared point-to-epipolar-line distance is at
-    most ``threshold``^2 (cv2's classic ``FM_RANSAC`` measure); the best one is refitted on its inliers up to ``refits`` times
-    while that strictly grows the count.  The inlier set is not cv2's: another sampler, and plain counting instead of MAGSAC.
+    ``"fundamental"``: ``hypotheses`` 8-point samples are drawn from ``seed`` (or taken from ``samples``, (H, 8) indices), each
+    solved by the normalised 8-point algorithm and scored by its number of matches whose larger squared point-to-epipolar-line
+    distance is at most ``threshold``^2 (cv2's classic ``FM_RANSAC`` measure); the best one is refitted on its inliers up to
+    ``refits`` times while that strictly grows the count.  The inlier set is not cv2's: another sampler, and plain counting
+    instead of MAGSAC.
+
+    ``"essential"``: the samples hold 5 matches (``samples``: (H, 5)), each solved by the five-point algorithm in coordinates
+    normalised by K = (``focal_length``, ``principal_point``), one K for both images as the reference builds it (gcp.py:232-236).
+    Each of the up to 10 essential matrices of a sample is scored as the pixel-space matrix K^-T E K^-1 with the same measure
+    and the same ``threshold`` in pixels; the refit is projected onto the essential matrices.  ``principal_point`` missing:
+    half of ``image_size``, else the midpoint of the bounding box of ``pts1`` (gcp.py:223-229).  ``focal_length`` missing:
+    ``NotImplementedError``: the reference's guess "focal length = image width" (gcp.py:206-220) stays with the reference,
+    because a filter that is preferred for its use of the intrinsics should not invent them.
 
     The default ``hypotheses = 16384`` is what confidence 0.999 needs for 8-point samples down to an inlier share w of about
-    0.38: H = log(1 - 0.999) / log(1 - w^8), about 16 000 at w = 0.38 (3 100 at w = 0.5, 118 at w = 0.7).  The device evaluates
-    all of them outright, so nothing is saved by stopping early.
+    0.38: H = log(1 - 0.999) / log(1 - w^8), about 16 000 at w = 0.38 (3 100 at w = 0.5, 118 at w = 0.7); for 5-point samples
+    it reaches down to w of about 0.21 (2 800 samples at w = 0.3).  The device evaluates all of them outright, so nothing is
+    saved by stopping early; the essential filter scores ten slots per sample.
 
-    The edge cases are the reference's (gcp.py:189-198, 254-257, 275-279): an empty input gives an empty bool array, ``"none"``
-    all True, fewer than 8 points all True, an unknown method the reference's ``ValueError``; fewer than 8 inliers anywhere
-    give all True as well (cv2 returning no mask, gcp.py:270-271).  ``"essential"`` raises ``NotImplementedError``: the 5-point
-    solver stays with the reference.
+    The edge cases are the reference's (gcp.py:189-203, 254-257, 275-279): an empty input gives an empty bool array, ``"none"``
+    all True, fewer than 8 points (``"essential"``: 5) all True, an unknown method the reference's ``ValueError``; fewer than 8
+    (5) inliers anywhere give all True as well (cv2 returning no mask, gcp.py:249-250, 270-271).
 
-    ``return_model=True`` returns (mask, F, info): F (3, 3) with b^T F a = 0 for a = (x1, y1, 1), b = (x2, y2, 1), or None when
-    no model was fitted, and the info dict of ``_lib.epipolar_ransac``."""
+    ``return_model=True`` returns (mask, F, info): F (3, 3) in pixel coordinates with b^T F a = 0 for a = (x1, y1, 1),
+    b = (x2, y2, 1), or None when no model was fitted, and the info dict of ``_lib.epipolar_ransac``; for ``"essential"`` info
+    also holds ``"E"`` = K^T F K and ``chosen`` counts slots, sample * 10 + slot."""
     pts1 = np.asarray(pts1, dtype=np.float64)
     pts2 = np.asarray(pts2, dtype=np.float64)
 
@@ -156,16 +171,18 @@ def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypothese
     method_lower = method.lower()
     if method_lower == "none":
         return result(np.ones(len(pts1), dtype=bool))
-    if method_lower == "essential":
-        raise NotImplementedError("outlier_filter='essential' (cv2.findEssentialMat, the 5-point solver) stays with the reference; "
-                                  "use 'fundamental' or 'none'")
-    if method_lower != "fundamental":
+    if method_lower not in ("essential", "fundamental"):
         raise ValueError(
             f"Unknown outlier_filter '{method}'. "
             "Available: 'essential', 'fundamental', 'none'"
         )
-    if len(pts1) < 8:
+    essential = method_lower == "essential"
+    if len(pts1) < (5 if essential else 8):
         return result(np.ones(len(pts1), dtype=bool))
+    if essential and focal_length is None:
+        raise NotImplementedError("outlier_filter='essential' without a focal length: the guess 'focal length = image width' stays "
+                                  "with the reference; pass focal_length (filter_matches: params with 'fov' and 'w'), or use "
+                                  "'fundamental' or 'none'")
     if pts1.ndim != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
         raise ValueError(f"points must be two (n, 2) arrays of one length, not {pts1.shape} and {pts2.shape}")
     if not (np.isfinite(pts1).all() and np.isfinite(pts2).all()):
@@ -176,8 +193,23 @@ def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypothese
         raise ValueError("hypotheses must be at least 1")
     if not 0 <= int(refits) <= _lib.EPI_MAX_REFITS:
         raise ValueError(f"refits must be 0..{_lib.EPI_MAX_REFITS}")
-    r = _lib.epipolar_ransac(pts1, pts2, threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
-    return result(r["mask"], r["F"], r["info"])
+    if not essential:
+        r = _lib.epipolar_ransac(pts1, pts2, threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
+        return result(r["mask"], r["F"], r["info"])
+    if principal_point is None:
+        # reference gcp.py:223-229, verbatim
+        if image_size is not None:
+            principal_point = (image_size[0] / 2, image_size[1] / 2)
+        else:
+            cx = (pts1[:, 0].max() + pts1[:, 0].min()) / 2
+            cy = (pts1[:, 1].max() + pts1[:, 1].min()) / 2
+            principal_point = (cx, cy)
+    K = _lib._epi_K(focal_length, principal_point)
+    if samples is not None:
+        samples = _lib._epi_samples(samples, len(pts1), 5)
+    r = _lib.essential_ransac(pts1, pts2, K[0], K[1:], threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
+    Km = np.array([[K[0], 0.0, K[1]], [0.0, K[0], K[2]], [0.0, 0.0, 1.0]])
+    return result(r["mask"], r["F"], dict(r["info"], E=Km.T @ r["F"] @ Km))
 
 
 def _spatial_cells(pts, grid_size, image_size):
@@ -228,14 +260,27 @@ def filter_spatial(pts, grid_size, image_size, selection="first", random_state=N
 
 
 def filter_matches(pts1, pts2, image_size, outlier_filter="fundamental", threshold=10.0, spatial_thin_grid=None,
-                   spatial_thin_selection="first", spatial_thin_random_state=None, **ransac):
+                   spatial_thin_selection="first", spatial_thin_random_state=None, params=None, **ransac):
     """``image_match`` from its line 507 to 544 (reference gcp.py), given the points ``match_keypoints`` returns: the geometric
     filter, then the spatial thinning on ``pts1``, then the DataFrame ``u_org, v_org, u_sim, v_sim`` (the empty frame with those
     columns when nothing is left).  ``image_size`` is (width, height) of the photograph, or None when no thinning is asked for;
-    ``**ransac`` goes to ``filter_geometric`` (hypotheses, seed, refits, samples)."""
+    ``**ransac`` goes to ``filter_geometric`` (hypotheses, seed, refits, samples).  ``params``: the camera parameters the
+    simulated image was rendered from; ``outlier_filter="essential"`` takes its focal length and principal point from them as
+    ``image_match`` does (gcp.py:466-474): f = (w / 2) / tan(fov / 2) from ``fov`` (degrees) and ``w``, (cx, cy) from ``cx``
+    and ``cy``, else (w / 2, h / 2)."""
     pts1, pts2 = np.asarray(pts1), np.asarray(pts2)
+    focal_length = None
+    principal_point = None
+    if params is not None:
+        if "fov" in params and "w" in params:
+            focal_length = (params["w"] / 2) / math.tan(params["fov"] * math.pi / 180 / 2)
+        if "cx" in params and "cy" in params:
+            principal_point = (params["cx"], params["cy"])
+        elif "w" in params and "h" in params:
+            principal_point = (params["w"] / 2, params["h"] / 2)
     if outlier_filter != "none" and len(pts1) > 0:
-        mask = filter_geometric(pts1, pts2, method=outlier_filter, threshold=threshold, **ransac)
+        mask = filter_geometric(pts1, pts2, method=outlier_filter, threshold=threshold, focal_length=focal_length,
+                                principal_point=principal_point, image_size=image_size, **ransac)
         pts1 = pts1[mask]
         pts2 = pts2[mask]
     if spatial_thin_grid is not None and len(pts1) > 0:

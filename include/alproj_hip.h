@@ -732,6 +732,53 @@ int alp_epipolar_ransac(const double *p1, const double *p2, int64_t n, const int
                         uint64_t seed, double threshold, int refits, int splits, double F[9], uint8_t *mask,
                         int64_t info[24]);
 
+/* The same filter with outlier_filter="essential", src/alproj/gcp.py:200-252 (cv2.findEssentialMat with K): minimal samples of 5
+ * matches, the five-point solver on each (Nister's formulation with Stewenius' Gauss-Jordan step), up to 10 essential matrices a
+ * sample.  K[3] = {f, cx, cy} serves both images, as the reference builds it (gcp.py:232-236).  Every matrix is scored, chosen and
+ * reported as the pixel-space matrix F = K^-T E K^-1 at unit Frobenius norm, under the error expression above, so `threshold` is
+ * in pixels.  The order of the operations, for a numpy restatement (no fused multiply-adds):
+ *     r = 1 / f;  x' = (x - cx) * r,  y' = (y - cy) * r                       both images
+ *     a = E K^-1:     a[i][0] = r*E[i][0],  a[i][1] = r*E[i][1],  a[i][2] = E[i][2] - r*(cx*E[i][0] + cy*E[i][1])
+ *     F = K^-T a:     F[0][j] = r*a[0][j],  F[1][j] = r*a[1][j],  F[2][j] = a[2][j] - r*(cx*a[0][j] + cy*a[1][j])
+ *     F /= sqrt(sum of F[i][j]^2 in row-major order)
+ * Caps: 5 <= n <= 2^20, 1 <= H <= 2^20 / 10 (alp_epipolar_samples5: 2^20), 10 * H * n <= 2^35; f finite and > 0, cx and cy finite;
+ * otherwise ALP_EINVAL before anything is uploaded, as for the refusals above.
+ *
+ * alp_epipolar_samples5: samples[H][5], rows of 5 distinct indices drawn as alp_epipolar_samples draws its rows of 8, keyed by
+ *   (seed, hypothesis, attempt) but on a stream word of their own: the 8-wide rows of a seed do not depend on them.  A function
+ *   of (n, H, seed) alone.
+ * alp_epipolar_solve5: F[H][10][9] and nsol[H].  Per sample: the 5 x 9 epipolar matrix of the normalised points (a row is
+ *   x2'x1' x2'y1' x2' y2'x1' y2'y1' y2' x1' y1' 1); its null space by Gaussian elimination with complete pivoting (the first
+ *   largest entry in row-major order; a pivot at or below 1e-13 of the first one: rank below 5), null vector c = 0..3 having 1 at
+ *   free column 5 + c, 0 at the other three free columns and the rest by back substitution summed from the left; E = x N0 + y N1
+ *   + z N2 + N3; the ten cubics det E = 0 and 2 E E^T E - tr(E E^T) E = 0 over the monomials x^3 y^3 x^2y xy^2 x^2z x^2 y^2z
+ *   y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1; Gauss-Jordan with row pivoting on the first ten columns; the rows of x^2z, x^2,
+ *   y^2z, y^2, xyz, xy give B(z) (x, y, 1)^T = 0, and det B is a polynomial of degree 10 in z.  All its real roots are found, each
+ *   to the last bit that bisection can decide: between two neighbouring real roots of a derivative the next lower derivative is
+ *   monotone, so the roots of the k-th derivative bracket those of the (k-1)-th, from the linear one down to the polynomial
+ *   itself, inside Cauchy's bound.  A root of even multiplicity is not found.  For each root, (x, y, 1) is the cross product of two
+ *   rows of B(z) (of the three pairs the one with the largest third component), then up to three Gauss-Newton steps on the ten
+ *   cubics in (x, y, z) (a step that does not shrink the residual ends them).  A solution whose cubics, taken at E of unit
+ *   Frobenius norm, still exceed 5e-14 in Euclidean norm after the steps is dropped: the steps did not converge, and what they
+ *   left is no essential matrix.  Then F as above.  The solutions of a sample stand in ascending order of the root z that
+ *   bisection found, which means something only with respect to the null-space basis above.  The steps move z, so the
+ *   polished z need not ascend, and two neighbouring roots may be taken to the same solution, which then fills two slots.
+ *   The unused slots hold 9 NaN.  A sample of rank below 5 (a repeated point), a vanishing pivot or leading coefficient, a
+ *   non-finite coefficient of the polynomial or any non-finite F gives 90 NaN and nsol 0.  The sign of F is not fixed.
+ * alp_essential_ransac: alp_epipolar_ransac over the 10 * H slots of alp_epipolar_solve5, with these differences.  samples: NULL
+ *   = drawn as alp_epipolar_samples5 draws them, else samples[H][5].  A NaN slot counts 0; info[0] is the chosen slot h * 10 + slot,
+ *   the lowest on a tie.  The refit forms the 9 x 9 sum in the K-normalised coordinates x', y' above, so that its smallest
+ *   eigenvector is K^T F K of the pixel-space fit; that matrix is projected onto the essential matrices (singular values (s, s, 0)
+ *   with s the mean of the two largest) and taken back to pixels and to unit norm as above.  When the chosen count is below 5,
+ *   which means that no sample gave a finite matrix, every mask entry is 1 and info[5] = 1.  The other info words are those of
+ *   alp_epipolar_ransac; the launch plan is that of 10 * H hypotheses. */
+int alp_epipolar_samples5(int64_t n, int64_t H, uint64_t seed, int32_t *samples);
+int alp_epipolar_solve5(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H,
+                        const double K[3], double *F, int32_t *nsol);
+int alp_essential_ransac(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H,
+                         uint64_t seed, const double K[3], double threshold, int refits, int splits, double F[9],
+                         uint8_t *mask, int64_t info[24]);
+
 /* The spatial thinning of image_match, src/alproj/gcp.py:282-357 (_filter_spatial): mask[n] keeps one point per distinct value
  * of cell_id[n].  dist == NULL: the lowest index of each cell (selection="first").  Otherwise the lowest dist of each cell, the
  * lowest index on an equal dist (selection="center": pandas' idxmin); dist must be >= 0 and not NaN.  The table is indexed by
