@@ -4,7 +4,9 @@ There is no CPU fallback: if the shared library is missing, or no MI355X-class H
 can be initialised, the first call that needs the device raises ``AlprojHipError``.
 """
 import ctypes
+import math
 import os
+import statistics
 import threading
 import weakref
 
@@ -291,6 +293,11 @@ _SIGNATURES = {
     "alp_epipolar_solve5": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, _c_dp, _c_dp, ctypes.POINTER(ctypes.c_int32)],
     "alp_essential_ransac": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_uint64, _c_dp, _c_double, _c_int, _c_int,
                              _c_dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64)],
+    "alp_epipolar_select": [_c_dp, _c_dp, _c_i64, _c_dp, _c_i64, _c_i64, _c_int, _c_dp, ctypes.POINTER(_c_i64)],
+    "alp_epipolar_lmeds": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_uint64, _c_i64, _c_double, _c_double,
+                           _c_int, _c_int, _c_dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64), _c_dp],
+    "alp_essential_lmeds": [_c_dp, _c_dp, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_uint64, _c_dp, _c_i64, _c_double,
+                            _c_double, _c_int, _c_int, _c_dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_c_i64), _c_dp],
     "alp_grid_thin": [ctypes.POINTER(_c_i64), _c_dp, _c_i64, ctypes.POINTER(ctypes.c_uint8)],
     "alp_rasterize_points": [_c_dp, _c_dp, _c_dp, _c_i64, _c_i64, _c_double, _c_double, _c_double, _c_i64, _c_i64,
                              _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_uint8)],
@@ -1294,6 +1301,86 @@ def essential_ransac(p1, p2, focal_length, principal_point, threshold, hypothese
                                      hypotheses, int(seed) & (2 ** 64 - 1), as_dp(K), float(threshold), int(refits), int(splits), as_dp(F),
                                      mask.ctypes.data_as(_c_u8p), info))
     return {"F": F, "mask": mask.astype(bool), "info": _epi_ransac_info(info)}
+
+
+EPI_SELECT_PASSES = 16
+EPI_SELECT_INFO = EPI_SCORE_INFO + ("passes", "hist_bytes")
+
+
+def lmeds_rank(n, m, quantile=0.5):
+    """The 1-based rank of the order statistic that is a hypothesis' value: min(n, max(m + 1, ceil(quantile * n))), m the size of
+    a minimal sample.  Below n = 2 (m + 1) that is m + 1 whatever the quantile (up to 0.5): a minimal sample fits its own m
+    matches exactly, so a lower rank would be met by every hypothesis."""
+    return int(min(n, max(m + 1, math.ceil(quantile * n))))
+
+
+def lmeds_scale2(n, m, quantile=0.5):
+    """The square of 2.5 * (1 / Phi^-1((1 + quantile) / 2)) * (1 + 5 / (n - m)): Rousseeuw and Leroy's robust standard
+    deviation from the chosen quantile of the squared errors (the constant is 1.4826 at the median), times 2.5.  n > m;
+    quantile = 1 has no finite constant and gives 0.0: the bound is then the floor."""
+    if quantile >= 1.0:
+        return 0.0
+    scale = 2.5 * (1.0 / statistics.NormalDist().inv_cdf((1.0 + quantile) / 2.0)) * (1.0 + 5.0 / (n - m))
+    return scale * scale
+
+
+def epipolar_select(p1, p2, F, rank, splits=0):
+    """alp_epipolar_select: (value (H,) float64, info: the launch plan, EPI_SELECT_INFO): the ``rank``-th smallest error (1-based) of
+    every one of the (H, 3, 3) matrices ``F`` over all matches, a NaN error counting as +inf."""
+    p1, p2 = _epi_points(p1, p2)
+    F = np.ascontiguousarray(F, dtype=np.float64).reshape(-1, 9)
+    value = np.empty(len(F), dtype=np.float64)
+    info = (_c_i64 * 8)()
+    check(lib().alp_epipolar_select(as_dp(p1), as_dp(p2), len(p1), as_dp(F), len(F), int(rank), int(splits), as_dp(value), info))
+    return value, dict(zip(EPI_SELECT_INFO, (int(v) for v in info)))
+
+
+def _epi_lmeds_result(F, mask, info, stats):
+    v = [int(x) for x in info]
+    s = [float(x) for x in stats]
+    d = _epi_ransac_info(info)
+    d.update(passes=v[20], passes_single=v[21], match_tiles=v[22], hist_bytes=v[23])
+    return {"F": F, "mask": mask.astype(bool), "info": d, "value": s[0], "final_value": s[1],
+            "bound": float("nan") if d["keep_all"] else math.sqrt(s[2]), "refit_values": s[3:3 + d["refits_run"]]}
+
+
+def epipolar_lmeds(p1, p2, rank, scale2, floor2=1.0, hypotheses=16384, seed=0, refits=4, samples=None, splits=0):
+    """alp_epipolar_lmeds: the least-median-of-squares filter in one device loop -> dict F (3, 3), mask (n,) bool, info (as for
+    epipolar_ransac, the counts taken at each matrix' own bound, plus passes, passes_single, match_tiles, hist_bytes), value (of
+    the chosen hypothesis), final_value, bound (pixels: the square root of the final b2; NaN when every match was kept) and
+    refit_values (of every refit run, the rejected last one included)."""
+    p1, p2 = _epi_points(p1, p2)
+    if samples is not None:
+        samples = _epi_samples(samples, len(p1))
+        hypotheses = len(samples)
+    hypotheses = int(hypotheses)
+    F = np.empty((3, 3), dtype=np.float64)
+    mask = np.empty(len(p1), dtype=np.uint8)
+    info = (_c_i64 * 24)()
+    stats = (_c_double * 12)()
+    check(lib().alp_epipolar_lmeds(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
+                                   hypotheses, int(seed) & (2 ** 64 - 1), int(rank), float(scale2), float(floor2), int(refits),
+                                   int(splits), as_dp(F), mask.ctypes.data_as(_c_u8p), info, stats))
+    return _epi_lmeds_result(F, mask, info, stats)
+
+
+def essential_lmeds(p1, p2, focal_length, principal_point, rank, scale2, floor2=1.0, hypotheses=16384, seed=0, refits=4, samples=None,
+                    splits=0):
+    """alp_essential_lmeds: epipolar_lmeds over the ten slots of every five-point sample; ``chosen`` is sample * 10 + slot."""
+    p1, p2 = _epi_points(p1, p2)
+    K = _epi_K(focal_length, principal_point)
+    if samples is not None:
+        samples = _epi_samples(samples, len(p1), 5)
+        hypotheses = len(samples)
+    hypotheses = int(hypotheses)
+    F = np.empty((3, 3), dtype=np.float64)
+    mask = np.empty(len(p1), dtype=np.uint8)
+    info = (_c_i64 * 24)()
+    stats = (_c_double * 12)()
+    check(lib().alp_essential_lmeds(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
+                                    hypotheses, int(seed) & (2 ** 64 - 1), as_dp(K), int(rank), float(scale2), float(floor2),
+                                    int(refits), int(splits), as_dp(F), mask.ctypes.data_as(_c_u8p), info, stats))
+    return _epi_lmeds_result(F, mask, info, stats)
 
 
 def grid_thin(cell_id, dist=None):

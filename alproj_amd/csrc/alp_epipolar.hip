@@ -31,6 +31,17 @@
 //                         the count of the candidate, and the decision.  All of them read `stopped` from the state record and return
 //                         at once when it is set: the host enqueues `refits` rounds and never looks.
 //   epi_mask_kernel       mask and error of every match under one F
+//   epi_select_kernel, epi_select_merge_kernel
+//                         the LMedS filter: the rank-th smallest error of every hypothesis, exactly, without an H x n array: a
+//                         radix select on the 64 bits of the error, the most significant 4-bit digit first, 16 passes.  The
+//                         layout is the score kernel's; in every pass a lane forms its errors again and, for each one whose
+//                         higher digits equal the prefix found so far, bumps one of 16 counters in LDS (counter d of lane l at
+//                         d * 256 + l: a lane's own column, no bank conflict).  The merge adds the splits' counters in order
+//                         (integers), finds the digit at which they reach the remaining rank and extends the prefix.
+//   epi_lmeds_choose_kernel, epi_errs_kernel, epi_lmeds_eval_kernel
+//                         the smallest value, the lowest index on a tie; the errors of one F (the chosen one, a refit's candidate)
+//                         as an array; and one workgroup that selects the value of that array (8-bit digits, integer LDS
+//                         atomics, 8 passes), forms the bound, counts the inliers and decides like epi_decide_kernel
 //   thin_*_kernel         alp_grid_thin: atomic minima on (distance bits) and then on the index, per cell
 #include "alp_sampler.h"
 
@@ -49,6 +60,12 @@ struct EpiState {
     long long info[EPI_INFO];
     int count, stopped, keep_all;
     int essential;                // T is K twice over (cx, cy, 1 / f) and a fitted matrix is projected onto the essential ones
+    // the LMedS filter (alp_epipolar_lmeds / alp_essential_lmeds): a match is an inlier iff e <= bound2, which the value of the
+    // current F sets, and `count` is the number of inliers at that bound
+    int lmeds, rank;              // rank: 1-based, the order statistic that is a hypothesis' value
+    double scale2, floor2;        // bound2 = max(scale2 * value, floor2)
+    double value, bound2;         // of Fcur
+    double stats[EPI_LMEDS_STATS];
 };
 static_assert(sizeof(EpiState) <= EPI_STATE_BYTES, "the state record outgrew its slot");
 
@@ -824,6 +841,7 @@ __global__ __launch_bounds__(EPI_REDUCE_BLOCK) void epi_accum_kernel(const doubl
                                                                      const EpiState *__restrict__ st, double *__restrict__ sym) {
     __shared__ double red[4 * EPI_SYM];
     if (st->stopped) return;
+    if (st->lmeds) t2 = st->bound2;
     double f[9], T[6], acc[EPI_SYM];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = st->Fcur[k];
@@ -957,18 +975,224 @@ __global__ void epi_decide_kernel(const int *__restrict__ cpart, int blocks, int
     }
 }
 
-// F: 9 doubles on the device; keep_all: NULL, or a flag on the device that turns every mask entry into 1
+// F: 9 doubles on the device; keep_all: NULL, or a flag on the device that turns every mask entry into 1; bound2: NULL, or the
+// squared bound on the device that replaces t2 (the LMedS filter)
 __global__ __launch_bounds__(256) void epi_mask_kernel(const double4 *__restrict__ pts, int n, const double *__restrict__ F, double t2,
-                                                       const int *__restrict__ keep_all, unsigned char *__restrict__ mask,
-                                                       double *__restrict__ err) {
+                                                       const int *__restrict__ keep_all, const double *__restrict__ bound2,
+                                                       unsigned char *__restrict__ mask, double *__restrict__ err) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (bound2) t2 = *bound2;
     double f[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = F[k];
     const double e = epi_error(f, pts[i]);
     err[i] = e;
     mask[i] = (e <= t2 || (keep_all && *keep_all)) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ the LMedS filter
+// An error is a non-negative double or +inf once a NaN counts as +inf, so errors order as their bit patterns do as unsigned
+// integers: the key of an error.
+constexpr u64 EPI_KEY_INF = 0x7ff0000000000000ull;
+enum { I_PASSES = 20, I_PASSES1, I_MATCH_TILES, I_HIST_BYTES };               // info words of alp_epipolar_lmeds past the refit counts
+enum { S_CHOSEN_VALUE = 0, S_FINAL_VALUE, S_BOUND2, S_REFIT_VALUE0 };         // stats words
+static_assert(I_HIST_BYTES < EPI_INFO && S_REFIT_VALUE0 + EPI_MAX_REFITS <= EPI_LMEDS_STATS, "info or stats too short");
+
+__device__ __forceinline__ u64 epi_key_of(double e) { return e != e ? EPI_KEY_INF : (u64)__double_as_longlong(e); }
+
+// the key of e with one division, as epi_inlier forms e: s2 / min(a, b) = max(s2 / a, s2 / b) bit for bit.  Where the two
+// differ, one is NaN and the other +inf (s2 = inf over one infinite divisor), which is one key.
+__device__ __forceinline__ u64 epi_key(const double (&F)[9], const double4 q) {
+    double ss, d2, d1;
+    epi_terms(F, q.x, q.y, q.z, q.w, ss, d2, d1);
+    double dm = d1 < d2 ? d1 : d2;
+    if (d1 != d1) dm = d1;
+    return epi_key_of(ss / dm);
+}
+
+// One pass: `shift` is the place of the pass' digit (60 in the first pass, 0 in the last).  prefix[h]: the digits above it
+// (not read in the first pass); hist: the counters of this split, [16][h_pad] from its base.
+__global__ __launch_bounds__(EPI_HYP_TILE) void epi_select_kernel(const double4 *__restrict__ pts, int n, const double *__restrict__ F, int H,
+                                                                  int splits, long long match_tiles, long long h_pad,
+                                                                  const u64 *__restrict__ prefix, int shift, unsigned *__restrict__ hist) {
+    __shared__ double4 tile[EPI_MATCH_TILE];
+    __shared__ unsigned cnt[EPI_SELECT_DIGITS * EPI_HYP_TILE];
+    const long long htile = blockIdx.x / (unsigned)splits;
+    const int split = (int)(blockIdx.x % (unsigned)splits);
+    const long long h = htile * EPI_HYP_TILE + threadIdx.x;
+    double f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = h < H ? F[(size_t)h * 9 + k] : nan64();
+    const bool first = shift == 64 - EPI_SELECT_BITS;
+    const u64 pre = first ? 0 : prefix[h];
+    const u64 above = first ? 0 : ~(u64)0 << (shift + EPI_SELECT_BITS);
+    unsigned *const mine = cnt + threadIdx.x;         // counter d at mine[d * 256]: no other lane touches it
+#pragma unroll
+    for (int d = 0; d < EPI_SELECT_DIGITS; ++d) mine[d * EPI_HYP_TILE] = 0;
+    int64_t tb, te;
+    match_split_range(match_tiles, splits, split, &tb, &te);
+    for (long long t = tb; t < te; ++t) {
+        const int base = (int)(t * EPI_MATCH_TILE);
+        const int count = n - base < EPI_MATCH_TILE ? n - base : EPI_MATCH_TILE;
+        __syncthreads();
+        for (int i = threadIdx.x; i < count; i += EPI_HYP_TILE) tile[i] = pts[base + i];
+        __syncthreads();
+#pragma unroll 4
+        for (int m = 0; m < count; ++m) {
+            const u64 k = epi_key(f, tile[m]);
+            if (((k ^ pre) & above) == 0) atomicAdd(mine + (int)((k >> shift) & (EPI_SELECT_DIGITS - 1)) * EPI_HYP_TILE, 1u);
+        }
+    }
+    unsigned *const out = hist + (size_t)split * EPI_SELECT_DIGITS * h_pad + h;
+#pragma unroll
+    for (int d = 0; d < EPI_SELECT_DIGITS; ++d) out[(size_t)d * h_pad] = mine[d * EPI_HYP_TILE];
+}
+
+// a thread per padded hypothesis: the counters of the splits added in order, the digit at which they reach the remaining rank,
+// the prefix extended by it and the rank reduced by what lies below it; after the last pass the prefix is the value
+__global__ __launch_bounds__(256) void epi_select_merge_kernel(const unsigned *__restrict__ hist, int splits, long long h_pad, int H, int shift,
+                                                               int rank0, u64 *__restrict__ prefix, int *__restrict__ rank,
+                                                               double *__restrict__ value) {
+    const long long h = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (h >= h_pad) return;
+    const bool first = shift == 64 - EPI_SELECT_BITS;
+    const unsigned r = (unsigned)(first ? rank0 : rank[h]);
+    unsigned below = 0;
+    int digit = EPI_SELECT_DIGITS - 1;
+    for (int d = 0; d < EPI_SELECT_DIGITS; ++d) {
+        unsigned c = 0;
+        for (int s = 0; s < splits; ++s) c += hist[((size_t)s * EPI_SELECT_DIGITS + d) * h_pad + h];
+        if (below + c >= r) {
+            digit = d;
+            break;
+        }
+        below += c;
+    }
+    const u64 p = (first ? 0 : prefix[h]) | (u64)digit << shift;
+    prefix[h] = p;
+    rank[h] = (int)(r - below);
+    if (shift == 0 && h < H) value[h] = __longlong_as_double((long long)p);
+}
+
+// one workgroup: the smallest value, the lowest index on a tie (value and index do not pack into one 64-bit key: a
+// lexicographic compare); the state of the filter from it
+__global__ __launch_bounds__(256) void epi_lmeds_choose_kernel(const double *__restrict__ value, int H, const double *__restrict__ F, int rank,
+                                                               double scale2, double floor2, EpiState *__restrict__ st) {
+    __shared__ u64 bkey[256];
+    __shared__ int bidx[256];
+    u64 key = ~(u64)0;
+    int idx = INT_MAX;
+    for (int h = threadIdx.x; h < H; h += 256) {          // ascending h: a strict compare keeps the lowest index
+        const u64 k = (u64)__double_as_longlong(value[h]);
+        if (k < key) key = k, idx = h;
+    }
+    bkey[threadIdx.x] = key, bidx[threadIdx.x] = idx;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int t = 1; t < 256; ++t)
+        if (bkey[t] < key || (bkey[t] == key && bidx[t] < idx)) key = bkey[t], idx = bidx[t];
+    const double v = __longlong_as_double((long long)key);
+    for (int k = 0; k < 9; ++k) st->Fcur[k] = F[(size_t)idx * 9 + k], st->Fcand[k] = nan64();
+    for (int k = 0; k < EPI_INFO; ++k) st->info[k] = 0;
+    for (int k = 0; k < EPI_MAX_REFITS; ++k) st->info[I_REFIT_COUNT0 + k] = -1;
+    for (int k = 0; k < EPI_LMEDS_STATS; ++k) st->stats[k] = nan64();
+    st->lmeds = 1, st->rank = rank, st->scale2 = scale2, st->floor2 = floor2;
+    st->count = 0;
+    st->keep_all = st->stopped = key < EPI_KEY_INF ? 0 : 1;
+    const double sv = scale2 * v;
+    st->value = v, st->bound2 = sv > floor2 ? sv : floor2;
+    st->stats[S_CHOSEN_VALUE] = st->stats[S_FINAL_VALUE] = v, st->stats[S_BOUND2] = st->bound2;
+    st->info[I_CHOSEN] = idx, st->info[I_KEEP_ALL] = st->keep_all;
+}
+
+// the keys of the errors of every match under the current F (candidate == 0) or the refit's candidate, with the mask
+// kernel's arithmetic
+__global__ __launch_bounds__(256) void epi_errs_kernel(const double4 *__restrict__ pts, int n, const EpiState *__restrict__ st, int candidate,
+                                                       u64 *__restrict__ keys) {
+    if (st->stopped) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = candidate ? st->Fcand[k] : st->Fcur[k];
+    keys[i] = epi_key_of(epi_error(f, pts[i]));
+}
+
+// One workgroup over the keys of one F.  round < 0: the chosen hypothesis, whose value is known: the count of its inliers.
+// Otherwise the candidate of refit `round`: its value by a radix select on the array (8-bit digits, integer LDS atomics: the
+// counts do not depend on their order), its bound, its count, and the decision: it replaces the current F only when its value is
+// strictly smaller, otherwise the loop stops.  A value that is not finite counts no inliers.
+__global__ __launch_bounds__(EPI_SELECT1_BLOCK) void epi_lmeds_eval_kernel(const u64 *__restrict__ keys, int n, int round, EpiState *__restrict__ st) {
+    __shared__ unsigned hist[256];
+    __shared__ u64 s_prefix;
+    __shared__ unsigned s_rank;
+    __shared__ int red[EPI_SELECT1_BLOCK / 64];
+    if (st->stopped) return;
+    u64 vkey = (u64)__double_as_longlong(st->value);
+    if (round >= 0) {
+        u64 pre = 0;
+        unsigned r = (unsigned)st->rank;
+        for (int pass = 0; pass < EPI_SELECT1_PASSES; ++pass) {
+            const int shift = 56 - 8 * pass;
+            const u64 above = pass == 0 ? 0 : ~(u64)0 << (shift + 8);
+            __syncthreads();
+            if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+            __syncthreads();
+            for (int i = threadIdx.x; i < n; i += EPI_SELECT1_BLOCK) {
+                const u64 k = keys[i];
+                if (((k ^ pre) & above) == 0) atomicAdd(hist + (int)((k >> shift) & 255), 1u);
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                unsigned below = 0;
+                int digit = 255;
+                for (int d = 0; d < 256; ++d) {
+                    if (below + hist[d] >= r) {
+                        digit = d;
+                        break;
+                    }
+                    below += hist[d];
+                }
+                s_prefix = pre | (u64)digit << shift, s_rank = r - below;
+            }
+            __syncthreads();
+            pre = s_prefix, r = s_rank;
+        }
+        vkey = pre;
+    }
+    const bool finite = vkey < EPI_KEY_INF;
+    const double v = __longlong_as_double((long long)vkey);
+    const double sv = st->scale2 * v, floor2 = st->floor2;
+    const double b2 = sv > floor2 ? sv : floor2;
+    const u64 bkey = (u64)__double_as_longlong(b2);           // b2 >= 0: e <= b2 is key <= its key (a NaN e has the key of +inf, and b2 is below it whenever v is finite and scale2 * v does not overflow)
+    int c = 0;
+    if (finite)
+        for (int i = threadIdx.x; i < n; i += EPI_SELECT1_BLOCK) c += (keys[i] <= bkey && keys[i] < EPI_KEY_INF) ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    c = 0;
+    for (int w = 0; w < EPI_SELECT1_BLOCK / 64; ++w) c += red[w];
+    if (round < 0) {
+        st->count = c;
+        st->info[I_CHOSEN_COUNT] = st->info[I_FINAL_COUNT] = c;
+        return;
+    }
+    st->info[I_REFIT_COUNT0 + round] = c;
+    st->info[I_REFITS_RUN] = round + 1;
+    st->stats[S_REFIT_VALUE0 + round] = v;
+    if (v < st->value) {
+        for (int k = 0; k < 9; ++k) st->Fcur[k] = st->Fcand[k];
+        st->count = c, st->value = v, st->bound2 = b2;
+        st->info[I_FINAL_COUNT] = c;
+        st->info[I_REFITS_KEPT] += 1;
+        st->stats[S_FINAL_VALUE] = v, st->stats[S_BOUND2] = b2;
+    } else {
+        st->stopped = 1;
+    }
 }
 
 // ------------------------------------------------------------------ alp_grid_thin
@@ -1008,8 +1232,14 @@ struct EpiCall {
     unsigned char *mask() const { return (unsigned char *)(d + p.off_mask); }
     double *err() const { return (double *)(d + p.off_err); }
 
-    int reserve(int64_t n, int64_t H, int splits) {
-        p = host::epi_plan(n, H, splits, ctx().cu_count);
+    unsigned *hist() const { return (unsigned *)(d + p.off_hist); }
+    u64 *prefix() const { return (u64 *)(d + p.off_prefix); }
+    int *rank() const { return (int *)(d + p.off_rank); }
+    double *value() const { return (double *)(d + p.off_value); }
+
+    // with_select: the plan of the LMedS filter, which has the select's arrays after all the others
+    int reserve(int64_t n, int64_t H, int splits, bool with_select = false) {
+        p = with_select ? host::epi_select_plan(n, H, splits, ctx().cu_count) : host::epi_plan(n, H, splits, ctx().cu_count);
         if (int rc = dev.reserve(p.scratch_bytes)) return rc;
         d = dev;
         return ALP_OK;
@@ -1052,6 +1282,16 @@ struct EpiCall {
                            (const double *)F(), (int)H, t2, p.splits, (long long)p.match_tiles, (long long)p.h_pad, partial());
         hipLaunchKernelGGL(epi_merge_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx().stream, (const int *)partial(), p.splits,
                            (long long)p.h_pad, (int)H, counts());
+    }
+    // value()[h] = the rank-th smallest error of hypothesis h: the passes of the select, each followed by its merge
+    void launch_select(int64_t n, int64_t H, int rank) {
+        for (int pass = 0; pass < p.passes; ++pass) {
+            const int shift = 64 - EPI_SELECT_BITS * (pass + 1);
+            hipLaunchKernelGGL(epi_select_kernel, dim3((unsigned)p.workgroups), dim3(EPI_HYP_TILE), 0, ctx().stream, (const double4 *)pts(), (int)n,
+                               (const double *)F(), (int)H, p.splits, (long long)p.match_tiles, (long long)p.h_pad, (const u64 *)prefix(), shift, hist());
+            hipLaunchKernelGGL(epi_select_merge_kernel, dim3((unsigned)(p.h_pad / 256)), dim3(256), 0, ctx().stream, (const unsigned *)hist(), p.splits,
+                               (long long)p.h_pad, (int)H, shift, rank, prefix(), this->rank(), value());
+        }
     }
 };
 
@@ -1175,7 +1415,7 @@ extern "C" int alp_epipolar_mask(const double *p1, const double *p2, int64_t n, 
     if (e == hipSuccess) {
         KTimeScope kt;
         hipLaunchKernelGGL(epi_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double4 *)c.pts(), (int)n,
-                           (const double *)c.F(), threshold * threshold, (const int *)nullptr, c.mask(), c.err());
+                           (const double *)c.F(), threshold * threshold, (const int *)nullptr, (const double *)nullptr, c.mask(), c.err());
         e = hipGetLastError();
     }
     if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, c.mask(), (size_t)n, hipMemcpyDeviceToHost, st);
@@ -1228,7 +1468,7 @@ int epi_ransac(const char *fn, const double *p1, const double *p2, int64_t n, co
             hipLaunchKernelGGL(epi_decide_kernel, dim3(1), dim3(64), 0, st, (const int *)c.cpart(), (int)rb, r, state);
         }
         hipLaunchKernelGGL(epi_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pts, (int)n, (const double *)state->Fcur, t2,
-                           (const int *)&state->keep_all, c.mask(), c.err());
+                           (const int *)&state->keep_all, (const double *)nullptr, c.mask(), c.err());
         e = hipGetLastError();
     }
     if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, c.mask(), (size_t)n, hipMemcpyDeviceToHost, st);
@@ -1254,6 +1494,123 @@ extern "C" int alp_essential_ransac(const double *p1, const double *p2, int64_t 
                                     const double K[3], double threshold, int refits, int splits, double F[9], uint8_t *mask, int64_t info[24]) {
     if (!K) return fail(ALP_EINVAL, "%s: NULL K", __func__);
     return epi_ransac(__func__, p1, p2, n, samples, H, seed, K, threshold, refits, splits, F, mask, info);
+}
+
+namespace {
+
+// what the select adds to epi_check_points: the work of its passes, and the rank
+int epi_check_select(const char *fn, int64_t n, int64_t H, int slots, int64_t rank) {
+    if (!host::epi_select_caps_ok(n, H * slots, slots == 1 ? EPI_MIN_N : EPI_SAMPLE5))
+        return fail(ALP_EINVAL, "%s: %d passes * H * n = %d * %lld * %lld pass 2^35 error evaluations", fn, EPI_SELECT_PASSES, EPI_SELECT_PASSES,
+                    (long long)(H * slots), (long long)n);
+    if (rank < 1 || rank > n) return fail(ALP_EINVAL, "%s: rank = %lld, must be 1..n = %lld", fn, (long long)rank, (long long)n);
+    return ALP_OK;
+}
+
+// the LMedS filter: K == NULL the fundamental one, else the essential one
+int epi_lmeds(const char *fn, const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, uint64_t seed, const double *K,
+              int64_t rank, double scale2, double floor2, int refits, int splits, double F[9], uint8_t *mask, int64_t info[24], double stats[12]) {
+    if (int rc = require_init()) return rc;
+    const int slots = K ? EPI_SLOTS5 : 1, width = K ? EPI_SAMPLE5 : EPI_SAMPLE;
+    if (int rc = epi_check_points(fn, p1, p2, n, H, slots)) return rc;
+    if (int rc = epi_check_select(fn, n, H, slots, rank)) return rc;
+    if (K)
+        if (int rc = epi_check_K(fn, K)) return rc;
+    if (!(std::isfinite(scale2) && scale2 >= 0.0)) return fail(ALP_EINVAL, "%s: scale2 must be finite and not negative", fn);
+    if (!(std::isfinite(floor2) && floor2 >= 0.0)) return fail(ALP_EINVAL, "%s: floor2 must be finite and not negative", fn);
+    if (!(refits >= 0 && refits <= EPI_MAX_REFITS)) return fail(ALP_EINVAL, "%s: refits must be 0..8", fn);
+    if (int rc = epi_check_splits(fn, splits, n)) return rc;
+    if (samples)
+        if (int rc = epi_check_samples(fn, samples, H, n, width)) return rc;
+    const int64_t HS = H * slots;
+    EpiCall c;
+    if (int rc = c.reserve(n, HS, splits, true)) return rc;
+    hipStream_t st = ctx().stream;
+    EpiState host_state;
+    hipError_t e = c.upload(p1, p2, n, !K);
+    if (e == hipSuccess && samples) e = hipMemcpyAsync(c.samples(), samples, (size_t)H * width * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        // enqueued at once, like epi_ransac: what a round does is decided on the device
+        KTimeScope kt;
+        const double4 *pts = c.pts();
+        EpiState *state = c.state();
+        u64 *keys = (u64 *)c.err();
+        const unsigned rb = (unsigned)c.p.reduce_blocks, nb = (unsigned)((n + 255) / 256);
+        if (K) {
+            if (!samples) c.launch_samples5(n, H, seed);
+            c.launch_solve5(H, K);
+        } else {
+            if (!samples) c.launch_samples(n, H, seed);
+            c.launch_solve(H);
+        }
+        c.launch_select(n, HS, (int)rank);
+        hipLaunchKernelGGL(epi_lmeds_choose_kernel, dim3(1), dim3(256), 0, st, (const double *)c.value(), (int)HS, (const double *)c.F(), (int)rank,
+                           scale2, floor2, state);
+        hipLaunchKernelGGL(epi_errs_kernel, dim3(nb), dim3(256), 0, st, pts, (int)n, (const EpiState *)state, 0, keys);
+        hipLaunchKernelGGL(epi_lmeds_eval_kernel, dim3(1), dim3(EPI_SELECT1_BLOCK), 0, st, (const u64 *)keys, (int)n, -1, state);
+        for (int r = 0; r < refits; ++r) {
+            hipLaunchKernelGGL(epi_accum_kernel, dim3(rb), dim3(EPI_REDUCE_BLOCK), 0, st, pts, (int)n, 0.0, (const EpiState *)state, c.sym());
+            hipLaunchKernelGGL(epi_refit_kernel, dim3(1), dim3(64), 0, st, (const double *)c.sym(), (int)rb, state);
+            hipLaunchKernelGGL(epi_errs_kernel, dim3(nb), dim3(256), 0, st, pts, (int)n, (const EpiState *)state, 1, keys);
+            hipLaunchKernelGGL(epi_lmeds_eval_kernel, dim3(1), dim3(EPI_SELECT1_BLOCK), 0, st, (const u64 *)keys, (int)n, r, state);
+        }
+        hipLaunchKernelGGL(epi_mask_kernel, dim3(nb), dim3(256), 0, st, pts, (int)n, (const double *)state->Fcur, 0.0, (const int *)&state->keep_all,
+                           (const double *)&state->bound2, c.mask(), c.err());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, c.mask(), (size_t)n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&host_state, c.state(), sizeof(EpiState), hipMemcpyDeviceToHost, st);
+    if (int rc = epi_finish(fn, e)) return rc;
+    if (F) memcpy(F, host_state.Fcur, 72);
+    if (info) {
+        for (int k = 0; k < EPI_INFO; ++k) info[k] = host_state.info[k];
+        info[I_HYP_TILE] = c.p.hyp_tile, info[I_MATCH_TILE] = c.p.match_tile, info[I_SPLITS] = c.p.splits, info[I_WORKGROUPS] = c.p.workgroups;
+        info[I_BYTES] = (int64_t)c.p.scratch_bytes, info[I_REDUCE_BLOCKS] = c.p.reduce_blocks;
+        info[I_PASSES] = c.p.passes, info[I_PASSES1] = EPI_SELECT1_PASSES, info[I_MATCH_TILES] = c.p.match_tiles;
+        info[I_HIST_BYTES] = (int64_t)c.p.hist_bytes;
+    }
+    if (stats) memcpy(stats, host_state.stats, sizeof(host_state.stats));
+    return ALP_OK;
+}
+
+}  // namespace
+
+extern "C" int alp_epipolar_select(const double *p1, const double *p2, int64_t n, const double *F, int64_t H, int64_t rank, int splits,
+                                   double *value, int64_t info[8]) {
+    if (int rc = require_init()) return rc;
+    if (int rc = epi_check_points(__func__, p1, p2, n, H)) return rc;
+    if (int rc = epi_check_select(__func__, n, H, 1, rank)) return rc;
+    ALP_REQUIRE(F && value, "NULL F or output");
+    if (int rc = epi_check_splits(__func__, splits, n)) return rc;
+    EpiCall c;
+    if (int rc = c.reserve(n, H, splits, true)) return rc;
+    if (info) {
+        info[0] = c.p.hyp_tile, info[1] = c.p.match_tile, info[2] = c.p.splits, info[3] = c.p.workgroups;
+        info[4] = (int64_t)c.p.scratch_bytes, info[5] = c.p.match_tiles, info[6] = c.p.passes, info[7] = (int64_t)c.p.hist_bytes;
+    }
+    hipStream_t st = ctx().stream;
+    hipError_t e = c.upload(p1, p2, n, false);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.F(), F, (size_t)H * 72, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        KTimeScope kt;
+        c.launch_select(n, H, (int)rank);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(value, c.value(), (size_t)H * 8, hipMemcpyDeviceToHost, st);
+    return epi_finish(__func__, e);
+}
+
+extern "C" int alp_epipolar_lmeds(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, uint64_t seed, int64_t rank,
+                                  double scale2, double floor2, int refits, int splits, double F[9], uint8_t *mask, int64_t info[24],
+                                  double stats[12]) {
+    return epi_lmeds(__func__, p1, p2, n, samples, H, seed, nullptr, rank, scale2, floor2, refits, splits, F, mask, info, stats);
+}
+
+extern "C" int alp_essential_lmeds(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, uint64_t seed,
+                                   const double K[3], int64_t rank, double scale2, double floor2, int refits, int splits, double F[9],
+                                   uint8_t *mask, int64_t info[24], double stats[12]) {
+    if (!K) return fail(ALP_EINVAL, "%s: NULL K", __func__);
+    return epi_lmeds(__func__, p1, p2, n, samples, H, seed, K, rank, scale2, floor2, refits, splits, F, mask, info, stats);
 }
 
 extern "C" int alp_epipolar_samples5(int64_t n, int64_t H, uint64_t seed, int32_t *samples) {

@@ -26,6 +26,11 @@ constexpr int64_t EPI_MIN_N = 8, EPI_MAX_N = (int64_t)1 << 20, EPI_MAX_H = (int6
 // H * n error evaluations of one call: a count is at most n <= 2^20 and fits int32 whatever H; 2^35 evaluations are a fraction
 // of a second of the score kernel
 constexpr int64_t EPI_MAX_WORK = (int64_t)1 << 35;
+// the LMedS filter's select over the hypotheses: a radix select on the 64 bits of an error, 4 bits a pass
+constexpr int EPI_SELECT_BITS = 4, EPI_SELECT_DIGITS = 1 << EPI_SELECT_BITS, EPI_SELECT_PASSES = 64 / EPI_SELECT_BITS;
+constexpr int EPI_SELECT1_BLOCK = 1024;        // threads of the one workgroup that selects over the error array of one F,
+constexpr int EPI_SELECT1_PASSES = 8;          // 8 bits a pass
+constexpr int EPI_LMEDS_STATS = 12;            // doubles of alp_epipolar_lmeds' stats
 constexpr int64_t THIN_MAX_N = (int64_t)1 << 30;
 constexpr int64_t THIN_MAX_SPAN = (int64_t)1 << 26;      // cells of alp_grid_thin's table
 
@@ -42,6 +47,9 @@ struct EpiPlan {
     // byte offsets in the call's device block (each a multiple of 256) and its size
     size_t off_raw1 = 0, off_raw2 = 0, off_pts = 0, off_samples = 0, off_F = 0, off_partial = 0, off_counts = 0, off_state = 0,
            off_sym = 0, off_cpart = 0, off_mask = 0, off_err = 0, scratch_bytes = 0;
+    // epi_select_plan alone: the passes of the select over the hypotheses and its arrays, after all of the above
+    int passes = 0;
+    size_t hist_bytes = 0, off_hist = 0, off_prefix = 0, off_rank = 0, off_value = 0;
 };
 
 // n in [8, 2^20] (min_n = 5: the essential filter), H in [1, 2^20], H * n <= 2^35: what every entry point of the unit requires
@@ -86,6 +94,32 @@ inline EpiPlan epi_plan(int64_t n, int64_t H, int forced, int cu_count) {
     p.off_cpart = take((size_t)p.reduce_blocks * 4);
     p.off_mask = take((size_t)n);
     p.off_err = take((size_t)n * 8);
+    p.scratch_bytes = at;
+    return p;
+}
+
+// passes * H * n <= 2^35 on top of epi_caps_ok: every pass of the select forms every error again
+inline bool epi_select_caps_ok(int64_t n, int64_t H, int64_t min_n = EPI_MIN_N) {
+    return epi_caps_ok(n, H, min_n) && H <= EPI_MAX_WORK / EPI_SELECT_PASSES / n;
+}
+
+// epi_plan with the arrays of the LMedS select appended: every offset of epi_plan stays what it is.  The partial histograms are
+// [splits][16][h_pad] counters, counter d of hypothesis h in split s at (s * 16 + d) * h_pad + h; prefix and rank have a word per
+// padded hypothesis (the lanes past H run on all-NaN matrices), value one per hypothesis.
+inline EpiPlan epi_select_plan(int64_t n, int64_t H, int forced, int cu_count) {
+    EpiPlan p = epi_plan(n, H, forced, cu_count);
+    size_t at = p.scratch_bytes;
+    auto take = [&at](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) / 256 * 256;
+        return o;
+    };
+    p.passes = EPI_SELECT_PASSES;
+    p.hist_bytes = (size_t)p.splits * EPI_SELECT_DIGITS * p.h_pad * 4;
+    p.off_hist = take(p.hist_bytes);
+    p.off_prefix = take((size_t)p.h_pad * 8);
+    p.off_rank = take((size_t)p.h_pad * 4);
+    p.off_value = take((size_t)H * 8);
     p.scratch_bytes = at;
     return p;
 }

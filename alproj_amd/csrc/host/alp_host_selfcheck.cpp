@@ -711,8 +711,31 @@ void check_epi_plan() {
                     CHECK(off[0] == 0, "first offset");
                     for (int i = 0; i < 12; ++i)
                         CHECK(off[i] % 256 == 0 && off[i + 1] >= off[i] + need[i] && off[i + 1] < off[i] + need[i] + 256, "array %d of the block", i);
+                    CHECK(p.passes == 0 && p.hist_bytes == 0 && p.off_hist == 0 && p.off_prefix == 0 && p.off_rank == 0 && p.off_value == 0,
+                          "the counting path plans no select");
+                    // the plan of the LMedS select: the counting path's plan word for word, then its own arrays, aligned and disjoint
+                    if (!host::epi_select_caps_ok(n, H)) continue;
+                    const host::EpiPlan q = host::epi_select_plan(n, H, forced, cu);
+                    CHECK(q.splits == p.splits && q.splits <= tiles && q.workgroups == p.workgroups && q.h_pad == p.h_pad && q.match_tiles == p.match_tiles &&
+                              q.reduce_blocks == p.reduce_blocks && q.solve_blocks == p.solve_blocks,
+                          "the select's launch plan is the score's");
+                    const size_t qoff[] = {q.off_raw1, q.off_raw2, q.off_pts, q.off_samples, q.off_F, q.off_partial, q.off_counts, q.off_state,
+                                           q.off_sym, q.off_cpart, q.off_mask, q.off_err};
+                    for (int i = 0; i < 12; ++i) CHECK(qoff[i] == off[i], "offset %d moved under the select's plan", i);
+                    CHECK(q.passes == EPI_SELECT_PASSES && q.passes * EPI_SELECT_BITS == 64 && (int64_t)q.passes * H <= EPI_MAX_WORK / n, "passes and their work");
+                    CHECK(q.hist_bytes == (size_t)q.splits * EPI_SELECT_DIGITS * q.h_pad * 4, "bytes of the partial histograms");
+                    const size_t soff[] = {p.scratch_bytes, q.off_hist, q.off_prefix, q.off_rank, q.off_value, q.scratch_bytes};
+                    const size_t sneed[] = {0, q.hist_bytes, (size_t)q.h_pad * 8, (size_t)q.h_pad * 4, (size_t)H * 8};
+                    CHECK(q.off_hist == p.scratch_bytes, "the select's arrays start where the counting path's block ends");
+                    for (int i = 0; i < 5; ++i)
+                        CHECK(soff[i] % 256 == 0 && soff[i + 1] >= soff[i] + sneed[i] && soff[i + 1] < soff[i] + sneed[i] + 256, "array %d of the select", i);
                 }
             }
+    // the caps of the select: 16 passes * H * n <= 2^35 on top of the others
+    CHECK(host::epi_select_caps_ok(1 << 11, EPI_MAX_H) && !host::epi_select_caps_ok((1 << 11) + 1, EPI_MAX_H) && host::epi_select_caps_ok(EPI_MAX_N, 1 << 11) &&
+              !host::epi_select_caps_ok(EPI_MAX_N, (1 << 11) + 1) && !host::epi_select_caps_ok(7, 1) && host::epi_select_caps_ok(5, 10, EPI_SAMPLE5) &&
+              !host::epi_select_caps_ok(INT64_MAX, INT64_MAX) && !host::epi_select_caps_ok(-1, -1) && host::epi_select_caps_ok(5000, 163840, EPI_SAMPLE5),
+          "caps of the select");
 }
 
 // ------------------------------------------------------------------ the error message is per thread
@@ -766,6 +789,7 @@ int canary(const char *which) {
 // normal_batch,n,B,cu -> "blocks groups_per" of normal_batch_grid (blocks = the stripes per pose), 1 <= B <= NORMAL_BATCH_MAX
 // mend,n,P,V,TC,cu -> "stripes tile_cols" of mend_grid
 // epi,n,H,forced_splits,cu -> "hyp_tile match_tile splits hyp_tiles match_tiles workgroups solve_blocks reduce_blocks bytes" of epi_plan
+// lmeds,n,H,forced_splits,cu -> the same of epi_select_plan, then "passes hist_bytes off_hist off_prefix off_rank off_value"
 // frame,implicit,grid_h,grid_w,n_tri,w,h,cu,tile_w,tile_h -> "tiles_x tiles plan_grid grid_wgs parked_wgs[0] parked_wgs[1] general_wgs large_wgs
 //   index_grid resolve_grid tile_bounds_bytes tile_lists_bytes" of frame_plan
 // queues,ALP_QUEUE_CAP text or '-' -> "cap small large cells small_b large_b cells_b": the start capacities
@@ -843,6 +867,20 @@ int plan_query(const char *q) {
         const host::EpiPlan p = host::epi_plan(nn, hh, forced, ecu);
         printf("%d %d %d %lld %lld %lld %lld %d %lld\n", p.hyp_tile, p.match_tile, p.splits, (long long)p.hyp_tiles, (long long)p.match_tiles,
                (long long)p.workgroups, (long long)p.solve_blocks, p.reduce_blocks, (long long)p.scratch_bytes);
+        return 0;
+    }
+    if (!strncmp(q, "lmeds,", 6)) {
+        long long nn = 0, hh = 0;
+        int forced = 0, ecu = 0;
+        if (sscanf(q + 6, "%lld,%lld,%d,%d", &nn, &hh, &forced, &ecu) != 4 || !host::epi_select_caps_ok(nn, hh) || forced < 0 || ecu < 1 ||
+            forced > (nn + EPI_MATCH_TILE - 1) / EPI_MATCH_TILE) {
+            fprintf(stderr, "bad plan query: %s\n", q);
+            return 2;
+        }
+        const host::EpiPlan p = host::epi_select_plan(nn, hh, forced, ecu);
+        printf("%d %d %d %lld %lld %lld %lld %d %lld %d %lld %lld %lld %lld %lld\n", p.hyp_tile, p.match_tile, p.splits, (long long)p.hyp_tiles,
+               (long long)p.match_tiles, (long long)p.workgroups, (long long)p.solve_blocks, p.reduce_blocks, (long long)p.scratch_bytes, p.passes,
+               (long long)p.hist_bytes, (long long)p.off_hist, (long long)p.off_prefix, (long long)p.off_rank, (long long)p.off_value);
         return 0;
     }
     if (!strncmp(q, "mend,", 5)) {

@@ -25,12 +25,16 @@ The two steps that ``image_match`` runs on every set of matches before it return
                          and chosen the same way in pixel coordinates, the refit projected onto the essential matrices
                          (``alp_essential_ransac``).  The inlier set is NOT cv2's: cv2's random stream and MAGSAC
                          scoring cannot be restated, so the algorithm is this project's own, plain inlier counting
-                         with the error measure of cv2's classic ``FM_RANSAC``
+                         with the error measure of cv2's classic ``FM_RANSAC``; ``ransac_method="LMEDS"`` (gcp.py:160-161)
+                         replaces the fixed threshold by least median of squares over the same hypotheses: the r-th
+                         smallest error of every hypothesis by an exact radix select on the device
+                         (``alp_epipolar_lmeds`` / ``alp_essential_lmeds``), the bound from the smallest one;
+                         ``filter_matches`` forwards it with its ``**ransac``
 * ``filter_spatial``     ``_filter_spatial`` (gcp.py:282-357), bit for bit (``alp_grid_thin``)
 * ``filter_matches``     lines 507-544 as a whole: points -> the DataFrame u_org, v_org, u_sim, v_sim
 
 Detection (``detectAndCompute``), the essential-matrix filter's guess of a focal length that nobody
-gave it (gcp.py:206-220), cv2's USAC / MAGSAC / LMedS scoring and the learned matchers behind
+gave it (gcp.py:206-220), cv2's USAC / MAGSAC scoring and the learned matchers behind
 ``vismatch`` stay with the reference: cv2 is neither imported nor needed here.  ``set_gcp`` accepts, besides the reference's
 ``reverse_proj`` DataFrame, the device-resident ``alproj_amd.project.ReverseProjection``: the
 (u_sim, v_sim) -> (x, y, z) join then becomes one gather from the coordinate image in HBM
@@ -129,8 +133,12 @@ def match_keypoints(pts_org, des_org, pts_sim, des_sim, ratio=0.7):
     return np.float32(pts_org[query_idx]).astype("int32"), np.float32(pts_sim[train_idx]).astype("int32")
 
 
+RANSAC_METHODS = ("RANSAC", "LMEDS")
+
+
 def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypotheses=16384, seed=0, refits=4, samples=None,
-                     return_model=False, focal_length=None, principal_point=None, image_size=None):
+                     return_model=False, focal_length=None, principal_point=None, image_size=None, *, ransac_method="RANSAC",
+                     quantile=0.5, min_threshold=1.0):
     """``_filter_geometric`` (reference gcp.py:160-279) for ``method="fundamental"`` and ``method="essential"``, on the device: a
     bool mask of the matches that agree with one fundamental or essential matrix.
 
@@ -157,9 +165,25 @@ def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypothese
     all True, fewer than 8 points (``"essential"``: 5) all True, an unknown method the reference's ``ValueError``; fewer than 8
     (5) inliers anywhere give all True as well (cv2 returning no mask, gcp.py:249-250, 270-271).
 
+    ``ransac_method`` (keyword only, case-insensitive; reference gcp.py:160-161, 239-245, 260-266): ``"RANSAC"``, the default, is
+    the inlier counting at ``threshold`` described above.  ``"LMEDS"`` is least median of squares, which needs no threshold and
+    ignores ``threshold`` as cv2 does: the value of a hypothesis is the r-th smallest error over all n matches, r = min(n,
+    max(m + 1, ceil(quantile * n))) with m = 8 (5) the size of a minimal sample (below n = 2 (m + 1) that is m + 1 whatever the
+    quantile); the hypothesis with the smallest value v is chosen (the lowest index on a tie), a match is an inlier iff its
+    error is at most b^2 = max(scale^2 * v, min_threshold^2) with scale = 2.5 * (1 / Phi^-1((1 + quantile) / 2)) * (1 + 5 / (n -
+    m)) (Rousseeuw and Leroy's robust standard deviation, 1.4826 at the median), and the refit on the inliers is kept while it
+    strictly lowers the value (``alp_epipolar_lmeds`` / ``alp_essential_lmeds``; not cv2's LMedS either).  ``quantile`` in
+    (0, 1]: below the inlier share when more than half of the matches are outliers.  ``min_threshold`` (pixels, finite, >= 0):
+    the floor of the bound, 1 px by default because ``astype("int32")`` (gcp.py:69-70) moves every coordinate by up to a pixel.
+    With n <= m every match is kept before any device call; a smallest value that is not finite keeps every match.
+    ``"USAC_MAGSAC"`` and ``"USAC_DEFAULT"`` raise ``NotImplementedError`` (cv2's scoring cannot be restated), anything else
+    ``ValueError``: the reference's silent fall-back to MAGSAC is not repeated.
+
     ``return_model=True`` returns (mask, F, info): F (3, 3) in pixel coordinates with b^T F a = 0 for a = (x1, y1, 1),
     b = (x2, y2, 1), or None when no model was fitted, and the info dict of ``_lib.epipolar_ransac``; for ``"essential"`` info
-    also holds ``"E"`` = K^T F K and ``chosen`` counts slots, sample * 10 + slot."""
+    also holds ``"E"`` = K^T F K and ``chosen`` counts slots, sample * 10 + slot.  With ``"LMEDS"`` info is that of
+    ``_lib.epipolar_lmeds`` and also holds ``method``, ``rank``, ``value``, ``final_value``, ``bound`` (pixels) and
+    ``refit_values``."""
     pts1 = np.asarray(pts1, dtype=np.float64)
     pts2 = np.asarray(pts2, dtype=np.float64)
 
@@ -177,7 +201,20 @@ def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypothese
             "Available: 'essential', 'fundamental', 'none'"
         )
     essential = method_lower == "essential"
-    if len(pts1) < (5 if essential else 8):
+    ransac_upper = str(ransac_method).upper()
+    if ransac_upper in ("USAC_MAGSAC", "USAC_DEFAULT"):
+        raise NotImplementedError(f"ransac_method='{ransac_method}': cv2's USAC / MAGSAC scoring cannot be restated and stays with the "
+                                  "reference; available here: 'RANSAC', 'LMEDS'")
+    if ransac_upper not in RANSAC_METHODS:
+        raise ValueError(f"Unknown ransac_method '{ransac_method}'. Available: 'RANSAC', 'LMEDS'")
+    lmeds = ransac_upper == "LMEDS"
+    m = 5 if essential else 8
+    if lmeds:
+        if not (isinstance(quantile, (int, float)) and 0.0 < quantile <= 1.0):
+            raise ValueError("quantile must lie in (0, 1]")
+        if not (np.isfinite(min_threshold) and min_threshold >= 0):
+            raise ValueError("min_threshold must be finite and not negative")
+    if len(pts1) < m or (lmeds and len(pts1) <= m):
         return result(np.ones(len(pts1), dtype=bool))
     if essential and focal_length is None:
         raise NotImplementedError("outlier_filter='essential' without a focal length: the guess 'focal length = image width' stays "
@@ -193,7 +230,17 @@ def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypothese
         raise ValueError("hypotheses must be at least 1")
     if not 0 <= int(refits) <= _lib.EPI_MAX_REFITS:
         raise ValueError(f"refits must be 0..{_lib.EPI_MAX_REFITS}")
+    if lmeds:
+        rank, scale2 = _lib.lmeds_rank(len(pts1), m, quantile), _lib.lmeds_scale2(len(pts1), m, quantile)
+        floor2 = float(min_threshold) * float(min_threshold)
+
+        def lmeds_info(r):
+            return dict(r["info"], method="LMEDS", rank=rank, value=r["value"], final_value=r["final_value"], bound=r["bound"],
+                        refit_values=r["refit_values"])
     if not essential:
+        if lmeds:
+            r = _lib.epipolar_lmeds(pts1, pts2, rank, scale2, floor2, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
+            return result(r["mask"], r["F"], lmeds_info(r))
         r = _lib.epipolar_ransac(pts1, pts2, threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
         return result(r["mask"], r["F"], r["info"])
     if principal_point is None:
@@ -207,7 +254,11 @@ def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypothese
     K = _lib._epi_K(focal_length, principal_point)
     if samples is not None:
         samples = _lib._epi_samples(samples, len(pts1), 5)
-    r = _lib.essential_ransac(pts1, pts2, K[0], K[1:], threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
+    if lmeds:
+        r = _lib.essential_lmeds(pts1, pts2, K[0], K[1:], rank, scale2, floor2, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
+        r["info"] = lmeds_info(r)
+    else:
+        r = _lib.essential_ransac(pts1, pts2, K[0], K[1:], threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
     Km = np.array([[K[0], 0.0, K[1]], [0.0, K[0], K[2]], [0.0, 0.0, 1.0]])
     return result(r["mask"], r["F"], dict(r["info"], E=Km.T @ r["F"] @ Km))
 
@@ -264,7 +315,8 @@ def filter_matches(pts1, pts2, image_size, outlier_filter="fundamental", thresho
     """``image_match`` from its line 507 to 544 (reference gcp.py), given the points ``match_keypoints`` returns: the geometric
     filter, then the spatial thinning on ``pts1``, then the DataFrame ``u_org, v_org, u_sim, v_sim`` (the empty frame with those
     columns when nothing is left).  ``image_size`` is (width, height) of the photograph, or None when no thinning is asked for;
-    ``**ransac`` goes to ``filter_geometric`` (hypotheses, seed, refits, samples).  ``params``: the camera parameters the
+    ``**ransac`` goes to ``filter_geometric`` (hypotheses, seed, refits, samples, and ransac_method, quantile, min_threshold: the
+    reference's ``ransac_method`` argument, gcp.py:160-161).  ``params``: the camera parameters the
     simulated image was rendered from; ``outlier_filter="essential"`` takes its focal length and principal point from them as
     ``image_match`` does (gcp.py:466-474): f = (w / 2) / tan(fov / 2) from ``fov`` (degrees) and ``w``, (cx, cy) from ``cx``
     and ``cy``, else (w / 2, h / 2)."""

@@ -779,6 +779,49 @@ int alp_essential_ransac(const double *p1, const double *p2, int64_t n, const in
                          uint64_t seed, const double K[3], double threshold, int refits, int splits, double F[9],
                          uint8_t *mask, int64_t info[24]);
 
+/* The same two filters with ransac_method="LMEDS", src/alproj/gcp.py:160-279 (the argument at :160-161, handed to cv2 at :239-245
+ * and :260-266): least median of squares (Rousseeuw 1984), which needs no threshold.  Not cv2's LMedS: an algorithm of the
+ * library's own over the hypotheses, the error e and the refit defined above, so that numpy can restate it exactly.
+ *     value of F     v = the rank-th smallest (rank is 1-based) of e over all n matches, a NaN e (and every e of a NaN F) counting
+ *                    as +inf.  e is then a non-negative double or +inf, and such doubles order as their bit patterns do as
+ *                    unsigned 64-bit integers: the device selects on the bits, exactly, and v is one of the e bit for bit.
+ *     choice         the hypothesis (the slot h * 10 + slot) with the smallest v, the lowest index on a tie; a smallest v that is
+ *                    not finite keeps every match (mask all 1, info[5] = 1) and runs no refit.
+ *     bound          b2 = max(scale2 * v, floor2): one multiplication, then the larger; a match is an inlier iff e <= b2.
+ *     refit          up to `refits` (0..8) times: the refit of alp_epipolar_ransac (alp_essential_ransac) on the inliers of the
+ *                    current F at its bound, the value of the candidate; the candidate replaces the current F, and its value and
+ *                    bound the current ones, only when its value is strictly smaller, otherwise the loop stops.  mask[n]: the
+ *                    inliers of the final F at its own bound.
+ * The caller forms rank, scale2 and floor2; the Python layer takes rank = min(n, max(m + 1, ceil(quantile * n))) with m = 8 (5),
+ * scale2 = (2.5 * (1 / Phi^-1((1 + quantile) / 2)) * (1 + 5 / (n - m)))^2 (Rousseeuw and Leroy's robust standard deviation; 1.4826
+ * at the median) and floor2 = min_threshold^2.  There is no threshold argument.
+ * Caps: those of the sibling entry points, and passes * H * n <= 2^35 with passes = 16 (every pass of the select forms every error
+ * again; the essential filter: 10 * H for H); rank in 1..n; scale2 and floor2 finite and >= 0; refits 0..8; otherwise ALP_EINVAL
+ * before anything is uploaded, as for NULL arrays, a sample index outside [0, n) and splits above the number of match tiles.
+ *
+ * alp_epipolar_select: value[H], the rank-th smallest e of every F[H][9] (+inf for a NaN F).  A radix select on the bits of e, the
+ *   most significant 4-bit digit first; no H x n array is formed and the result does not depend on splits (0 = the launch plan's
+ *   choice, > 0 forces it).  info[8], may be NULL: hypothesis tile, match tile, splits used, workgroups, device bytes of the call,
+ *   match tiles, passes, bytes of the partial histograms.
+ * alp_epipolar_lmeds / alp_essential_lmeds: the whole filter, enqueued at once with no host round trip between its stages; samples,
+ *   seed, K, F[9] and mask[n] as for alp_epipolar_ransac / alp_essential_ransac.  info[24], may be NULL, in alp_epipolar_ransac's
+ *   layout with inlier counts at the bound of the matrix in question where the counts were: [0] chosen hypothesis (slot), [1] the
+ *   inliers of the chosen F at its bound, [2] of the final F at its bound, [3] refits run, [4] refits kept, [5] 1 when all matches
+ *   were kept, [6] hypothesis tile, [7] match tile, [8] splits, [9] workgroups of a pass of the select, [10] device bytes, [11]
+ *   workgroups of the refit's reductions, [12..19] the inliers of each refit's candidate at the candidate's own bound (-1: not run;
+ *   0 when its value is not finite), [20] passes of the select over the hypotheses, [21] passes of the select over the errors of
+ *   one F, [22] match tiles, [23] bytes of the partial histograms.  stats[12], may be NULL: [0] the chosen value, [1] the final
+ *   value, [2] the final b2, [3..10] the value of each refit's candidate (NaN: not run), [11] NaN.  When every match was kept,
+ *   [0] = [1] = +inf and [2] is not meaningful. */
+int alp_epipolar_select(const double *p1, const double *p2, int64_t n, const double *F, int64_t H, int64_t rank, int splits,
+                        double *value, int64_t info[8]);
+int alp_epipolar_lmeds(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, uint64_t seed,
+                       int64_t rank, double scale2, double floor2, int refits, int splits, double F[9], uint8_t *mask,
+                       int64_t info[24], double stats[12]);
+int alp_essential_lmeds(const double *p1, const double *p2, int64_t n, const int32_t *samples, int64_t H, uint64_t seed,
+                        const double K[3], int64_t rank, double scale2, double floor2, int refits, int splits, double F[9],
+                        uint8_t *mask, int64_t info[24], double stats[12]);
+
 /* The spatial thinning of image_match, src/alproj/gcp.py:282-357 (_filter_spatial): mask[n] keeps one point per distinct value
  * of cell_id[n].  dist == NULL: the lowest index of each cell (selection="first").  Otherwise the lowest dist of each cell, the
  * lowest index on an equal dist (selection="center": pandas' idxmin); dist must be >= 0 and not NaN.  The table is indexed by
