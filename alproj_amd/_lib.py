@@ -1194,14 +1194,19 @@ _c_i32p = ctypes.POINTER(ctypes.c_int32)
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 
 
-def epipolar_samples(n, hypotheses, seed=0):
-    """alp_epipolar_samples: (H, 8) int32, every row 8 distinct indices in [0, n); a function of (n, H, seed) alone."""
+def _epi_draw(width, n, hypotheses, seed):
     hypotheses = int(hypotheses)
     if hypotheses < 1:
         raise ValueError("hypotheses must be at least 1")
-    out = np.empty((hypotheses, 8), dtype=np.int32)
-    check(lib().alp_epipolar_samples(int(n), hypotheses, int(seed) & (2 ** 64 - 1), out.ctypes.data_as(_c_i32p)))
+    out = np.empty((hypotheses, width), dtype=np.int32)
+    entry = lib().alp_epipolar_samples if width == 8 else lib().alp_epipolar_samples5
+    check(entry(int(n), hypotheses, int(seed) & (2 ** 64 - 1), out.ctypes.data_as(_c_i32p)))
     return out
+
+
+def epipolar_samples(n, hypotheses, seed=0):
+    """alp_epipolar_samples: (H, 8) int32, every row 8 distinct indices in [0, n); a function of (n, H, seed) alone."""
+    return _epi_draw(8, n, hypotheses, seed)
 
 
 def epipolar_solve8(p1, p2, samples):
@@ -1236,40 +1241,56 @@ def epipolar_mask(p1, p2, F, threshold):
     return mask.astype(bool), err
 
 
-def _epi_ransac_info(info):
+_EPI_CRITERIA = {"ransac": (float,), "lmeds": (int, float, float)}       # the criterion's numbers as the entry points take them
+
+
+def _epi_filter(kind, p1, p2, K, criterion, hypotheses, seed, refits, samples, splits):
+    """A whole-filter call -> its result dict.  kind: "ransac" with criterion (threshold,), or "lmeds" with (rank, scale2,
+    floor2), which also returns its stats; K: None, or (focal_length, principal_point) of the essential filters, whose samples
+    are 5 wide and not 8.  The two choose the entry point."""
+    if len(criterion) != len(_EPI_CRITERIA[kind]):
+        raise ValueError(f"a {kind} criterion holds {len(_EPI_CRITERIA[kind])} numbers, not {len(criterion)}")
+    p1, p2 = _epi_points(p1, p2)
+    if K is not None:
+        K = _epi_K(*K)
+    if samples is not None:
+        samples = _epi_samples(samples, len(p1), 8 if K is None else 5)
+        hypotheses = len(samples)
+    lmeds = kind == "lmeds"
+    entry = getattr(lib(), f"alp_{'epipolar' if K is None else 'essential'}_{kind}")
+    F = np.empty((3, 3), dtype=np.float64)
+    mask = np.empty(len(p1), dtype=np.uint8)
+    info = (_c_i64 * 24)()
+    stats = (_c_double * 12)()
+    args = [as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None, int(hypotheses),
+            int(seed) & (2 ** 64 - 1)]
+    args += [as_dp(K)] if K is not None else []
+    args += [as_type(v) for as_type, v in zip(_EPI_CRITERIA[kind], criterion)]
+    args += [int(refits), int(splits), as_dp(F), mask.ctypes.data_as(_c_u8p), info] + ([stats] if lmeds else [])
+    check(entry(*args))
     v = [int(x) for x in info]
     run = v[3]
-    return {"chosen": v[0], "chosen_count": v[1], "final_count": v[2], "refits_run": run, "refits_kept": v[4],
-            "keep_all": bool(v[5]), "hyp_tile": v[6], "match_tile": v[7], "splits": v[8], "workgroups": v[9],
-            "scratch_bytes": v[10], "reduce_blocks": v[11], "refit_counts": v[12:12 + run]}
+    d = {"chosen": v[0], "chosen_count": v[1], "final_count": v[2], "refits_run": run, "refits_kept": v[4],
+         "keep_all": bool(v[5]), "hyp_tile": v[6], "match_tile": v[7], "splits": v[8], "workgroups": v[9],
+         "scratch_bytes": v[10], "reduce_blocks": v[11], "refit_counts": v[12:12 + run]}
+    if not lmeds:
+        return {"F": F, "mask": mask.astype(bool), "info": d}
+    s = [float(x) for x in stats]
+    d.update(passes=v[20], passes_single=v[21], match_tiles=v[22], hist_bytes=v[23])
+    return {"F": F, "mask": mask.astype(bool), "info": d, "value": s[0], "final_value": s[1],
+            "bound": float("nan") if d["keep_all"] else math.sqrt(s[2]), "refit_values": s[3:3 + run]}
 
 
 def epipolar_ransac(p1, p2, threshold, hypotheses=16384, seed=0, refits=4, samples=None, splits=0):
     """alp_epipolar_ransac: the whole geometric filter in one device loop -> dict F (3, 3), mask (n,) bool, info (chosen,
     chosen_count, final_count, refits_run, refits_kept, keep_all, refit_counts, and the launch plan)."""
-    p1, p2 = _epi_points(p1, p2)
-    if samples is not None:
-        samples = _epi_samples(samples, len(p1))
-        hypotheses = len(samples)
-    hypotheses = int(hypotheses)
-    F = np.empty((3, 3), dtype=np.float64)
-    mask = np.empty(len(p1), dtype=np.uint8)
-    info = (_c_i64 * 24)()
-    check(lib().alp_epipolar_ransac(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
-                                    hypotheses, int(seed) & (2 ** 64 - 1), float(threshold), int(refits), int(splits), as_dp(F),
-                                    mask.ctypes.data_as(_c_u8p), info))
-    return {"F": F, "mask": mask.astype(bool), "info": _epi_ransac_info(info)}
+    return _epi_filter("ransac", p1, p2, None, (threshold,), hypotheses, seed, refits, samples, splits)
 
 
 def epipolar_samples5(n, hypotheses, seed=0):
     """alp_epipolar_samples5: (H, 5) int32, every row 5 distinct indices in [0, n); a function of (n, H, seed) alone, and another
     stream than the 8-wide rows of the same seed."""
-    hypotheses = int(hypotheses)
-    if hypotheses < 1:
-        raise ValueError("hypotheses must be at least 1")
-    out = np.empty((hypotheses, 5), dtype=np.int32)
-    check(lib().alp_epipolar_samples5(int(n), hypotheses, int(seed) & (2 ** 64 - 1), out.ctypes.data_as(_c_i32p)))
-    return out
+    return _epi_draw(5, n, hypotheses, seed)
 
 
 def epipolar_solve5(p1, p2, samples, focal_length, principal_point):
@@ -1288,19 +1309,7 @@ def epipolar_solve5(p1, p2, samples, focal_length, principal_point):
 def essential_ransac(p1, p2, focal_length, principal_point, threshold, hypotheses=16384, seed=0, refits=4, samples=None, splits=0):
     """alp_essential_ransac: the essential-matrix filter in one device loop -> dict F (3, 3) in pixel coordinates, mask (n,) bool,
     info as for epipolar_ransac; ``chosen`` is sample * 10 + slot."""
-    p1, p2 = _epi_points(p1, p2)
-    K = _epi_K(focal_length, principal_point)
-    if samples is not None:
-        samples = _epi_samples(samples, len(p1), 5)
-        hypotheses = len(samples)
-    hypotheses = int(hypotheses)
-    F = np.empty((3, 3), dtype=np.float64)
-    mask = np.empty(len(p1), dtype=np.uint8)
-    info = (_c_i64 * 24)()
-    check(lib().alp_essential_ransac(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
-                                     hypotheses, int(seed) & (2 ** 64 - 1), as_dp(K), float(threshold), int(refits), int(splits), as_dp(F),
-                                     mask.ctypes.data_as(_c_u8p), info))
-    return {"F": F, "mask": mask.astype(bool), "info": _epi_ransac_info(info)}
+    return _epi_filter("ransac", p1, p2, (focal_length, principal_point), (threshold,), hypotheses, seed, refits, samples, splits)
 
 
 EPI_SELECT_PASSES = 16
@@ -1335,52 +1344,19 @@ def epipolar_select(p1, p2, F, rank, splits=0):
     return value, dict(zip(EPI_SELECT_INFO, (int(v) for v in info)))
 
 
-def _epi_lmeds_result(F, mask, info, stats):
-    v = [int(x) for x in info]
-    s = [float(x) for x in stats]
-    d = _epi_ransac_info(info)
-    d.update(passes=v[20], passes_single=v[21], match_tiles=v[22], hist_bytes=v[23])
-    return {"F": F, "mask": mask.astype(bool), "info": d, "value": s[0], "final_value": s[1],
-            "bound": float("nan") if d["keep_all"] else math.sqrt(s[2]), "refit_values": s[3:3 + d["refits_run"]]}
-
-
 def epipolar_lmeds(p1, p2, rank, scale2, floor2=1.0, hypotheses=16384, seed=0, refits=4, samples=None, splits=0):
     """alp_epipolar_lmeds: the least-median-of-squares filter in one device loop -> dict F (3, 3), mask (n,) bool, info (as for
     epipolar_ransac, the counts taken at each matrix' own bound, plus passes, passes_single, match_tiles, hist_bytes), value (of
     the chosen hypothesis), final_value, bound (pixels: the square root of the final b2; NaN when every match was kept) and
     refit_values (of every refit run, the rejected last one included)."""
-    p1, p2 = _epi_points(p1, p2)
-    if samples is not None:
-        samples = _epi_samples(samples, len(p1))
-        hypotheses = len(samples)
-    hypotheses = int(hypotheses)
-    F = np.empty((3, 3), dtype=np.float64)
-    mask = np.empty(len(p1), dtype=np.uint8)
-    info = (_c_i64 * 24)()
-    stats = (_c_double * 12)()
-    check(lib().alp_epipolar_lmeds(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
-                                   hypotheses, int(seed) & (2 ** 64 - 1), int(rank), float(scale2), float(floor2), int(refits),
-                                   int(splits), as_dp(F), mask.ctypes.data_as(_c_u8p), info, stats))
-    return _epi_lmeds_result(F, mask, info, stats)
+    return _epi_filter("lmeds", p1, p2, None, (rank, scale2, floor2), hypotheses, seed, refits, samples, splits)
 
 
 def essential_lmeds(p1, p2, focal_length, principal_point, rank, scale2, floor2=1.0, hypotheses=16384, seed=0, refits=4, samples=None,
                     splits=0):
     """alp_essential_lmeds: epipolar_lmeds over the ten slots of every five-point sample; ``chosen`` is sample * 10 + slot."""
-    p1, p2 = _epi_points(p1, p2)
-    K = _epi_K(focal_length, principal_point)
-    if samples is not None:
-        samples = _epi_samples(samples, len(p1), 5)
-        hypotheses = len(samples)
-    hypotheses = int(hypotheses)
-    F = np.empty((3, 3), dtype=np.float64)
-    mask = np.empty(len(p1), dtype=np.uint8)
-    info = (_c_i64 * 24)()
-    stats = (_c_double * 12)()
-    check(lib().alp_essential_lmeds(as_dp(p1), as_dp(p2), len(p1), samples.ctypes.data_as(_c_i32p) if samples is not None else None,
-                                    hypotheses, int(seed) & (2 ** 64 - 1), as_dp(K), int(rank), float(scale2), float(floor2),
-                                    int(refits), int(splits), as_dp(F), mask.ctypes.data_as(_c_u8p), info, stats))
-    return _epi_lmeds_result(F, mask, info, stats)
+    return _epi_filter("lmeds", p1, p2, (focal_length, principal_point), (rank, scale2, floor2), hypotheses, seed, refits,
+                       samples, splits)
 
 
 def grid_thin(cell_id, dist=None):

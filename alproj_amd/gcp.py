@@ -231,36 +231,33 @@ def filter_geometric(pts1, pts2, method="fundamental", threshold=10.0, hypothese
     if not 0 <= int(refits) <= _lib.EPI_MAX_REFITS:
         raise ValueError(f"refits must be 0..{_lib.EPI_MAX_REFITS}")
     if lmeds:
-        rank, scale2 = _lib.lmeds_rank(len(pts1), m, quantile), _lib.lmeds_scale2(len(pts1), m, quantile)
-        floor2 = float(min_threshold) * float(min_threshold)
-
-        def lmeds_info(r):
-            return dict(r["info"], method="LMEDS", rank=rank, value=r["value"], final_value=r["final_value"], bound=r["bound"],
-                        refit_values=r["refit_values"])
-    if not essential:
-        if lmeds:
-            r = _lib.epipolar_lmeds(pts1, pts2, rank, scale2, floor2, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
-            return result(r["mask"], r["F"], lmeds_info(r))
-        r = _lib.epipolar_ransac(pts1, pts2, threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
-        return result(r["mask"], r["F"], r["info"])
-    if principal_point is None:
-        # reference gcp.py:223-229, verbatim
-        if image_size is not None:
-            principal_point = (image_size[0] / 2, image_size[1] / 2)
-        else:
-            cx = (pts1[:, 0].max() + pts1[:, 0].min()) / 2
-            cy = (pts1[:, 1].max() + pts1[:, 1].min()) / 2
-            principal_point = (cx, cy)
-    K = _lib._epi_K(focal_length, principal_point)
-    if samples is not None:
-        samples = _lib._epi_samples(samples, len(pts1), 5)
-    if lmeds:
-        r = _lib.essential_lmeds(pts1, pts2, K[0], K[1:], rank, scale2, floor2, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
-        r["info"] = lmeds_info(r)
+        rank = _lib.lmeds_rank(len(pts1), m, quantile)
+        criterion = (rank, _lib.lmeds_scale2(len(pts1), m, quantile), float(min_threshold) * float(min_threshold))
     else:
-        r = _lib.essential_ransac(pts1, pts2, K[0], K[1:], threshold, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
-    Km = np.array([[K[0], 0.0, K[1]], [0.0, K[0], K[2]], [0.0, 0.0, 1.0]])
-    return result(r["mask"], r["F"], dict(r["info"], E=Km.T @ r["F"] @ Km))
+        criterion = (threshold,)
+    camera = ()
+    if essential:
+        if principal_point is None:
+            # reference gcp.py:223-229, verbatim
+            if image_size is not None:
+                principal_point = (image_size[0] / 2, image_size[1] / 2)
+            else:
+                cx = (pts1[:, 0].max() + pts1[:, 0].min()) / 2
+                cy = (pts1[:, 1].max() + pts1[:, 1].min()) / 2
+                principal_point = (cx, cy)
+        K = _lib._epi_K(focal_length, principal_point)
+        camera = (K[0], K[1:])
+    fn = {(False, False): _lib.epipolar_ransac, (False, True): _lib.epipolar_lmeds, (True, False): _lib.essential_ransac,
+          (True, True): _lib.essential_lmeds}[essential, lmeds]
+    r = fn(pts1, pts2, *camera, *criterion, hypotheses=hypotheses, seed=seed, refits=refits, samples=samples)
+    info = r["info"]
+    if lmeds:
+        info = dict(info, method="LMEDS", rank=rank, value=r["value"], final_value=r["final_value"], bound=r["bound"],
+                    refit_values=r["refit_values"])
+    if essential:
+        Km = np.array([[K[0], 0.0, K[1]], [0.0, K[0], K[2]], [0.0, 0.0, 1.0]])
+        info = dict(info, E=Km.T @ r["F"] @ Km)
+    return result(r["mask"], r["F"], info)
 
 
 def _spatial_cells(pts, grid_size, image_size):

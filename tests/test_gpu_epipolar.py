@@ -13,6 +13,8 @@ selection, the refit loop and its stop, the final mask        test_ransac_equals
 the device's own draws, too few inliers                       test_ransac_own_draws, test_ransac_keeps_everything_without_eight_inliers
 ties and order in the thinning, the rounded root              test_filter_spatial_equals_the_reference, test_grid_thin_edges
 lines 507-544 as a whole, refusals of the C entry points      test_filter_matches_reproduces_the_reference_lines, test_entry_point_refusals
+the one driver of the four whole filters: text and order      test_whole_filters_refuse_alike
+of its refusals
 
 What makes no device call (refusals and edge cases of the Python layer, selection="random") needs no GPU: tests/test_epipolar_cases.py.
 """
@@ -387,3 +389,57 @@ def test_entry_point_refusals(L):
     refused(lib.alp_grid_thin(cell.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None, -1, U8), "n must be 0..2^30")
     # every output of the whole filter may be NULL
     assert lib.alp_epipolar_ransac(P, P, 16, None, 4, 0, 3.0, 4, 0, None, None, None) == 0
+
+
+FILTER_ENTRY_POINTS = {          # name -> (minimal sample, the text of its H range)
+    "alp_epipolar_ransac": (8, "2^20"),
+    "alp_essential_ransac": (5, "2^20 / 10"),
+    "alp_epipolar_lmeds": (8, "2^20"),
+    "alp_essential_lmeds": (5, "2^20 / 10"),
+}
+
+
+@pytest.mark.parametrize("name", FILTER_ENTRY_POINTS)
+def test_whole_filters_refuse_alike(L, name):
+    """The four whole filters share one driver: each refuses the common bad arguments with ALP_EINVAL and the one message, under
+    its own name, before anything is launched; and of several bad arguments it names the first in the order points, rank
+    (LMedS), K (essential), the criterion's numbers, refits, splits, samples."""
+    lib = L.lib()
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+    width, h_range = FILTER_ENTRY_POINTS[name]
+    p = np.ascontiguousarray(np.random.default_rng(0).uniform(0, 100, (513, 2)))
+    P = p.ctypes.data_as(dp)
+    lmeds, essential = name.endswith("lmeds"), "essential" in name
+    s = np.tile(np.arange(width, dtype=np.int32), (4, 1))
+    s[2, 3] = 16
+    bad_samples = s.ctypes.data_as(ip)
+
+    def refused(text, p1=P, n=16, samples=None, H=4, refits=4, splits=0, rank=width + 1, focal=800.0, number=None):
+        K = [np.array([focal, 50.0, 50.0]).ctypes.data_as(dp)] if essential else []
+        # the criterion's numbers: (rank, scale2, floor2) or the threshold; `number` replaces scale2 or the threshold
+        criterion = [rank, 14.0 if number is None else number, 1.0] if lmeds else [3.0 if number is None else number]
+        rc = getattr(lib, name)(p1, P, n, samples, H, 0, *K, *criterion, refits, splits, None, None, None, *([None] if lmeds else []))
+        assert rc == -1, (rc, text)
+        assert lib.alp_last_error().decode() == f"{name}: {text}"
+
+    refused(f"n = {width - 1}, must be {width}..2^20", n=width - 1)
+    refused(f"H = 0, must be 1..{h_range}", H=0)
+    refused("refits must be 0..8", refits=9)
+    refused("splits = 3, but 513 matches are only 2 tiles of 512", n=513, splits=3)
+    refused("sample 3 of hypothesis 2 is 16, outside 0..15", samples=bad_samples)
+    refused("NULL input", p1=None)
+    # the order: every argument after the one named is bad as well
+    later = dict(samples=bad_samples)
+    refused("splits = 3, but 16 matches are only 1 tiles of 512", splits=3, **later)
+    later.update(splits=3)
+    refused("refits must be 0..8", refits=9, **later)
+    later.update(refits=9)
+    refused(("scale2" if lmeds else "threshold") + " must be finite and not negative", number=float("nan"), **later)
+    later.update(number=float("nan"))
+    if essential:
+        refused("the focal length must be finite and positive", focal=-1.0, **later)
+        later.update(focal=-1.0)
+    if lmeds:
+        refused("rank = 0, must be 1..n = 16", rank=0, **later)
+        later.update(rank=0)
+    refused(f"n = {width - 1}, must be {width}..2^20", n=width - 1, **later)
