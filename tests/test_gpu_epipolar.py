@@ -10,6 +10,7 @@ partial tiles of matches and hypotheses, the split merge      test_score_launch_
                                                               test_score_beyond_one_wave_of_workgroups
 NaN hypotheses, a match exactly on the threshold              test_score_edges
 selection, the refit loop and its stop, the final mask        test_ransac_equals_the_restatement (and the truth), test_ransac_large_n
+the final F itself, the solve and the refit case by case      test_ransac_equals_the_restatement, tests/test_gpu_epipolar_linalg.py
 the device's own draws, too few inliers                       test_ransac_own_draws, test_ransac_keeps_everything_without_eight_inliers
 ties and order in the thinning, the rounded root              test_filter_spatial_equals_the_reference, test_grid_thin_edges
 lines 507-544 as a whole, refusals of the C entry points      test_filter_matches_reproduces_the_reference_lines, test_entry_point_refusals
@@ -28,6 +29,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import epipolar_cases as ec  # noqa: E402
+import linalg_cases as lg  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -218,7 +220,13 @@ def test_ransac_equals_the_restatement(L, n, n_out, threshold, seed):
     assert not (np.abs(e - threshold ** 2) <= 0.01 * threshold ** 2).any()
     got = L.epipolar_ransac(p1, p2, threshold, samples=samples)
     assert_ransac_equal(got, want, f"scene({n}, {n_out})")
-    print("distance of the final F to the restatement's", ec.sign_distance(got["F"], want["F"])[0])
+    # the final F itself: the last kept refit against the extended-precision refit on the set it summed over, or the chosen
+    # sample's solve against the extended-precision solve, at the tolerance rule of linalg_cases
+    ref, kappa, family = lg.whole_filter_reference(p1, p2, samples, want, threshold)
+    d = ec.sign_distance(got["F"], ref["F"])[0]
+    print("distance of the final F to the restatement's", ec.sign_distance(got["F"], want["F"])[0], "to the exact one", d,
+          "allowed", lg.tolerance(family, kappa), family)
+    assert d <= lg.tolerance(family, kappa)
     np.testing.assert_array_equal(got["mask"], ec.inliers(got["F"], p1, p2, threshold))
     assert got["mask"][~out].all()
     kept = out & got["mask"]
